@@ -12,6 +12,11 @@ subtraction) is part of every timed step.
     python bench.py --gpus N --steps K --warmup W          # N > 1 without a launcher: spawns its own N ranks (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # or under the launcher: ranks read RANK / WORLD_SIZE / MASTER_*
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full  # + parity, sustained pass, roofline, secondary configs, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + what the last timed step computed, DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step); everything else it can measure
+or check runs only with --full (the --no-* options and --sustain-seconds then pick from that set).
 """
 import argparse
 import json
@@ -197,7 +202,14 @@ def main():
                     help="kitti: the reference's KITTI training loss (fb_weight 0.2, occ_weight 12.4, mask_occlusion fb) with flow "
                          "heads rescaled so that the occlusion masks are mixed at every level (SURVEY 8(d) config 2)")
     ap.add_argument("--sustain-seconds", type=float, default=5.0,
-                    help="after the K timed steps, keep stepping this long and report it as sustained_value (0 = skip)")
+                    help="--full: after the K timed steps, keep stepping this long and report it as sustained_value (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: step-1 parity with the CPU oracle, the "
+                         "sustained pass, the roofline, the fp32-MFMA re-measurement, the secondary configs, the CPU baseline and "
+                         "(N > 1) the comm record; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): the loss, the "
+                         "flow pyramids and a fixed seeded sample of the updated parameters and of the gradients (dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -263,7 +275,7 @@ def main():
                for _ in range(NBATCH)]
     lr = 1e-4
     parity = None
-    if rank == 0 and world == 1 and not args.no_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_parity:
         parity = measure_parity(eng, batches[0])      # step-1 loss and flows vs the CPU oracle, BEFORE any timing
     step_no = [0]
     # forward + loss + backward as hipGraph replays; with more than one rank the backward pass is cut into parts, and each
@@ -305,8 +317,10 @@ def main():
     eng.check_device_faults()       # raises if a stream-K fix-up wait timed out during the timed steps (a wrong tile)
     ms = dt / args.steps * 1e3
     pairs_per_s = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)      # the state the last timed step left, before anything below steps again
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         # the K-step figure above is a near-cold number (0.15 s of work); a training run sits at the clocks the chip
         # sustains: same step, >= sustain_seconds of it (step count from the all-reduced time: identical on every rank)
         n_sus = max(args.steps, int(args.sustain_seconds / (dt / args.steps)) + 1)
@@ -345,9 +359,10 @@ def main():
         out["parity"] = parity
     if world > 1 or force_dist:
         out["rccl_world_size"] = dist.get_world_size()      # the rank count the RCCL communicator reports
-        out["comm"] = measure_comm(runner, eng, step, barrier, args, world, ms, dev, dist)
+        if args.full:
+            out["comm"] = measure_comm(runner, eng, step, barrier, args, world, ms, dev, dist)
 
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         out["roofline"] = measure_roofline(eng, args)
         clk = (sustained or {}).get("clock")
         if clk and out["roofline"].get("frac") and clk["sclk_mhz_median"] > 0:
@@ -356,11 +371,11 @@ def main():
                 "nominal_mhz": 2400, "sampled_sclk_mhz": clk["sclk_mhz_median"], "sampled_power_w": clk["power_w_median"],
                 "frac_at_sampled_clock": round(out["roofline"]["frac"] * 2400.0 / clk["sclk_mhz_median"], 4),
                 "note": "frac x 2400 / sclk sampled beside the sustained pass (profiles/r06_clock_power_under_load.txt); `peak` and `frac` are the nominal ones"}
-    if rank == 0 and world == 1 and not args.no_alt and args.flownet == 'C' and eng.math == "bf16x3":
+    if args.full and rank == 0 and world == 1 and not args.no_alt and args.flownet == 'C' and eng.math == "bf16x3":
         out["value_fp32_mfma_only"] = measure_alt_fp32(args)      # same step with every conv kernel on the fp32 MFMA
-    if rank == 0 and world == 1 and not args.no_secondary and (args.flownet, args.dtype, H, W) == ('C', 'f32', 384, 512):
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and (args.flownet, args.dtype, H, W) == ('C', 'f32', 384, 512):
         out["secondary"] = measure_secondary(args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.flownet == 'C':
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.flownet == 'C':
         out["cpu_baseline"] = measure_cpu_baseline(H, W)
         if out["cpu_baseline"]["value"]:
             out["speedup_vs_cpu_baseline"] = round(pairs_per_s / out["cpu_baseline"]["value"], 1)
@@ -377,6 +392,45 @@ def main():
         pass
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+DUMP_PARAM_SAMPLE = 1 << 21     # positions of the parameter / gradient vectors written (8 MB each as float32)
+DUMP_FLOW_MAX = 1 << 19         # a flow level larger than this is written as a sample of this many positions
+DUMP_SEED = 20240101
+
+
+def _seeded_sample(t, n):
+    """t itself if it has at most n elements, else t flattened at the sorted positions of n draws from DUMP_SEED (the same
+    positions for every tensor of the same size)."""
+    import numpy as np
+    import torch
+    if t.numel() <= n:
+        return t
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), n))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(eng, out_dir):
+    """What the last timed step computed, as its caller receives it, into out_dir/<name>.npy (float32), so that two builds
+    run with the same arguments (same seeded weights and images) can be compared output for output:
+      loss                         the step's loss including the L2 term, [1]
+      flow<l>_fw, flow<l>_bw       the trained network's flow pyramid (NHWC), sampled beyond DUMP_FLOW_MAX elements
+      params_sample, grads_sample  the updated parameters and the step's data-loss gradients in the reference's variable
+                                   order (export_tf_params / export_tf_grads, concatenated), at DUMP_PARAM_SAMPLE seeded positions
+    About 17 MB at the benchmark's shape; at most 16 + 14 x 2 MB at any shape."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"loss": eng.loss_acc}
+    fw, bw = eng.flows()
+    for lvl, f, b in zip(eng.stages[-1].flow_levels, fw, bw):
+        arrays["flow%d_fw" % lvl] = _seeded_sample(f, DUMP_FLOW_MAX)
+        arrays["flow%d_bw" % lvl] = _seeded_sample(b, DUMP_FLOW_MAX)
+    for name, tensors in (("params_sample", eng.export_tf_params()), ("grads_sample", eng.export_tf_grads())):
+        arrays[name] = _seeded_sample(torch.cat([t.reshape(-1) for t in tensors.values()]), DUMP_PARAM_SAMPLE)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def measure_roofline(eng, args):
@@ -611,7 +665,7 @@ def measure_secondary(args):
     """BASELINE configs[3] and configs[4] in the driver's own line: each the same script in a sub-process (own roofline leg,
     no CPU baseline / fp32 re-measurement / sustained pass), reduced to the fields a reader needs."""
     import subprocess
-    base = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup),
+    base = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--full",
             "--no-cpu-baseline", "--no-alt", "--no-secondary", "--sustain-seconds", "0"]
     cfgs = [("FlowNetCSS 768x1024 B=2 (BASELINE configs[3]; last network trained, the two in front frozen; flow heads x 0.3: flows of tens of pixels, "
              "the regime pinned against the fp64 oracle at this batch)",

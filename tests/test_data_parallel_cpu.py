@@ -281,3 +281,16 @@ def test_bench_clock_sampler_parses_rocm_smi_json_and_degrades_to_none():
     s.SMI = "/nonexistent/rocm-smi"
     time.sleep(0.2)
     assert s.stop() is None
+
+
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """bench.py --dump-outputs: a tensor above the cap is written as a sample at positions fixed by the seed alone (two runs,
+    two builds: the same positions), within the cap; a small one whole."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    t = torch.arange(100000, dtype=torch.float32).reshape(10, 100, 100)
+    a, b = bench._seeded_sample(t, 1000), bench._seeded_sample(t.clone(), 1000)
+    assert torch.equal(a, b) and 900 < a.numel() <= 1000
+    assert torch.equal(a, a.sort().values) and a.unique().numel() == a.numel()
+    assert bench._seeded_sample(t, 100000) is t

@@ -161,7 +161,7 @@ def test_bench_launches_its_own_ranks(dev):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["UNFLOW_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-secondary",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-secondary",
                         "--no-cpu-baseline", "--no-alt", "--no-parity", "--no-roofline", "--sustain-seconds", "0"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -171,6 +171,31 @@ def test_bench_launches_its_own_ranks(dev):
     assert d["n_gpus"] == 2 and d["rccl_world_size"] == 2 and d["config"]["global_batch"] == 8
     assert d["comm"]["params_identical_across_ranks"] is True
     assert d["value"] > 0 and d["steps"] == 3
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(dev, tmp_path):
+    """A plain `bench.py --gpus 1` times exactly --steps steps and measures nothing else (the extras are --full's); with
+    --dump-outputs it writes what the last timed step computed as float32 .npy files, the loss equal to the line's final_loss."""
+    import json
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "image-pairs/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    for k in ("parity", "roofline", "secondary", "cpu_baseline", "value_fp32_mfma_only"):
+        assert k not in d, k
+    assert d["sustained"] is None
+    files = {p.name: np.load(p) for p in out.glob("*.npy")}
+    expect = {"loss", "params_sample", "grads_sample"} | {"flow%d_%s" % (l, s) for l in range(2, 7) for s in ("fw", "bw")}
+    assert set(n[:-4] for n in files) == expect
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["flow2_fw.npy"].shape == (4, 96, 128, 2)
+    assert round(float(files["loss.npy"][0]), 4) == d["config"]["final_loss"]
 
 
 def test_trainer_forwards_train_all_and_trains_the_first_network(dev):

@@ -6,7 +6,8 @@ tag=${1:-ser}
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out
-( cd /tmp && UNFLOW_WGRAD_GROUP=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 30 --warmup 6 --no-secondary --no-cpu-baseline --no-alt --no-parity --sustain-seconds 0 > $out/${tag}_serial_bench_under_rocprof.json 2> $out/${tag}_rocprof.err )
+root=$(pwd)
+( cd /tmp && UNFLOW_WGRAD_GROUP=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof -o b -- python $root/bench.py --steps 30 --warmup 6 --full --no-secondary --no-cpu-baseline --no-alt --no-parity --sustain-seconds 0 > $out/${tag}_serial_bench_under_rocprof.json 2> $out/${tag}_rocprof.err )
 find $out/${tag}_prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/${tag}_serial_kernel_stats.csv
 ( cd /tmp && UNFLOW_WGRAD_GROUP=0 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $out/${tag}_prof1 -o t -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-graph --no-secondary --no-cpu-baseline --no-alt --no-parity --no-roofline --sustain-seconds 0 > /dev/null 2>> $out/${tag}_rocprof.err )
 tr=$(find $out/${tag}_prof1 -name "*kernel_trace.csv" | head -1)
