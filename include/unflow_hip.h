@@ -521,6 +521,25 @@ int unflow_conv2d_transpose_bwd_filter_pl(const float* x, int ldx, const unflow_
 int unflow_resize_bilinear_tf1(const float* in, float* out, int B, int H, int W, int C, int out_h, int out_w,
                                float scale, unflow_stream_t stream);
 
+/* Supervised flow loss of one network (supervised.py:50-62), forward and backward in one launch (csrc/supervised.hip):
+ * loss_acc[0] += weight * sum(mask * ((flow_scale * up(flow) - flow_gt)^2 + 1e-6)^0.45) / (B*H*W*2), where up() is the TF1
+ * legacy bilinear resize of flow [B,h,w,2] to [H,W] with unflow_resize_bilinear_tf1's fp32 expression order (r = H/h = W/w
+ * in {1, 2, 4, 8}, else UNFLOW_ERR_SHAPE); flow_gt [B,H,W,2]; mask_gt [B,H,W,1] or NULL (= ones), broadcast over u and v.
+ * d_flow [B,h,w,2] (may be NULL: no gradient) receives d loss / d flow at the coarse resolution — written (accumulate = 0)
+ * or added (accumulate = 1), as a gather without float atomics (bit-reproducible). */
+int unflow_supervised_flow_loss(const float* flow, int h, int w, const float* flow_gt, const float* mask_gt, float flow_scale,
+                                float weight, float* loss_acc, float* d_flow, int accumulate, int B, int H, int W,
+                                unflow_stream_t stream);
+
+/* Stage input of a FlowNetS refinement network of the one-direction (supervised) engine: unflow_stack_input with
+ * first = first4[n], second = second4[n] ([N,H,W,4] each, e.g. the two halves of the network input), and its train_all
+ * gradient wrt prev_flow2 (ACCUMULATED with float atomics, like unflow_stack_input_bwd). */
+int unflow_stack_input_pair(const float* first4, const float* second4, const float* prev_flow2, float* out, int ld_out, int N,
+                            int H, int W, int h, int w, float flow_scale, unflow_stream_t stream);
+int unflow_stack_input_pair_bwd(const float* d_out, int ld_out, const float* first4, const float* second4,
+                                const float* prev_flow2, float* d_prev_flow2, int N, int H, int W, int h, int w,
+                                float flow_scale, unflow_stream_t stream);
+
 /* Fused L2-regularised TF-form Adam over a flat parameter vector (train.py:151-152; flownet.py:176):
  * g = grad*grad_scale + (i < n_regularized ? l2_scale * p : 0);
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr_t * m / (sqrt(v) + eps). */

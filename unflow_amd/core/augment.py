@@ -137,3 +137,10 @@ def draw_training_augmentation(num_batch, generator=None):
                                 brightness_stddev=0.02, min_colour=0.9, max_colour=1.1, min_gamma=0.7,
                                 max_gamma=1.5, generator=generator))
     return aug
+
+
+def draw_supervised_augmentation(num_batch, generator=None):
+    """The draws of the supervised step (supervised.py:21-25): photometric only, the same ranges as the photometric part of
+    draw_training_augmentation; one draw per image pair, applied to both frames."""
+    return draw_photometric(num_batch, noise_stddev=0.04, min_contrast=-0.3, max_contrast=0.3, brightness_stddev=0.02,
+                            min_colour=0.9, max_colour=1.1, min_gamma=0.7, max_gamma=1.5, generator=generator)

@@ -135,11 +135,18 @@ class ActView(dict):
 
 
 class _Op:
-    """One forward launch of a stage: a layer (src slice -> dst slice) or the correlation."""
-    __slots__ = ('kind', 'l', 'src', 'dst')
+    """One forward launch of a stage: a layer (src slice -> dst slice) or the correlation; n: the samples (rows) it runs on."""
+    __slots__ = ('kind', 'l', 'src', 'dst', 'n')
 
     def __init__(self, kind, l, src, dst):
-        self.kind, self.l, self.src, self.dst = kind, l, src, dst
+        self.kind, self.l, self.src, self.dst, self.n = kind, l, src, dst, 0
+
+
+def _rows(t, n):
+    """The first n samples of a PT (fp32 tensor and planes), or t itself when it has n."""
+    if t.t.shape[0] == n:
+        return t
+    return L.PT(t.t[:n], None if t.pl is None else t.pl[:, :n], t.scale)
 
 
 class _Stage:
@@ -255,6 +262,18 @@ class _Stage:
             layer(fr, 'flow1_up0', 'deconv', 4, seg('flow1', 'flow'), seg('cat0', 'up'), 2, 2, False)
             layer(fr, 'flow0', 'conv', 3, whole('cat0'), seg('flow0', 'flow'), 2, 1, False)
         self.by_name = {l.name.split('/')[-1]: l for l in self.layers}
+        # samples (rows) of every buffer and op.  Bidirectional engine: all N = 2B.  One-direction (supervised) engine: the
+        # FlowNetC feature tower (conv1 .. conv3, the conv2 segment of cat2) runs on both frames, 2B rows; everything from
+        # conv_redir and the correlation on, and every buffer of a FlowNetS, has B rows
+        enc = ('c1', 'cat2', 'c3') if self.is_c else ()
+        one_dir = getattr(eng, 'supervised', False)
+        # (a stage built for its layer table alone, without an engine's shape, counts rows in units of B)
+        nB, nN = (eng.B, eng.N) if hasattr(eng, 'N') else (1, 2)
+        self.rows = {name: (nN if (not one_dir or name in enc) else nB) for name in B}
+        self.rows['x0'] = nN
+        for op in self.ops:
+            # (the correlation reads and, backward, writes all rows of c3: both frames' features)
+            op.n = self.rows['c3'] if op.kind == 'corr' else min(self.rows[op.src[0]], self.rows[op.dst[0]])
         self._plan_backward()
 
     # -------------------------------------------------------------- backward plan
@@ -274,22 +293,41 @@ class _Stage:
             if op.src[0] != 'x0':
                 order.setdefault(op.src[0], []).append((i, op))
         self.bwd = []
+        # Row ranges (one-direction engine only; with N rows everywhere neither dict gets an entry): a consumer whose rows
+        # reach past those of every earlier writer is the first writer of the rows beyond (d cat2[B:2B): conv3 alone) — they
+        # are zeroed in front of its accumulating call; an activation whose last consumer for some rows is the correlation
+        # (d c3[B:2B): its grad1 alone) gets the leaky-ReLU derivative of those rows by a stand-alone launch after it.
+        self.bwd_zero_rows, self.bwd_post_act = {}, {}
         for i, op in enumerate(rev):
             sb, slo, shi = op.src
             act_lo = act_hi = 0
             first = False
             if sb != 'x0':
                 cons = order[sb]
-                first = cons[0][0] == i
+                prior = max((o.n for j, o in cons if j < i), default=0)
+                first = prior == 0
                 if first:
                     assert slo == 0 and shi == self.bufs[sb][2], "first data gradient into %s must cover it" % sb
+                elif prior < op.n:
+                    self.bwd_zero_rows[i] = (prior, op.n)
                 rng = []
                 for (pb, plo, phi), pl in producers.items():
                     if pb != sb or not pl.act or plo < slo or phi > shi:
                         continue
-                    last = max(j for j, o in cons if o.src[1] <= plo and o.src[2] >= phi)
-                    if last == i:
-                        rng.append((plo - slo, phi - slo))
+                    cov = [(j, o) for j, o in cons if o.src[1] <= plo and o.src[2] >= phi]
+                    mine, r0 = [], 0
+                    for r1 in sorted(set(o.n for _, o in cov)):        # row bands [r0, r1): their last consumer
+                        last = max(j for j, o in cov if o.n >= r1)
+                        if last == i:
+                            mine.append((r0, r1))
+                        r0 = r1
+                    if not mine:
+                        continue
+                    if op.kind == 'corr':
+                        self.bwd_post_act.setdefault(i, []).extend((a, b, plo - slo, phi - slo) for a, b in mine)
+                        continue
+                    assert mine[0][0] == 0 and mine[-1][1] == op.n, "a data gradient must finish all of its rows"
+                    rng.append((plo - slo, phi - slo))
                 if rng:
                     rng.sort()
                     for (a0, a1), (b0, b1) in zip(rng, rng[1:]):
@@ -320,12 +358,12 @@ class _Stage:
     # -------------------------------------------------------------- buffers
     def alloc(self):
         e = self.eng
-        N, H, W, dev = e.N, e.H, e.W, e.dev
+        H, W, dev = e.H, e.W, e.dev
         npl = e.n_planes
         self.A, self.Gd = {}, {}
         for name, (div, lay, width) in self.bufs.items():
             is_flow = name.startswith('flow')
-            self.A[name] = L.PT.alloc((N, H // div, W // div, width), dev, 0 if is_flow else npl)
+            self.A[name] = L.PT.alloc((self.rows[name], H // div, W // div, width), dev, 0 if is_flow else npl)
         # d loss / d stage input -> the previous network (train_all only; otherwise behind stop_gradient, flownet.py:51-54)
         self.need_in_grad = (not self.is_c) and self.index > 0 and e.train_all
         if self.need_in_grad and self.full_res:
@@ -335,7 +373,8 @@ class _Stage:
                 if name == 'x0s' and not self.need_in_grad:
                     continue
                 is_flow = name.startswith('flow')
-                self.Gd[name] = L.PT.alloc((N, H // div, W // div, width), dev, 0 if is_flow else npl, scale=e.grad_plane_scale)
+                self.Gd[name] = L.PT.alloc((self.rows[name], H // div, W // div, width), dev, 0 if is_flow else npl,
+                                           scale=e.grad_plane_scale)
         # single-producer conv outputs that only convolutions consume (no flow head, no concat, no correlation fallback): they
         # live as operand planes alone — no fp32 write in the forward pass, and the data gradient that needs the sign of
         # the activation (leaky-ReLU derivative) takes it from the leading plane
@@ -363,9 +402,13 @@ class _Stage:
         if not self.is_c:
             x0s = self.act['x0s']
             pf = prev_flow2
-            check(_lib.lib().unflow_stack_input(ptr(e.x0), ptr(pf), ptr(x0s), x0s.stride(2), B, N, e.H, e.W,
-                                                0 if pf is None else pf.shape[1], 0 if pf is None else pf.shape[2],
-                                                cf(4 * FLOW_SCALE), e.stream()), "stack_input")
+            ph, pw = (0, 0) if pf is None else (pf.shape[1], pf.shape[2])
+            if e.supervised:      # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B)
+                check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[:B]), ptr(e.x0[B:]), ptr(pf), ptr(x0s), x0s.stride(2), B,
+                                                         e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
+            else:
+                check(_lib.lib().unflow_stack_input(ptr(e.x0), ptr(pf), ptr(x0s), x0s.stride(2), B, N, e.H, e.W, ph, pw,
+                                                    cf(4 * FLOW_SCALE), e.stream()), "stack_input")
             inp = self.A[self.bin]
             if inp.pl is not None:
                 w_in = pad4(self.in_ch)
@@ -375,15 +418,22 @@ class _Stage:
                 c3, out = self.pt(op.src), self.pt(op.dst)
                 C = op.src[2] - op.src[1]
                 h8, w8 = e.H // 8, e.W // 8
-                c3pl = _lib.planes_of(self._corr_planes(c3, refresh=True))   # bf16 x 3 planes: the matrix-core path
-                check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t), ptr(c3.t), c3.t.stride(2), c3pl, c3pl, B,
-                                                                ptr(out.t), out.t.stride(2), N, C, h8, w8, 1, 20, 20, 1, 2,
-                                                                e.stream()), "correlation")
+                pl = self._corr_planes(c3, refresh=True)                      # bf16 x 3 planes: the matrix-core path
+                if e.supervised:      # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
+                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, B:]))
+                    check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[:B]), ptr(c3.t[B:]), c3.t.stride(2), p0, p1, 0,
+                                                                    ptr(out.t), out.t.stride(2), B, C, h8, w8, 1, 20, 20, 1, 2,
+                                                                    e.stream()), "correlation")
+                else:
+                    c3pl = _lib.planes_of(pl)
+                    check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t), ptr(c3.t), c3.t.stride(2), c3pl, c3pl, B,
+                                                                    ptr(out.t), out.t.stride(2), N, C, h8, w8, 1, 20, 20, 1, 2,
+                                                                    e.stream()), "correlation")
                 if out.pl is not None:       # operand planes of the cost volume for conv3_1 (pad channels zeroed)
                     L.planes_from_f32(out.t, out.pl)
                 continue
             l = op.l
-            x, y = self.pt(op.src), self.pt(op.dst)
+            x, y = _rows(self.pt(op.src), op.n), _rows(self.pt(op.dst), op.n)
             if l.cout_p != l.cout:
                 y = L.PT(y.t.as_strided(y.t.shape[:3] + (l.cout_p,), y.t.stride(), y.t.storage_offset()),
                          None if y.pl is None else y.pl)
@@ -409,6 +459,18 @@ class _Stage:
         if refresh:
             L.planes_from_f32(c3.t, self._c3_b3)
         return self._c3_b3
+
+    def _leaky_bwd_rows(self, g, a, r0, r1, clo, chi):
+        """conv3's leaky-ReLU derivative on d c3 rows [r0, r1) (channels [clo, chi) of the slices g / a) and the operand
+        planes of those rows: in the one-direction engine only the correlation's grad1 reaches them (conv_redir runs on the
+        first B rows and applies the derivative there in its epilogue)."""
+        gt, at = g.t[r0:r1, ..., clo:chi], a.t[r0:r1, ..., clo:chi]
+        L.leaky_bwd_inplace(gt, at)
+        if g.pl is not None:
+            pl = g.pl[:, r0:r1, ..., clo:min(g.pl.shape[-1], clo + round8(chi - clo))]
+            check(_lib.lib().unflow_planes_from_f32(ptr(gt), gt.stride(2), cl(gt.shape[0] * gt.shape[1] * gt.shape[2]),
+                                                    chi - clo, min(round8(chi - clo), pl.shape[-1]), _lib.planes_of(pl, g.scale),
+                                                    self.eng.stream()), "planes_from_f32")
 
     def backward(self, part=None, before_join=None):
         """part None: everything; k: the k-th slice of the backward list (default cuts: 0 = decoder + conv6_1..conv4 — 94 %
@@ -451,20 +513,30 @@ class _Stage:
         flow_jobs = []
         n_flow = sum(1 for op, _, _, _ in self.bwd[lo:hi] if op.kind == 'layer' and op.l.cout <= 2) if e.batch_flow_wgrad else 0
 
-        for op, first, act_lo, act_hi in self.bwd[lo:hi]:
+        for k, (op, first, act_lo, act_hi) in enumerate(self.bwd[lo:hi], lo):
             if op.kind == 'corr':
                 c3, g3, gout = self.pt(op.src), self.pt(op.src, True), self.pt(op.dst, True)
                 C = op.src[2] - op.src[1]
                 h8, w8 = e.H // 8, e.W // 8
                 assert first
-                c3pl = _lib.planes_of(self._corr_planes(c3))                 # bf16 x 3 planes: feature operand by LDS-DMA
-                check(_lib.lib().unflow_correlation_nhwc_bwd_pl(ptr(gout.t), gout.t.stride(2), ptr(c3.t), ptr(c3.t),
-                                                                c3.t.stride(2), c3pl, c3pl, B, ptr(g3.t), ptr(None),
-                                                                g3.t.stride(2), 1, N, C, h8, w8, 1, 20, 20, 1, 2, e.stream()),
-                      "correlation_grad")
+                pl = self._corr_planes(c3)                                    # bf16 x 3 planes: feature operand by LDS-DMA
+                if e.supervised:      # separate gradients: grad0 -> d c3[0, B), grad1 -> d c3[B, 2B)
+                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, B:]))
+                    check(_lib.lib().unflow_correlation_nhwc_bwd_pl(ptr(gout.t), gout.t.stride(2), ptr(c3.t[:B]), ptr(c3.t[B:]),
+                                                                    c3.t.stride(2), p0, p1, 0, ptr(g3.t[:B]), ptr(g3.t[B:]),
+                                                                    g3.t.stride(2), 0, B, C, h8, w8, 1, 20, 20, 1, 2, e.stream()),
+                          "correlation_grad")
+                else:
+                    c3pl = _lib.planes_of(pl)
+                    check(_lib.lib().unflow_correlation_nhwc_bwd_pl(ptr(gout.t), gout.t.stride(2), ptr(c3.t), ptr(c3.t),
+                                                                    c3.t.stride(2), c3pl, c3pl, B, ptr(g3.t), ptr(None),
+                                                                    g3.t.stride(2), 1, N, C, h8, w8, 1, 20, 20, 1, 2, e.stream()),
+                          "correlation_grad")
+                for r0, r1, clo, chi in self.bwd_post_act.get(k, ()):
+                    self._leaky_bwd_rows(g3, c3, r0, r1, clo, chi)
                 continue
             l = op.l
-            x, dz = self.pt(op.src), self.pt(op.dst, True)
+            x, dz = _rows(self.pt(op.src), op.n), _rows(self.pt(op.dst, True), op.n)
             if l.cout_p != l.cout:
                 dz = L.PT(dz.t.as_strided(dz.t.shape[:3] + (l.cout_p,), dz.t.stride(), dz.t.storage_offset()), dz.pl, dz.scale)
             if e._bias_plan is None:
@@ -487,10 +559,14 @@ class _Stage:
                                       and op.l.name.endswith('conv1'))
             if sb not in self.Gd or (is_input and not self.need_in_grad):
                 continue                              # inputs are data (or behind stop_gradient, flownet.py:51-54)
-            dx = self.pt(op.src, True)
+            dx = _rows(self.pt(op.src, True), op.n)
             # the loss wrote d flowN first (flow buffers): everything after it accumulates
             accumulate = (not first) or sb.startswith('flow')
-            act_src = self.pt(op.src) if act_hi > act_lo else None
+            if k in self.bwd_zero_rows:           # rows no earlier consumer wrote: this call is their first writer
+                r0, r1 = self.bwd_zero_rows[k]
+                gz = self.Gd[sb].t[r0:r1]
+                check(_lib.lib().unflow_zero(ptr(gz), _lib.csz(gz.numel() * 4), e.stream()), "zero")
+            act_src = _rows(self.pt(op.src), op.n) if act_hi > act_lo else None
             apl = sb in self.planes_only
             if l.kind == 'conv':
                 L.conv_bwd_data(dz, l.w, l.wpl_d, dx, l.stride, accumulate, act_src, act_lo, act_hi, act_planes=apl)
@@ -512,12 +588,18 @@ class FlowNetEngine:
     reference, whose regulariser and optimizer span all variables — still receive the L2 gradient in the Adam update.
     With train_all the gradient also flows back through every inter-stage input (upsampled flow, warp, |warp - first|)
     into the earlier networks.  params['full_res'] adds the full-resolution decoder levels to the LAST network
-    (flownet.py:21,133-153; a FlowNetS) and the loss pyramid then has 7 levels (unsupervised.py:89-96)."""
+    (flownet.py:21,133-153; a FlowNetS) and the loss pyramid then has 7 levels (unsupervised.py:89-96).
 
-    def __init__(self, batch, height, width, params=None, device=None, seed=0, layout_only=False):
+    supervised=True: the one-direction engine of the supervised fine-tuning step (supervised.py:12-65).  The network input
+    is still [im1; im2] (2B rows): FlowNetC's feature tower runs on both frames, everything from the correlation on — and
+    every FlowNetS — on the B forward pairs only; the loss is the masked Charbonnier of the final flow against set_input's
+    target (unflow_supervised_flow_loss per counted network)."""
+
+    def __init__(self, batch, height, width, params=None, device=None, seed=0, layout_only=False, supervised=False):
         """layout_only: build the layer table and the flat parameter / gradient buffers (on `device`, which may then be the
         CPU) but no activations — for tools and the data-parallel tests that only need the flat layout and its buckets."""
         assert height % 64 == 0 and width % 64 == 0, "FlowNet needs H, W divisible by 64"
+        self.supervised = bool(supervised)
         self.params = dict(DEFAULT_PARAMS) if params is None else dict(params)
         if self.params.get('mask_occlusion', '') not in ('', 'fb', 'disocc'):   # unsupervised.py:125-126
             raise ValueError("mask_occlusion must be one of 'fb', 'disocc', ''")
@@ -526,6 +608,9 @@ class FlowNetEngine:
             raise ValueError("flownet spec: 'C'/'c' or 'S'/'s' first, then 'S'/'s' refinement nets (flownet.py:20-28)")
         self.train_all = bool(self.params.get('train_all')) and len(spec) > 1     # train.py:29-37, flownet.py:51-54
         self.full_res = bool(self.params.get('full_res'))
+        if self.supervised and self.full_res and self.train_all:
+            raise ValueError("supervised full_res with train_all: the reference subtracts the earlier networks' quarter-size "
+                             "flow2 * 20 from the full-size ground truth (supervised.py:50-60), a shape error")
         self.spec = spec
         self.B, self.H, self.W = batch, height, width
         self.N = 2 * batch
@@ -765,6 +850,15 @@ class FlowNetEngine:
         self.act.update(last.act)
         self.act.update(x0=self.x0, im01=self.im01)
         self.grad = last.grad
+        if self.supervised:
+            # engine-owned targets (fixed addresses for the captured graphs; set_input copies into them); no loss pyramid
+            self.flow_gt, self.mask_gt = z(self.B, H, W, 2), z(self.B, H, W, 1)
+            self.lv = []
+            self.loss_acc = z(1)
+            self.final_flow = z(self.B, H, W, 2)
+            self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
+            self.epe_out = z(2)
+            return
         # loss-side pyramid: one level per flow output of the last network (unsupervised.py:85-104)
         self.layer_weights = LAYER_WEIGHTS_FULL_RES if self.full_res else LAYER_WEIGHTS
         self.patch_distances = LAYER_PATCH_DISTANCES_FULL_RES if self.full_res else LAYER_PATCH_DISTANCES
@@ -788,6 +882,8 @@ class FlowNetEngine:
         of the engine (so a captured hipGraph never holds a stale mask pointer): without augmentation it holds B copies of
         the static mask, with augmentation the per-sample warped masks."""
         from .. import ops
+        if self.supervised:
+            return                # no border mask in the supervised loss (supervised.py:12-65)
         H, W, B = self.H, self.W, self.B
         sz = int(math.ceil(min(H, W) * 0.1))
         m = torch.zeros(1, H, W, 1, device=self.dev)
@@ -806,14 +902,20 @@ class FlowNetEngine:
         return [1 if (i == 0 and self.full_res) else (4 if i == 0 else 2) for i in range(len(self.lv))]
 
     # ------------------------------------------------------------------ forward
-    def set_input(self, im1, im2, augment=None):
+    def set_input(self, im1, im2, augment=None, target=None):
         """im1, im2: [B,H,W,3] float32 in [0,255] (what the reference's input queue delivers).
         augment: None (augment=False) or the draws of core.augment.draw_training_augmentation — then the step sees
         what unsupervised.py:37-68 builds: geometrically augmented images for the losses, photometrically augmented
-        mean-free ones for the network, and a per-sample border mask (product of the two warped masks)."""
+        mean-free ones for the network, and a per-sample border mask (product of the two warped masks).
+        Supervised engine: target = (flow_gt [B,H,W,2], mask_gt [B,H,W,1] or None = ones) is copied into the engine's own
+        buffers; augment is None or photometric draws only (core.augment.draw_supervised_augmentation, supervised.py:21-25)."""
         B, N, H, W = self.B, self.N, self.H, self.W
         lib = _lib.lib()
         st = self.stream()
+        if self.supervised:
+            return self._set_input_supervised(im1, im2, augment, target)
+        if target is not None:
+            raise ValueError("set_input: a target is for the supervised engine (FlowNetEngine(..., supervised=True))")
         # the kernels below take raw device pointers: bring whatever the input pipeline delivers (numpy batches of
         # core/input.py, host tensors, strided views) to contiguous fp32 on this engine's device — a no-op for a conforming tensor
         im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
@@ -858,6 +960,42 @@ class FlowNetEngine:
         A.photometric(self.im01, augment, out=self.x0, mean=CHANNEL_MEAN)  # im*_photo - channel_mean (:53-57,67-68)
         self._input_planes()
 
+    def _set_input_supervised(self, im1, im2, augment, target):
+        B, H, W = self.B, self.H, self.W
+        lib = _lib.lib()
+        st = self.stream()
+        im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
+        im2 = torch.as_tensor(im2).to(device=self.dev, dtype=torch.float32).contiguous()
+        if tuple(im1.shape) != (B, H, W, 3) or tuple(im2.shape) != (B, H, W, 3):
+            raise ValueError("set_input: expected two [%d,%d,%d,3] batches, got %s and %s"
+                             % (B, H, W, tuple(im1.shape), tuple(im2.shape)))
+        if target is None:
+            raise ValueError("set_input: the supervised engine needs target=(flow_gt, mask_gt)")
+        flow_gt, mask_gt = target
+        flow_gt = torch.as_tensor(flow_gt).to(device=self.dev, dtype=torch.float32).contiguous()
+        if tuple(flow_gt.shape) != (B, H, W, 2):
+            raise ValueError("set_input: flow_gt must be [%d,%d,%d,2], got %s" % (B, H, W, tuple(flow_gt.shape)))
+        check(lib.unflow_copy(ptr(self.flow_gt), ptr(flow_gt), _lib.csz(flow_gt.numel() * 4), st), "copy")
+        if mask_gt is None:
+            self.mask_gt.fill_(1.0)
+        else:
+            mask_gt = torch.as_tensor(mask_gt).to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(mask_gt.shape) != (B, H, W, 1):
+                raise ValueError("set_input: mask_gt must be [%d,%d,%d,1], got %s" % (B, H, W, tuple(mask_gt.shape)))
+            check(lib.unflow_copy(ptr(self.mask_gt), ptr(mask_gt), _lib.csz(mask_gt.numel() * 4), st), "copy")
+        if augment is None:
+            pl = self.X0.pl if (self.X0.pl is not None and self.stages[0].is_c) else None
+            check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(self.im01),
+                                                self.mean_host, _lib.planes_of(pl), st), "prepare_image_pair")
+            return
+        # random_photometric of both frames with the SAME per-pair draws (sample n of the 2B rows uses draw n % B), then
+        # the mean subtraction (supervised.py:21-35)
+        from . import augment as A
+        check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(self.im01), self.mean_host,
+                                            None, st), "prepare_image_pair")
+        A.photometric(self.im01, augment, out=self.x0, mean=CHANNEL_MEAN)
+        self._input_planes()
+
     def _input_planes(self):
         """Operand planes of the network input for conv1 of a FlowNetC (FlowNetS stages build theirs after stack_input)."""
         if self.X0.pl is not None and self.stages[0].is_c:
@@ -877,6 +1015,8 @@ class FlowNetEngine:
         """compute_losses + the pyramid assembly (losses.py:16-87, unsupervised.py:85-150) over the directed batch;
         with_grad also leaves d(loss)/d(flowN) in self.grad['flowN'].  Terms enter iff their `<name>_weight` is set
         (unsupervised.py:136-141), exactly the pruning TF does."""
+        if self.supervised:
+            return self._forward_loss_supervised(with_grad)
         lib = _lib.lib()
         st = self.stream()
         N, B = self.N, self.B
@@ -994,6 +1134,30 @@ class FlowNetEngine:
             check(lib.unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(self.loss_acc), st), "l2_loss")
         return self.loss_acc
 
+    def _forward_loss_supervised(self, with_grad=True):
+        """supervised.py:46-62: the last network's final flow (every network's with train_all, weight 1 / 2^i counted from
+        the last) against the target, charbonnier_loss(final - flow_gt, mask_gt), one fused launch per counted network; it
+        writes d loss / d flow2 (flow0 with full_res) of that network, the other flow levels get zero gradient."""
+        lib = _lib.lib()
+        st = self.stream()
+        check(lib.unflow_zero(ptr(self.loss_acc), _lib.csz(4), st), "zero")
+        counted = self.stages if self.train_all else self.stages[-1:]
+        for i, stg in enumerate(reversed(counted)):
+            lvl = 0 if stg.full_res else 2
+            f = stg.act['flow%d' % lvl]
+            gf = stg.grad['flow%d' % lvl] if with_grad else None
+            check(lib.unflow_supervised_flow_loss(ptr(f), f.shape[1], f.shape[2], ptr(self.flow_gt), ptr(self.mask_gt),
+                                                  cf(FLOW_SCALE * 4), cf(1.0 / 2 ** i), ptr(self.loss_acc), ptr(gf), 0,
+                                                  self.B, self.H, self.W, st), "supervised_flow_loss")
+            if with_grad:
+                for other in stg.flow_levels:
+                    if other != lvl:
+                        g = stg.grad['flow%d' % other]
+                        check(lib.unflow_zero(ptr(g), _lib.csz(g.numel() * 4), st), "zero")
+        if not self.defer_l2:
+            check(lib.unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(self.loss_acc), st), "l2_loss")
+        return self.loss_acc
+
     def _pyramid_levels(self, levels, wt):
         """ctypes array of unflow_pyr_level for unflow_loss_pyramid_default (rebuilt when the mask pointers change)."""
         Level = _lib.PyrLevel
@@ -1048,7 +1212,16 @@ class FlowNetEngine:
 
     def _stack_backward(self, st, prev):
         """d loss / d (flow2 of the previous network) through the stage input of `st` (train_all).  The previous
-        network's coarser flows do not reach the loss directly (only flows[-1] enters it, unsupervised.py:82-83)."""
+        network's coarser flows do not reach the loss directly (only flows[-1] enters it, unsupervised.py:82-83).
+        Supervised engine: d flow2 of the previous network already holds its own loss term (the loss launch wrote it, and
+        zeroed the other levels); the stage-input gradient is added to it."""
+        if self.supervised:
+            B = self.B
+            g2, pf, dx = prev.grad['flow2'], prev.act['flow2'], st.grad['x0s']
+            check(_lib.lib().unflow_stack_input_pair_bwd(ptr(dx), dx.stride(2), ptr(self.x0[:B]), ptr(self.x0[B:]), ptr(pf),
+                                                         ptr(g2), B, self.H, self.W, pf.shape[1], pf.shape[2],
+                                                         cf(4 * FLOW_SCALE), self.stream()), "stack_input_pair_bwd")
+            return
         for lvl in prev.flow_levels:
             gz = prev.grad['flow%d' % lvl]
             check(_lib.lib().unflow_zero(ptr(gz), _lib.csz(gz.numel() * 4), self.stream()), "zero")
@@ -1254,20 +1427,20 @@ class FlowNetEngine:
         return 0
 
     # ------------------------------------------------------------------ composite
-    def fwd_bwd(self, im1=None, im2=None):
+    def fwd_bwd(self, im1=None, im2=None, target=None):
         if im1 is not None:
-            self.set_input(im1, im2)
+            self.set_input(im1, im2, target=target)
         self.forward_net()
         loss = self.forward_loss(with_grad=True)
         self.backward_net()
         return loss
 
-    def train_step(self, im1, im2, lr):
+    def train_step(self, im1, im2, lr, target=None):
         """One optimisation step; returns the loss tensor [1] (complete once the Adam kernel has run: the 0.0004*sum(w^2)/2
         term is accumulated by the pass Adam makes over the parameters, not by a separate reduction)."""
         prev, self.defer_l2 = self.defer_l2, True
         try:
-            loss = self.fwd_bwd(im1, im2)
+            loss = self.fwd_bwd(im1, im2, target)
             self.adam_step(lr)
         finally:
             self.defer_l2 = prev
@@ -1275,22 +1448,28 @@ class FlowNetEngine:
 
     def final_flows(self):
         """final_flow_fw / _bw: resize_bilinear(flow2, im_shape) * 5 * 4 (unsupervised.py:103-104), or flow0 * 20 with
-        full_res (unsupervised.py:95-97)."""
+        full_res (unsupervised.py:95-97).  Supervised engine: (final_flow_fw, None)."""
         if self.full_res:
             f0 = self.act['flow0']
             check(_lib.lib().unflow_scale(ptr(f0), cf(FLOW_SCALE * 4), ptr(self.final_flow), cl(f0.numel()), self.stream()), "scale")
+            if self.supervised:
+                return self.final_flow, None
             return self.final_flow[:self.B], self.final_flow[self.B:]
         f2 = self.act['flow2']
         N, h, w, _ = f2.shape
         check(_lib.lib().unflow_resize_bilinear_tf1(ptr(f2), ptr(self.final_flow), N, h, w, 2, self.H, self.W,
                                                     cf(FLOW_SCALE * 4), self.stream()), "resize_bilinear")
+        if self.supervised:
+            return self.final_flow, None
         return self.final_flow[:self.B], self.final_flow[self.B:]
 
     def flows(self):
         """(flows_fw, flows_bw): lists [flow2..flow6] ([flow0, flow1, flow2..] with full_res), NHWC, like
-        flownet(..., backward_flow=True)[-1]."""
+        flownet(..., backward_flow=True)[-1].  Supervised engine: (flows_fw, None)."""
         B = self.B
         lv = self.stages[-1].flow_levels
+        if self.supervised:
+            return [self.act['flow%d' % l] for l in lv], None
         fw = [self.act['flow%d' % l][:B] for l in lv]
         bw = [self.act['flow%d' % l][B:] for l in lv]
         return fw, bw

@@ -109,15 +109,15 @@ class StepRunner:
             graphs.append(g)
         self.graphs = graphs
 
-    def step(self, im1, im2, lr, augment=None):
+    def step(self, im1, im2, lr, augment=None, target=None):
         """One optimisation step on the minibatch (im1, im2) [B,H,W,3] in [0,255]; returns the loss tensor [1] (complete
-        when the stream has drained)."""
+        when the stream has drained).  target: (flow_gt, mask_gt) of a supervised engine."""
         e = self.eng
         if not self._captured:
-            e.set_input(im1, im2, augment=augment)
+            e.set_input(im1, im2, augment=augment, target=target)
             self.capture()
             self._captured = True
-        e.set_input(im1, im2, augment=augment)
+        e.set_input(im1, im2, augment=augment, target=target)
         if e.planes_external and e._wplanes_version != e.P._version:
             e.refresh_weight_planes(force=True)          # the parameters were written behind the runner's back (a restore)
         lr_t = e.adam_begin(lr)
@@ -162,16 +162,23 @@ class Trainer:
     manual_decay_*, flownet, train_all, full_res, loss weights, mask modes ...).  With torch.distributed initialised,
     every rank trains on its own shard of the minibatch and the gradients are averaged with a bucketed RCCL all-reduce
     (average_gradients semantics).  The training step augments like the reference's (unsupervised_loss(augment=True),
-    train.py:160,170); `augment=False` switches that off."""
+    train.py:160,170); `augment=False` switches that off.
+
+    supervised=True: the supervised fine-tuning trainer (run.py:175-190, Trainer(supervised=True)): the one-direction engine,
+    train_batch_fn yields (im1, im2, flow_gt, mask_gt) batches (kitti.input.KITTIInput.input_train_gt) and the step augments
+    photometrically only (supervised.py:21-25).  eval keeps the bidirectional engine of the unsupervised loss, as the
+    reference does (train.py:277)."""
 
     ENGINE_KEYS = ('flownet', 'train_all', 'full_res', 'pyramid_loss', 'border_mask', 'mask_occlusion')
 
-    def __init__(self, batch_size, height, width, params, device=None, seed=0, augment=True, use_graph=True):
+    def __init__(self, batch_size, height, width, params, device=None, seed=0, augment=True, use_graph=True, supervised=False):
         self.params = dict(params)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
+        self.supervised = bool(supervised)
         eng_params = {k: v for k, v in params.items() if k.endswith('_weight') or k in self.ENGINE_KEYS}
-        self.engine = FlowNetEngine(batch_size, height, width, params=eng_params or None, device=device, seed=seed)
+        self.engine = FlowNetEngine(batch_size, height, width, params=eng_params or None, device=device, seed=seed,
+                                    supervised=self.supervised)
         self.runner = StepRunner(self.engine, self.world, use_graph=use_graph)
         self.augment = augment
         self.generator = torch.Generator().manual_seed(1000003 * (seed + 1) + self.rank)   # per-rank augmentation draws
@@ -313,7 +320,8 @@ class Trainer:
         """Trainer.run (train.py:116-145): train (at most) from min_iter + 1 to max_iter in chunks of params['save_interval']
         steps, a checkpoint after every chunk.  A checkpoint found in ckpt_dir must carry a global_step within [min_iter, max_iter];
         training then continues from global_step + 1.  train_batch_fn(iter_offset) returns an iterator of (im1, im2) batches
-        already shifted by iter_offset steps (the reference builds its input queue with shift = batch_size * iter_offset);
+        already shifted by iter_offset steps (the reference builds its input queue with shift = batch_size * iter_offset) — of
+        (im1, im2, flow_gt, mask_gt) batches for a supervised trainer;
         eval_fn(i), if given, runs after each chunk (self.eval(1) of the reference).  Returns the list of (iteration, loss) at the
         display interval."""
         save_interval = self.params['save_interval']
@@ -351,8 +359,13 @@ class Trainer:
         log = []
         for local_i, i in enumerate(range(start_iter, max_iter + 1)):
             self.iteration = local_i + iter_offset
-            im1, im2 = next(batches)
-            loss = self.train_step(im1, im2)
+            batch = next(batches)
+            if getattr(self, 'supervised', False):
+                im1, im2, flow_gt, mask_gt = batch
+                loss = self.train_step(im1, im2, target=(flow_gt, mask_gt))
+            else:
+                im1, im2 = batch
+                loss = self.train_step(im1, im2)
             if i == 1 or i % display == 0:
                 loss = float(loss)
                 self._check_faults()                    # the host has just synchronised on the loss: read the fault counters
@@ -369,14 +382,16 @@ class Trainer:
             self.runner.reducer.quiesce()
         self.engine.check_device_faults(world_sync=self.world > 1)
 
-    def train_step(self, im1, im2, augment=None):
+    def train_step(self, im1, im2, augment=None, target=None):
         """sess.run([train_op, loss_]) (train.py:247-251): returns the loss tensor (device, no sync).  `augment`: None = the
-        trainer's setting (random draws per step), False = off, or a dict of draws to replay."""
+        trainer's setting (random draws per step), False = off, or a dict of draws to replay.  target: (flow_gt, mask_gt)
+        of a supervised trainer."""
         lr = learning_rate_at(self.params, self.iteration)
         aug = self.augment if augment is None else augment
         if aug is True:
-            from .augment import draw_training_augmentation
-            aug = draw_training_augmentation(self.engine.B, self.generator)
-        loss = self.runner.step(im1, im2, lr, augment=aug or None)
+            from .augment import draw_training_augmentation, draw_supervised_augmentation
+            draw = draw_supervised_augmentation if getattr(self, 'supervised', False) else draw_training_augmentation
+            aug = draw(self.engine.B, self.generator)
+        loss = self.runner.step(im1, im2, lr, augment=aug or None, target=target)
         self.iteration += 1
         return loss

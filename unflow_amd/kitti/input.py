@@ -1,12 +1,13 @@
-"""Mirror of src/e2eflow/kitti/input.py for the evaluation inputs of Trainer.eval (train.py:265-385): image pairs of a
-KITTI `training` directory with their occluded / non-occluded ground-truth flow maps, batch 1, one epoch, no TF queues.
-The dataset downloaders (kitti/data.py) and the supervised fine-tuning input (input_train_gt :86-146) are out of scope."""
+"""Mirror of src/e2eflow/kitti/input.py without TF queues: the evaluation inputs of Trainer.eval (train.py:265-385) — image
+pairs of a KITTI `training` directory with their occluded / non-occluded ground-truth flow maps, batch 1, one epoch — and the
+supervised fine-tuning input input_train_gt (:86-146): KITTI 2015 + 2012 pairs with their flow_occ maps, jointly cropped.
+The dataset downloaders (kitti/data.py) are out of scope."""
 import os
 import random
 
 import numpy as np
 
-from ..core.input import Input, read_kitti_flow_png, read_png_image, resize_image_with_crop_or_pad
+from ..core.input import Input, decode_png, read_kitti_flow_png, read_png_image, resize_image_with_crop_or_pad
 
 
 class KITTIInput(Input):
@@ -64,3 +65,53 @@ class KITTIInput(Input):
 
     def input_test_2012(self, hold_out_inv=None):
         return self.input_test('data_stereo_flow/testing/colored_0', hold_out_inv)
+
+    def train_gt_files(self, hold_out):
+        """The example list of input_train_gt (kitti/input.py:86-124): per dataset (2015 image_2 + flow_occ, 2012 colored_0 +
+        flow_occ) images 2i and 2i+1 of the sorted listing go with GT file i; each list is shuffled with seed 0 and its first
+        `hold_out` entries dropped; the concatenation is shuffled again with seed 0.  [(im1, im2, gt), ...]."""
+        img_dirs = ['data_scene_flow/training/image_2', 'data_stereo_flow/training/colored_0']
+        gt_dirs = ['data_scene_flow/training/flow_occ', 'data_stereo_flow/training/flow_occ']
+        filenames = []
+        for img_dir, gt_dir in zip(img_dirs, gt_dirs):
+            img_dir = os.path.join(self.data.current_dir, img_dir)
+            gt_dir = os.path.join(self.data.current_dir, gt_dir)
+            img_files, gt_files = sorted(os.listdir(img_dir)), sorted(os.listdir(gt_dir))
+            assert len(img_files) % 2 == 0 and len(img_files) / 2 == len(gt_files)
+            ds = [(os.path.join(img_dir, img_files[2 * i]), os.path.join(img_dir, img_files[2 * i + 1]),
+                   os.path.join(gt_dir, gt_files[i])) for i in range(len(gt_files))]
+            random.seed(0)
+            random.shuffle(ds)
+            filenames.extend(ds[hold_out:])
+        random.seed(0)
+        random.shuffle(filenames)
+        return filenames
+
+    def input_train_gt(self, hold_out, seed=0, shift=0):
+        """input_train_gt (kitti/input.py:86-146): an endless iterator of (im1, im2, flow_gt, mask_gt) numpy batches
+        [B,h,w,3] x 2, [B,h,w,2], [B,h,w,1] over train_gt_files(hold_out), walked in order and cyclically like the
+        reference's string_input_producer(shuffle=False); random_crop takes ONE window of self.dims for both frames and the
+        16-bit GT (limit from im1's shape, RNG seeded with `seed`), the GT decodes as flow = (v - 2^15) / 64, mask = channel
+        2; the images are normalised when self.normalize.  shift: examples to skip at the start (resuming)."""
+        files = self.train_gt_files(hold_out)
+        h, w = self.dims
+        rng = np.random.RandomState(seed)
+        pos = shift
+        while True:
+            cols = [[] for _ in range(4)]
+            for _ in range(self.batch_size):
+                fn1, fn2, fgt = files[pos % len(files)]
+                pos += 1
+                a, b = read_png_image(fn1), read_png_image(fn2)
+                with open(fgt, 'rb') as f:
+                    gt = decode_png(f.read()).astype(np.float32)
+                oy = int(rng.randint(0, a.shape[0] - h + 1))
+                ox = int(rng.randint(0, a.shape[1] - w + 1))
+                a, b, gt = a[oy:oy + h, ox:ox + w], b[oy:oy + h, ox:ox + w], gt[oy:oy + h, ox:ox + w]
+                flow = (gt[:, :, 0:2] - 2 ** 15) / 64.0
+                mask = gt[:, :, 2:3]
+                if self.normalize:
+                    a, b = self._normalize_image(a), self._normalize_image(b)
+                for c, v in zip(cols, (a, b, flow, mask)):
+                    c.append(v)
+            yield tuple(np.stack(c).astype(np.float32) for c in cols)
