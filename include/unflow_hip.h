@@ -560,6 +560,40 @@ int unflow_l2_loss(const float* p, long n, float scale, float* loss_acc, unflow_
 int unflow_flow_error_sums(const float* f1, const float* f2, const float* mask /* may be NULL = ones */,
                            float* out2, long npix, unflow_stream_t stream);
 
+/* ===================================================================== */
+/* forward-only inference (csrc/inference.hip, core/inference.py)          */
+/* ===================================================================== */
+
+/* Per-sample geometry of both inference kernels: a DEVICE table desc[B][8] of int32 =
+ *   {h, w, y0, x0, nmaps, u8, 0, 0}: the frame's size, its origin in its staging row (may be negative: a frame taller / wider
+ *   than the staging buffer was centre-cropped into it), the ground-truth maps staged for it (0..2), and whether its staged
+ *   frames are uint8 (1) or fp32 (0) — the same for every sample of a launch.  h = 0: an unused slot of a short batch.
+ *   16-byte aligned.  The host rewrites the table between launches; a captured graph keeps its address. */
+
+/* frames [2][B][Hmax][Wmax][3] (uint8 or fp32, [0, 255], per desc u8) -> net_in4 [2B][H][W][4]: rows [0, B) from frame 0
+ * (im1), [B, 2B) from frame 1 (im2), each the TF1 legacy bilinear resample of the sample's (h, w) region at (y0, x0) (pixels
+ * outside the buffer read zero) to (H, W), then /255 - mean3/255 (unflow_prepare_image_pair's arithmetic; mean3 is a HOST
+ * pointer); channel 3 = 0.  A slot with h = 0 writes zeros.  net_pl (may be NULL): the operand planes as in
+ * unflow_prepare_image_pair. */
+int unflow_inference_input(const void* frames, const int* desc, int B, int Hmax, int Wmax, int H, int W, float* net_in4,
+                           const float* mean3, const unflow_planes* net_pl, unflow_stream_t stream);
+
+/* flow [B][fh][fw][2] (the last network's flow2, or flow0 at (H, W) with full_res) -> for every sample b with desc h > 0 and
+ * every frame pixel (y < h, x < w):
+ *   f = resize_tf1(resize_tf1(flow, H, W) * flow_scale, h, w) (full_res: resize_tf1(flow * flow_scale, h, w)),
+ *   u *= fp32(w / W), v *= fp32(h / H)  (resize_output_flow),
+ * bit-identical to unflow_resize_bilinear_tf1(flow, .., H, W, flow_scale) -> unflow_resize_bilinear_tf1(., .., h, w, 1) -> the
+ * per-axis multiply.  out_flow [B][Hmax][Wmax][2] (may be NULL) at (b, y, x); out_u16 [B][Hmax][Wmax][3] (may be NULL):
+ * uint16(max(0, min(f * 64 + 32768, 65535))) truncated, third channel 1.  gt_flow [2][B][Hmax][Wmax][2] and gt_mask
+ * [2][B][Hmax][Wmax] (both NULL: no metrics) staged like the frames (frame pixel (y, x) at (y + y0, x + x0), zero outside);
+ * for the desc's nmaps maps k: sums[b][k][0] = sum |gt - f| * m, sums[b][k][1] = sum m (fp64), counts[b][k] = #(|gt - f| * m
+ * >= max(3, 0.05 |gt|)).  Fixed-order reduction: partial = B * unflow_inference_output_blocks(Hmax, Wmax) * 6 doubles of
+ * scratch, ticket = B zero-initialised uint32 (left zero by every launch). */
+int unflow_inference_output_blocks(int Hmax, int Wmax);
+int unflow_inference_output(const float* flow, int fh, int fw, float flow_scale, int H, int W, const int* desc, int B, int Hmax,
+                            int Wmax, float* out_flow, unsigned short* out_u16, const float* gt_flow, const float* gt_mask,
+                            double* partial, unsigned* ticket, double* sums, int* counts, unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

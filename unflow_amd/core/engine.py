@@ -266,7 +266,7 @@ class _Stage:
         # FlowNetC feature tower (conv1 .. conv3, the conv2 segment of cat2) runs on both frames, 2B rows; everything from
         # conv_redir and the correlation on, and every buffer of a FlowNetS, has B rows
         enc = ('c1', 'cat2', 'c3') if self.is_c else ()
-        one_dir = getattr(eng, 'supervised', False)
+        one_dir = getattr(eng, 'one_dir', False)
         # (a stage built for its layer table alone, without an engine's shape, counts rows in units of B)
         nB, nN = (eng.B, eng.N) if hasattr(eng, 'N') else (1, 2)
         self.rows = {name: (nN if (not one_dir or name in enc) else nB) for name in B}
@@ -403,7 +403,7 @@ class _Stage:
             x0s = self.act['x0s']
             pf = prev_flow2
             ph, pw = (0, 0) if pf is None else (pf.shape[1], pf.shape[2])
-            if e.supervised:      # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B)
+            if e.one_dir:         # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B)
                 check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[:B]), ptr(e.x0[B:]), ptr(pf), ptr(x0s), x0s.stride(2), B,
                                                          e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
             else:
@@ -419,7 +419,7 @@ class _Stage:
                 C = op.src[2] - op.src[1]
                 h8, w8 = e.H // 8, e.W // 8
                 pl = self._corr_planes(c3, refresh=True)                      # bf16 x 3 planes: the matrix-core path
-                if e.supervised:      # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
+                if e.one_dir:         # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
                     p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, B:]))
                     check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[:B]), ptr(c3.t[B:]), c3.t.stride(2), p0, p1, 0,
                                                                     ptr(out.t), out.t.stride(2), B, C, h8, w8, 1, 20, 20, 1, 2,
@@ -595,11 +595,20 @@ class FlowNetEngine:
     every FlowNetS — on the B forward pairs only; the loss is the masked Charbonnier of the final flow against set_input's
     target (unflow_supervised_flow_loss per counted network)."""
 
-    def __init__(self, batch, height, width, params=None, device=None, seed=0, layout_only=False, supervised=False):
+    def __init__(self, batch, height, width, params=None, device=None, seed=0, layout_only=False, supervised=False,
+                 inference=False):
         """layout_only: build the layer table and the flat parameter / gradient buffers (on `device`, which may then be the
-        CPU) but no activations — for tools and the data-parallel tests that only need the flat layout and its buckets."""
+        CPU) but no activations — for tools and the data-parallel tests that only need the flat layout and its buckets.
+        inference: the forward-only engine (core/inference.py): the one-direction plan of supervised=True, and only what the
+        forward pass reads — the parameters P (no G / M / V), no activation gradients, no loss buffers, and of the weight
+        planes only the layout the forward kernels take (transposed for conv layers, direct for conv_transpose layers).  The
+        flat parameter layout is the training engine's, so load_tf_params / export_tf_params / checkpoints work unchanged."""
         assert height % 64 == 0 and width % 64 == 0, "FlowNet needs H, W divisible by 64"
+        if supervised and inference:
+            raise ValueError("FlowNetEngine: supervised and inference are exclusive")
         self.supervised = bool(supervised)
+        self.inference = bool(inference)
+        self.one_dir = self.supervised or self.inference     # FlowNetC tower on 2B rows, everything after it on B rows
         self.params = dict(DEFAULT_PARAMS) if params is None else dict(params)
         if self.params.get('mask_occlusion', '') not in ('', 'fb', 'disocc'):   # unsupervised.py:125-126
             raise ValueError("mask_occlusion must be one of 'fb', 'disocc', ''")
@@ -646,12 +655,15 @@ class FlowNetEngine:
             self.stages = [_Stage(self, k, i, self.full_res and i == len(spec) - 1) for i, k in enumerate(spec)]
             for st in self.stages[:-1]:
                 st.trainable = self.train_all
+            if self.inference:
+                for st in self.stages:
+                    st.trainable = False
             self.layers = [l for st in self.stages for l in st.layers]
             self.by_name = self.stages[-1].by_name
             self._alloc_params()
             if not layout_only:
                 self._alloc_activations()
-                if self.wgrad_group > 0 and self.dev.type == 'cuda':
+                if self.wgrad_group > 0 and self.dev.type == 'cuda' and not self.inference:
                     self.wgrad_stream = torch.cuda.Stream(self.dev)
                 self._build_masks()
         self.step_count = 0
@@ -672,18 +684,20 @@ class FlowNetEngine:
         nb = sum(l.cout_p for l in self.layers)
         self.n_weights, self.n_params = nw, nw + nb
         z = lambda: torch.zeros(self.n_params, dtype=torch.float32, device=self.dev)
-        self.P, self.G, self.M, self.V = z(), z(), z(), z()
+        self.P = z()
+        self.G, self.M, self.V = (None, None, None) if self.inference else (z(), z(), z())
+        view = lambda flat, lo, hi, shape=None: None if flat is None else (flat[lo:hi] if shape is None else flat[lo:hi].view(shape))
         off = 0
         for l in self.layers:
             n = int(torch.Size(l.wshape()).numel())
             l.w = self.P[off:off + n].view(l.wshape())
-            l.dw = self.G[off:off + n].view(l.wshape())
-            l.mw, l.vw = self.M[off:off + n].view(l.wshape()), self.V[off:off + n].view(l.wshape())   # Adam slots
+            l.dw = view(self.G, off, off + n, l.wshape())
+            l.mw, l.vw = view(self.M, off, off + n, l.wshape()), view(self.V, off, off + n, l.wshape())   # Adam slots
             off += n
         for l in self.layers:
             l.b = self.P[off:off + l.cout_p]
-            l.db = self.G[off:off + l.cout_p]
-            l.mb, l.vb = self.M[off:off + l.cout_p], self.V[off:off + l.cout_p]
+            l.db = view(self.G, off, off + l.cout_p)
+            l.mb, l.vb = view(self.M, off, off + l.cout_p), view(self.V, off, off + l.cout_p)
             off += l.cout_p
         # operand planes of the weights (csrc/conv_planes.hip): direct [P][tap][R][round8(Cc)], transposed
         # [P][tap][Cc][round8(R)] of W[tap][R][Cc]; one flat int16 buffer, refreshed by one batched launch
@@ -693,34 +707,47 @@ class FlowNetEngine:
             users = [l for l in self.layers if l.uses_planes()]
             tot = 0
             for l in users:
+                d, t = self._wp_layouts(l)
                 taps, R, Cc = l.wplane_view()
-                tot += P * (taps * R * round8(Cc) + taps * Cc * round8(R))
+                tot += P * (d * taps * R * round8(Cc) + t * taps * Cc * round8(R))
             self.WP = torch.zeros(tot, dtype=torch.int16, device=self.dev)
             off = 0
             for l in users:
+                d, t = self._wp_layouts(l)
                 taps, R, Cc = l.wplane_view()
-                n = P * taps * R * round8(Cc)
-                l.wpl_d = self.WP[off:off + n].view(P, taps, R, round8(Cc))
-                off += n
-                n = P * taps * Cc * round8(R)
-                l.wpl_t = self.WP[off:off + n].view(P, taps, Cc, round8(R))
-                off += n
+                if d:
+                    n = P * taps * R * round8(Cc)
+                    l.wpl_d = self.WP[off:off + n].view(P, taps, R, round8(Cc))
+                    off += n
+                if t:
+                    n = P * taps * Cc * round8(R)
+                    l.wpl_t = self.WP[off:off + n].view(P, taps, Cc, round8(R))
+                    off += n
             self._wp_users = users
             self._wp_table = self._wp_table_of(users)
             self._wp_range_tables = {}
         self._adam_tables = {}
 
+    def _wp_layouts(self, l):
+        """(direct, transposed): the weight-plane layouts a layer needs.  Training: both (forward and data gradient).
+        Inference: only what the forward kernels take — transposed for a conv (conv_fwd), direct for a conv_transpose
+        (deconv_fwd)."""
+        if not self.inference:
+            return True, True
+        return (l.kind == 'deconv'), (l.kind == 'conv')
+
     @staticmethod
     def _wp_table_of(users):
         import ctypes
         n = len(users)
+        addr = lambda t: None if t is None else t.data_ptr()          # noqa: E731  (NULL: that layout is not kept)
         return (n,
                 (ctypes.c_void_p * n)(*[l.w.data_ptr() for l in users]),
                 (ctypes.c_int * n)(*[l.wplane_view()[0] for l in users]),
                 (ctypes.c_int * n)(*[l.wplane_view()[1] for l in users]),
                 (ctypes.c_int * n)(*[l.wplane_view()[2] for l in users]),
-                (ctypes.c_void_p * n)(*[l.wpl_d.data_ptr() for l in users]),
-                (ctypes.c_void_p * n)(*[l.wpl_t.data_ptr() for l in users]))
+                (ctypes.c_void_p * n)(*[addr(l.wpl_d) for l in users]),
+                (ctypes.c_void_p * n)(*[addr(l.wpl_t) for l in users]))
 
     def refresh_weight_planes(self, force=False):
         """Re-split the parameters into their operand planes.  Needed whenever P changed: adam_step marks it; in-place
@@ -841,7 +868,7 @@ class FlowNetEngine:
         self.X0 = L.PT(z(N, H, W, 4), torch.zeros(self.n_planes, N, H, W, 4 if (W % 2 == 0 and RGB4_FORM) else 8, dtype=torch.int16, device=dev)
                        if self.n_planes else None)
         self.x0 = self.X0.t
-        self.im01 = z(N, H, W, 3)     # images in [0,1] for the losses
+        self.im01 = None if self.inference else z(N, H, W, 3)     # images in [0,1] for the losses
         for st in self.stages:
             st.alloc()
         last = self.stages[-1]
@@ -850,6 +877,12 @@ class FlowNetEngine:
         self.act.update(last.act)
         self.act.update(x0=self.x0, im01=self.im01)
         self.grad = last.grad
+        if self.inference:
+            # the output of final_flows(); no targets, no loss pyramid, no masks
+            self.lv = []
+            self.final_flow = z(self.B, H, W, 2)
+            self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
+            return
         if self.supervised:
             # engine-owned targets (fixed addresses for the captured graphs; set_input copies into them); no loss pyramid
             self.flow_gt, self.mask_gt = z(self.B, H, W, 2), z(self.B, H, W, 1)
@@ -882,8 +915,8 @@ class FlowNetEngine:
         of the engine (so a captured hipGraph never holds a stale mask pointer): without augmentation it holds B copies of
         the static mask, with augmentation the per-sample warped masks."""
         from .. import ops
-        if self.supervised:
-            return                # no border mask in the supervised loss (supervised.py:12-65)
+        if self.one_dir:
+            return                # no border mask in the supervised loss (supervised.py:12-65), no loss at all in inference
         H, W, B = self.H, self.W, self.B
         sz = int(math.ceil(min(H, W) * 0.1))
         m = torch.zeros(1, H, W, 1, device=self.dev)
@@ -914,6 +947,8 @@ class FlowNetEngine:
         st = self.stream()
         if self.supervised:
             return self._set_input_supervised(im1, im2, augment, target)
+        if self.inference:
+            return self._set_input_inference(im1, im2, augment, target)
         if target is not None:
             raise ValueError("set_input: a target is for the supervised engine (FlowNetEngine(..., supervised=True))")
         # the kernels below take raw device pointers: bring whatever the input pipeline delivers (numpy batches of
@@ -996,6 +1031,26 @@ class FlowNetEngine:
         A.photometric(self.im01, augment, out=self.x0, mean=CHANNEL_MEAN)
         self._input_planes()
 
+    def _set_input_inference(self, im1, im2, augment, target):
+        """The network input of the forward-only engine from two [B,H,W,3] batches in [0,255] (no augmentation, no target;
+        core/inference.py stages and resizes frames of any size with unflow_inference_input instead)."""
+        if augment is not None or target is not None:
+            raise ValueError("set_input: the inference engine takes neither augmentation draws nor a target")
+        B, H, W = self.B, self.H, self.W
+        im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
+        im2 = torch.as_tensor(im2).to(device=self.dev, dtype=torch.float32).contiguous()
+        if tuple(im1.shape) != (B, H, W, 3) or tuple(im2.shape) != (B, H, W, 3):
+            raise ValueError("set_input: expected two [%d,%d,%d,3] batches, got %s and %s"
+                             % (B, H, W, tuple(im1.shape), tuple(im2.shape)))
+        pl = self.X0.pl if (self.X0.pl is not None and self.stages[0].is_c) else None
+        check(_lib.lib().unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(None), self.mean_host,
+                                                   _lib.planes_of(pl), self.stream()), "prepare_image_pair")
+
+    def _no_training(self, what):
+        if self.inference:
+            raise RuntimeError("%s: this is a forward-only engine (FlowNetEngine(..., inference=True)); it has no loss, "
+                               "gradients or optimizer state" % what)
+
     def _input_planes(self):
         """Operand planes of the network input for conv1 of a FlowNetC (FlowNetS stages build theirs after stack_input)."""
         if self.X0.pl is not None and self.stages[0].is_c:
@@ -1015,6 +1070,7 @@ class FlowNetEngine:
         """compute_losses + the pyramid assembly (losses.py:16-87, unsupervised.py:85-150) over the directed batch;
         with_grad also leaves d(loss)/d(flowN) in self.grad['flowN'].  Terms enter iff their `<name>_weight` is set
         (unsupervised.py:136-141), exactly the pruning TF does."""
+        self._no_training("forward_loss")
         if self.supervised:
             return self._forward_loss_supervised(with_grad)
         lib = _lib.lib()
@@ -1198,6 +1254,7 @@ class FlowNetEngine:
     def backward_net(self, part=None):
         """Gradients of the trained (last) network; earlier stages are behind stop_gradient (flownet.py:51-54).
         part 0 / 1: the two halves used to overlap the data-parallel all-reduce (see grad_buckets)."""
+        self._no_training("backward_net")
         last_part = len(self.stages[-1].part_bounds) - 2
         with torch.cuda.device(self.dev):
             # the batched bias gradients (column sums of every dz: HBM-bound) go out on the main stream once the last data
@@ -1381,6 +1438,7 @@ class FlowNetEngine:
     def adam_step(self, lr, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8):
         """tf.train.AdamOptimizer(beta1=0.9, beta2=0.999) update (train.py:151-152), TF formulation, with the
         slim.l2_regularizer(0.0004) gradient added for the weight tensors (biases are not regularised)."""
+        self._no_training("adam_step")
         self.step_count += 1
         t = self.step_count
         lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
@@ -1428,6 +1486,7 @@ class FlowNetEngine:
 
     # ------------------------------------------------------------------ composite
     def fwd_bwd(self, im1=None, im2=None, target=None):
+        self._no_training("fwd_bwd")
         if im1 is not None:
             self.set_input(im1, im2, target=target)
         self.forward_net()
@@ -1438,6 +1497,7 @@ class FlowNetEngine:
     def train_step(self, im1, im2, lr, target=None):
         """One optimisation step; returns the loss tensor [1] (complete once the Adam kernel has run: the 0.0004*sum(w^2)/2
         term is accumulated by the pass Adam makes over the parameters, not by a separate reduction)."""
+        self._no_training("train_step")
         prev, self.defer_l2 = self.defer_l2, True
         try:
             loss = self.fwd_bwd(im1, im2, target)
@@ -1448,27 +1508,27 @@ class FlowNetEngine:
 
     def final_flows(self):
         """final_flow_fw / _bw: resize_bilinear(flow2, im_shape) * 5 * 4 (unsupervised.py:103-104), or flow0 * 20 with
-        full_res (unsupervised.py:95-97).  Supervised engine: (final_flow_fw, None)."""
+        full_res (unsupervised.py:95-97).  One-direction (supervised, inference) engine: (final_flow_fw, None)."""
         if self.full_res:
             f0 = self.act['flow0']
             check(_lib.lib().unflow_scale(ptr(f0), cf(FLOW_SCALE * 4), ptr(self.final_flow), cl(f0.numel()), self.stream()), "scale")
-            if self.supervised:
+            if self.one_dir:
                 return self.final_flow, None
             return self.final_flow[:self.B], self.final_flow[self.B:]
         f2 = self.act['flow2']
         N, h, w, _ = f2.shape
         check(_lib.lib().unflow_resize_bilinear_tf1(ptr(f2), ptr(self.final_flow), N, h, w, 2, self.H, self.W,
                                                     cf(FLOW_SCALE * 4), self.stream()), "resize_bilinear")
-        if self.supervised:
+        if self.one_dir:
             return self.final_flow, None
         return self.final_flow[:self.B], self.final_flow[self.B:]
 
     def flows(self):
         """(flows_fw, flows_bw): lists [flow2..flow6] ([flow0, flow1, flow2..] with full_res), NHWC, like
-        flownet(..., backward_flow=True)[-1].  Supervised engine: (flows_fw, None)."""
+        flownet(..., backward_flow=True)[-1].  One-direction engine: (flows_fw, None)."""
         B = self.B
         lv = self.stages[-1].flow_levels
-        if self.supervised:
+        if self.one_dir:
             return [self.act['flow%d' % l] for l in lv], None
         fw = [self.act['flow%d' % l][:B] for l in lv]
         bw = [self.act['flow%d' % l][B:] for l in lv]

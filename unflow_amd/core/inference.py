@@ -1,0 +1,378 @@
+"""Forward-only flow inference: what a user does with a trained model — flow for new frames, a checkpoint scored on KITTI,
+files for the benchmark (the non-GUI part of the reference's src/eval_gui.py).
+
+FlowEstimator owns one forward-only engine (FlowNetEngine(..., inference=True)), fixed device staging buffers, a device
+table of per-sample frame geometry and one captured hipGraph on one stream:
+
+    unflow_inference_input   staged frames (uint8 or fp32, any size up to max_frame) -> network input (+ conv1's planes)
+    engine.forward_net()
+    unflow_inference_output  flow2 -> frame-size flow [B][Hmax][Wmax][2], its KITTI 16-bit encoding, EPE / outlier sums
+
+Every batch — any mix of frame sizes, a short last one — replays the same graph: the host rewrites the geometry table
+(csrc/inference.hip).  Host staging is double-buffered in pinned memory; before the host overwrites a slot it waits for the
+event recorded after the last replay that read it (and the copies that brought its outputs back).
+"""
+import itertools
+import os
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import check, ptr
+from .engine import FLOW_SCALE, FlowNetEngine
+
+ENGINE_KEYS = ('flownet', 'train_all', 'full_res', 'pyramid_loss', 'border_mask', 'mask_occlusion')   # = Trainer.ENGINE_KEYS
+MAP_NAMES = {2: ('occluded', 'non-occluded'), 1: ('all',)}
+
+
+# ------------------------------------------------------------------------------------------------- host batch packing
+def frame_origin(n, staged):
+    """Where a frame of size n starts in a staged axis of size `staged` that holds resize_image_with_crop_or_pad(frame,
+    staged): its zero-padding offset (n <= staged) or minus its crop offset (n > staged) — TF's split, odd extra to the
+    bottom / right."""
+    return (staged - n) // 2 if n <= staged else -((n - staged) // 2)
+
+
+def pack_desc(shapes, batch, staged=None, nmaps=0, u8=False):
+    """The device table of unflow_inference_input / _output (include/unflow_hip.h): int32 [batch][8] =
+    {h, w, y0, x0, nmaps, u8, 0, 0} per sample.  shapes: the frames' (h, w), at most `batch` of them (the rest of the
+    slots: h = 0, unused).  staged None: raw frames at the origin of their staging row; (Hs, Ws): frames as KITTIInput
+    delivers them, cropped / padded to (Hs, Ws) (origins as resize_image_with_crop_or_pad)."""
+    if len(shapes) > batch:
+        raise ValueError("%d frames for a batch of %d" % (len(shapes), batch))
+    d = np.zeros((batch, 8), dtype=np.int32)
+    for i, (h, w) in enumerate(shapes):
+        y0, x0 = (0, 0) if staged is None else (frame_origin(int(h), staged[0]), frame_origin(int(w), staged[1]))
+        d[i] = (int(h), int(w), y0, x0, nmaps, int(bool(u8)), 0, 0)
+    return d
+
+
+def example_stream(batch_iter):
+    """Examples of what KITTIInput.input_{train,test}_{2012,2015}() yields, one tuple per example: batches of
+    (im1, im2, input_shape[, flow_occ, mask_occ, flow_noc, mask_noc]) or the 2-map form (..., flow_gt, mask)."""
+    for batch in batch_iter:
+        if len(batch) not in (3, 5, 7):
+            raise ValueError("a batch is (im1, im2, input_shape) + 0, 1 or 2 (flow, mask) pairs; got %d arrays" % len(batch))
+        arrs = [np.asarray(t.cpu().numpy() if isinstance(t, torch.Tensor) else t) for t in batch]
+        for i in range(arrs[0].shape[0]):
+            yield tuple(a[i] for a in arrs)
+
+
+def chunks(it, n):
+    buf = []
+    for x in it:
+        buf.append(x)
+        if len(buf) == n:
+            yield buf
+            buf = []
+    if buf:
+        yield buf
+
+
+class _Slot:
+    """One set of pinned host buffers and the event of the last device work that read or wrote them."""
+
+    def __init__(self, est):
+        B, Hm, Wm = est.B, est.Hmax, est.Wmax
+        pin = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, pin_memory=True)   # noqa: E731
+        self.frames = pin(2 * B * Hm * Wm * 3 * 4, dtype=torch.uint8)        # fp32-sized; uint8 frames use the first quarter
+        self.desc = pin(B, 8, dtype=torch.int32)
+        self.gt_flow = self.gt_mask = None
+        self.flow = pin(B, Hm, Wm, 2)
+        self.u16 = pin(B, Hm, Wm, 3, dtype=torch.int16)
+        self.sums = pin(B, 2, 2, dtype=torch.float64)
+        self.counts = pin(B, 2, dtype=torch.int32)
+        self.event = None
+        self.pending = None
+
+    def gt(self, est):
+        if self.gt_flow is None:
+            B, Hm, Wm = est.B, est.Hmax, est.Wmax
+            self.gt_flow = torch.zeros(2, B, Hm, Wm, 2, pin_memory=True)
+            self.gt_mask = torch.zeros(2, B, Hm, Wm, pin_memory=True)
+        return self.gt_flow, self.gt_mask
+
+    def wait(self):
+        if self.event is not None:
+            self.event.synchronize()
+
+
+class FlowEstimator:
+    """Frame-size optical flow of a trained FlowNet spec (params['flownet'], 'full_res', ...), `batch` pairs per replay at the
+    network size net_size = (H, W) (divisible by 64), frames of any size up to max_frame (default: net_size)."""
+
+    def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True):
+        self.params = dict(params)
+        self.B = int(batch)
+        self.H, self.W = (int(v) for v in net_size)
+        self.Hmax, self.Wmax = (int(v) for v in (max_frame or net_size))
+        self.dev = torch.device('cuda:0') if device is None else torch.device(device)
+        self.use_graph = bool(use_graph)
+        eng_params = {k: v for k, v in self.params.items() if k.endswith('_weight') or k in ENGINE_KEYS}
+        self.engine = FlowNetEngine(self.B, self.H, self.W, params=eng_params or None, device=self.dev, seed=None,
+                                    inference=True)
+        e = self.engine
+        B, Hm, Wm = self.B, self.Hmax, self.Wmax
+        L = _lib.lib()
+        with torch.cuda.device(self.dev):
+            z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.dev)   # noqa: E731
+            self.frames = z(2 * B * Hm * Wm * 3 * 4, dtype=torch.uint8)
+            self.desc = z(B, 8, dtype=torch.int32)
+            self.gt_flow, self.gt_mask = z(2, B, Hm, Wm, 2), z(2, B, Hm, Wm)
+            self.out_flow = z(B, Hm, Wm, 2)
+            self.out_u16 = z(B, Hm, Wm, 3, dtype=torch.int16)
+            nb = int(L.unflow_inference_output_blocks(Hm, Wm))
+            self.partial = z(B * nb * 6, dtype=torch.float64)
+            self.ticket = z(B, dtype=torch.int32)
+            self.sums = z(B, 2, 2, dtype=torch.float64)
+            self.counts = z(B, 2, dtype=torch.int32)
+        last = e.stages[-1]
+        self.flow_src = last.act['flow0'] if e.full_res else last.act['flow2']
+        self.in_planes = e.X0.pl if (e.X0.pl is not None and e.stages[0].is_c) else None
+        self.slots = None
+        self.graph = None
+        self.global_step = None
+        self._dims = None             # the staged (KITTIInput) frame size of the current evaluate / export pass
+
+    # ------------------------------------------------------------------------------------------ parameters
+    @classmethod
+    def from_checkpoint(cls, ckpt_dir, params, *args, **kwargs):
+        """An estimator with the networks Trainer.restore(ckpt_dir, engine=...) would restore: the trained networks from the
+        latest checkpoint of ckpt_dir, frozen networks of a stack from params['finetune'] (or the checkpoint, when it holds
+        them).  A network with no source is an error (train.network_files(strict=True))."""
+        from .input import restore_networks
+        from .train import network_files
+        est = cls(params, *args, **kwargs)
+        files, ckpt = network_files(est.params, est.engine.spec, ckpt_dir, strict=True)
+        restore_networks(est.engine, est.params, files)
+        est._params_changed()
+        est.global_step = None if ckpt is None else int(os.path.basename(ckpt).split('-')[-1])
+        return est
+
+    def load_tf_params(self, tf_params):
+        self.engine.load_tf_params(tf_params)
+        self._params_changed()
+
+    def _params_changed(self):
+        with torch.cuda.device(self.dev):
+            self.engine.refresh_weight_planes(force=True)      # the captured graph does not re-split: weights are static here
+
+    # ------------------------------------------------------------------------------------------ device work
+    def _launch(self):
+        """Input kernel, forward pass, output kernel on the current stream (what the graph holds)."""
+        e = self.engine
+        L = _lib.lib()
+        st = e.stream()
+        check(L.unflow_inference_input(ptr(self.frames), ptr(self.desc), self.B, self.Hmax, self.Wmax, self.H, self.W,
+                                       ptr(e.x0), e.mean_host, _lib.planes_of(self.in_planes), st), "inference_input")
+        e.forward_net()
+        f = self.flow_src
+        check(L.unflow_inference_output(ptr(f), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(self.desc),
+                                        self.B, self.Hmax, self.Wmax, ptr(self.out_flow), ptr(self.out_u16), ptr(self.gt_flow),
+                                        ptr(self.gt_mask), ptr(self.partial), ptr(self.ticket), ptr(self.sums),
+                                        ptr(self.counts), st), "inference_output")
+
+    def _run(self):
+        e = self.engine
+        if not self.use_graph:
+            self._launch()
+            return
+        if self.graph is None:
+            e.refresh_weight_planes(force=True)
+            e.planes_external = True          # the weights are static: the graph does not re-split them
+            self._launch()                    # eager pass first: grows the shared workspaces outside the capture
+            torch.cuda.current_stream(self.dev).synchronize()
+            s = torch.cuda.Stream(self.dev)
+            s.wait_stream(torch.cuda.current_stream(self.dev))
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    self._launch()
+            torch.cuda.current_stream(self.dev).wait_stream(s)
+            self.graph = g
+        self.graph.replay()
+
+    # ------------------------------------------------------------------------------------------ staging
+    def _slot(self, k):
+        if self.slots is None:
+            self.slots = [_Slot(self), _Slot(self)]
+        return self.slots[k % 2]
+
+    def _stage(self, slot, examples, staged, nmaps):
+        """Pack up to B examples (im1, im2, (h, w)[, gt flow, mask ...]) into the pinned slot; returns (desc, frame bytes)."""
+        B, Hm, Wm = self.B, self.Hmax, self.Wmax
+        u8 = all(np.asarray(ex[0]).dtype == np.uint8 and np.asarray(ex[1]).dtype == np.uint8 for ex in examples)
+        esz = 1 if u8 else 4
+        nbytes = 2 * B * Hm * Wm * 3 * esz
+        fr = slot.frames[:nbytes].numpy().view(np.uint8 if u8 else np.float32).reshape(2, B, Hm, Wm, 3)
+        shapes = []
+        for i, ex in enumerate(examples):
+            h, w = int(ex[2][0]), int(ex[2][1])
+            if h > Hm or w > Wm:
+                raise ValueError("a %dx%d frame exceeds max_frame %dx%d" % (h, w, Hm, Wm))
+            shapes.append((h, w))
+            for k in range(2):
+                a = np.asarray(ex[k])
+                hs, ws = a.shape[:2]
+                if hs > Hm or ws > Wm:
+                    raise ValueError("a staged frame of %dx%d exceeds max_frame %dx%d" % (hs, ws, Hm, Wm))
+                fr[k, i, :hs, :ws] = a
+                if staged is not None:           # the parts of the row outside the staged array read as zero
+                    fr[k, i, hs:] = 0
+                    fr[k, i, :hs, ws:] = 0
+            if nmaps:
+                gf, gm = slot.gt(self)
+                for m in range(nmaps):
+                    f, msk = np.asarray(ex[3 + 2 * m], dtype=np.float32), np.asarray(ex[4 + 2 * m], dtype=np.float32)
+                    hs, ws = f.shape[:2]
+                    gfa, gma = gf[m, i].numpy(), gm[m, i].numpy()
+                    gfa[:hs, :ws] = f
+                    gma[:hs, :ws] = msk.reshape(hs, ws)
+                    gfa[hs:] = 0
+                    gfa[:hs, ws:] = 0
+                    gma[hs:] = 0
+                    gma[:hs, ws:] = 0
+        slot.desc.numpy()[:] = pack_desc(shapes, B, staged, nmaps, u8)
+        return shapes, nbytes
+
+    def _submit(self, k, examples, staged=None, nmaps=0, want=('flow',)):
+        """Stage batch k into its slot, copy it in, run, and queue the copies back; returns the slot."""
+        slot = self._slot(k)
+        slot.wait()                               # the last replay that read this slot's buffers (and its copies back) is done
+        shapes, nbytes = self._stage(slot, examples, staged, nmaps)
+        with torch.cuda.device(self.dev):
+            cur = torch.cuda.current_stream(self.dev)
+            self.desc.copy_(slot.desc, non_blocking=True)
+            self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
+            if nmaps:
+                gf, gm = slot.gt(self)
+                self.gt_flow[:nmaps].copy_(gf[:nmaps], non_blocking=True)
+                self.gt_mask[:nmaps].copy_(gm[:nmaps], non_blocking=True)
+            self._run()
+            if 'flow' in want:
+                slot.flow.copy_(self.out_flow, non_blocking=True)
+            if 'u16' in want:
+                slot.u16.copy_(self.out_u16, non_blocking=True)
+            if nmaps:
+                slot.sums.copy_(self.sums, non_blocking=True)
+                slot.counts.copy_(self.counts, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+        slot.event = ev
+        slot.pending = (shapes, nmaps)
+        return slot
+
+    def _pipeline(self, batches, staged=None, nmaps_of=lambda b: 0, want=('flow',)):
+        """Yields (slot, shapes, nmaps, examples) per batch, in order; batch k + 1 is staged and queued before batch k is
+        handed to the caller, so host packing overlaps the device."""
+        prev = None
+        for k, exs in enumerate(batches):
+            nm = nmaps_of(exs)
+            slot = self._submit(k, exs, staged, nm, want)
+            if prev is not None:
+                yield self._collect(*prev)
+            prev = (slot, exs)
+        if prev is not None:
+            yield self._collect(*prev)
+
+    @staticmethod
+    def _collect(slot, exs):
+        slot.wait()
+        shapes, nmaps = slot.pending
+        return slot, shapes, nmaps, exs
+
+    # ------------------------------------------------------------------------------------------ public API
+    def estimate(self, frames1, frames2):
+        """Flow of every pair (frames1[i] -> frames2[i]): frames [h_i, w_i, 3] uint8 or float32 in [0, 255], any size up to
+        max_frame (both frames of a pair the same size).  Returns a list of [h_i, w_i, 2] float32 arrays."""
+        if len(frames1) != len(frames2):
+            raise ValueError("estimate: %d first frames, %d second frames" % (len(frames1), len(frames2)))
+        exs = []
+        for a, b in zip(frames1, frames2):
+            a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+            b = np.asarray(b.cpu().numpy() if isinstance(b, torch.Tensor) else b)
+            if a.shape != b.shape or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("estimate: a pair must be two [h, w, 3] frames of one size, got %s and %s" % (a.shape, b.shape))
+            if a.dtype != np.uint8:
+                a, b = a.astype(np.float32, copy=False), b.astype(np.float32, copy=False)
+            exs.append((a, b, a.shape[:2]))
+        out = []
+        for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B)):
+            fl = slot.flow.numpy()
+            out += [fl[i, :h, :w].copy() for i, (h, w) in enumerate(shapes)]
+        return out
+
+    def evaluate(self, batch_iter, num=None):
+        """Scores on what KITTIInput.input_train_{2012,2015}() yields — (im1, im2, input_shape, flow_occ, mask_occ, flow_noc,
+        mask_noc) — or the 2-map form (im1, im2, input_shape, flow_gt, mask), any batch size.  The frames are the
+        KITTIInput layout (cropped / padded to its dims, normalize=False); the flow is scored at each frame's own size
+        against the ground truth cropped back the same way (Trainer.eval's chain).  Returns the per-example averages of
+        AEE/<map> and outliers/<map> (%) — map = occluded, non-occluded (or all) — num_examples and per_example (rows in
+        `names` order).  num: at most that many examples."""
+        names, rows = None, []
+        it = example_stream(batch_iter)
+        if num is not None:
+            it = (ex for i, ex in zip(range(int(num)), it))
+        for slot, shapes, nmaps, _ in self._pipeline_staged(it, (), lambda exs: (len(exs[0]) - 3) // 2):
+            if nmaps == 0:
+                raise ValueError("evaluate: the batches carry no ground truth (a test split); use export()")
+            if names is None:
+                names = [n for m in MAP_NAMES[nmaps] for n in ('AEE/' + m, 'outliers/' + m)]
+            sums, counts = slot.sums.numpy(), slot.counts.numpy()
+            for i in range(len(shapes)):
+                row = []
+                for m in range(nmaps):
+                    err, msk = float(sums[i, m, 0]), float(sums[i, m, 1])
+                    row += [err / msk, 100.0 * float(counts[i, m]) / msk]
+                rows.append(row)
+        if not rows:
+            raise ValueError("evaluate: the input yielded no examples")
+        avg = np.mean(np.asarray(rows, dtype=np.float64), axis=0)
+        out = {k: float(v) for k, v in zip(names, avg)}
+        out.update(num_examples=len(rows), per_example=rows, names=names)
+        return out
+
+    def _staged_examples(self, it):
+        """Examples of the KITTIInput layout (all cropped / padded to one size): that size is remembered for the origins of the
+        descriptor table."""
+        for ex in it:
+            dims = np.asarray(ex[0]).shape[:2]
+            if self._dims is None:
+                self._dims = dims
+            elif tuple(dims) != tuple(self._dims):
+                raise ValueError("evaluate / export: the input's frames changed size (%s, then %s)" % (self._dims, dims))
+            yield ex
+
+    def _pipeline_staged(self, it, want, nmaps_of):
+        """_pipeline over examples of the KITTIInput layout."""
+        self._dims = None
+        gen = self._staged_examples(it)
+        first = next(gen, None)
+        if first is None:
+            return
+        batches = chunks(itertools.chain([first], gen), self.B)
+        yield from self._pipeline(batches, staged=tuple(self._dims), nmaps_of=nmaps_of, want=want)
+
+    def export(self, batch_iter, out_dir, fmt='png', num=None):
+        """The benchmark files of eval_gui.py --output_benchmark (:247-260): for the k-th example in iteration order,
+        out_dir/%06d_10.png (KITTI 16-bit RGB, --output_png) or out_dir/%06d_10.flo.  Input: what
+        KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths."""
+        from .input import write_flo, write_kitti_flow_png
+        if fmt not in ('png', 'flo'):
+            raise ValueError("export: fmt must be 'png' or 'flo'")
+        os.makedirs(out_dir, exist_ok=True)
+        it = example_stream(batch_iter)
+        if num is not None:
+            it = (ex for i, ex in zip(range(int(num)), it))
+        paths = []
+        want = ('u16',) if fmt == 'png' else ('flow',)
+        for slot, shapes, _, _ in self._pipeline_staged(it, want, lambda exs: 0):
+            for i, (h, w) in enumerate(shapes):
+                path = os.path.join(out_dir, '%06d_10.%s' % (len(paths), fmt))
+                if fmt == 'png':
+                    write_kitti_flow_png(path, slot.u16.numpy()[i, :h, :w].view(np.uint16))
+                else:
+                    write_flo(path, slot.flow.numpy()[i, :h, :w])
+                paths.append(path)
+        return paths

@@ -222,6 +222,26 @@ def read_kitti_flow_png(path):
     return torch.from_numpy(flow.copy()), torch.from_numpy(gt[:, :, 2:3].copy())
 
 
+
+def flow_to_int16(flow):
+    """eval_gui.py:68-74 on the host: flow [..., H, W, 2] -> uint16 [..., H, W, 3] = (cast(max(0, min(u * 64 + 32768, 65535))),
+    the same for v, 1), in fp32 with truncation — the KITTI benchmark's 16-bit flow encoding."""
+    f = np.asarray(flow.detach().cpu().numpy() if isinstance(flow, torch.Tensor) else flow, dtype=np.float32)
+    q = np.maximum(np.float32(0.0), np.minimum(f * np.float32(64.0) + np.float32(32768.0), np.float32(65535.0)))
+    out = np.ones(f.shape[:-1] + (3,), dtype=np.uint16)
+    out[..., :2] = q.astype(np.uint16)
+    return out
+
+
+def write_kitti_flow_png(path, flow_u16):
+    """A KITTI flow map: uint16 [H,W,3] (flow_to_int16) as a 16-bit RGB PNG (eval_gui.py write_rgb_png(bitdepth=16));
+    read_kitti_flow_png reads it back as ((u16 - 2^15) / 64, channel 2)."""
+    a = np.asarray(flow_u16)
+    if a.dtype != np.uint16 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_kitti_flow_png: expected uint16 [H,W,3], got %s %s" % (a.dtype, a.shape))
+    with open(path, 'wb') as f:
+        f.write(encode_png16_rgb(a))
+
 # ----------------------------------------------------------------------------------------------------------- resizing
 def resize_bilinear_tf1(x, out_h, out_w):
     """tf.image.resize_bilinear, TF1 legacy (align_corners=False, no half-pixel centres): src = dst * in / out."""

@@ -54,6 +54,52 @@ def learning_rate_at(params, decay_iters):
 DEFAULT_BUCKET_CUTS = ('conv6', 'conv4')
 
 
+def network_files(params, spec, ckpt_dir, strict=False):
+    """Where every network of `spec` comes from (train.py:23-65, Trainer.restore): ([file or None per network], checkpoint prefix
+    or None).  Without a checkpoint in ckpt_dir: the networks named by params['finetune'] (in network order).  With one: the
+    networks of the Saver's scope (all with train_all, else the last one) from the checkpoint, and — unless train_all — the
+    frozen networks in front from finetune[:n-1], or from the checkpoint when it holds them and finetune names nothing for
+    them.  A network in neither place keeps its initialisation: a warning, or with strict=True (inference: there is no
+    training to give it values) a ValueError."""
+    from . import tf_checkpoint as T
+    from .input import network_scope
+    n = len(spec)
+    finetune = list(params.get('finetune') or [])
+    if len(finetune) > n:
+        raise ValueError("%d finetune entries for the %d networks of spec %r (train.py:31)" % (len(finetune), n, spec))
+    ckpt = T.latest_checkpoint(ckpt_dir) if ckpt_dir is not None else None
+    files = [None] * n
+    if ckpt is not None:
+        have = set(T.checkpoint_entries(ckpt)[1])
+        for i in (range(n) if params.get('train_all') else [n - 1]):       # the Saver's scope (train.py:32-37)
+            files[i] = ckpt
+        external = [] if params.get('train_all') else finetune[:n - 1]
+        if not params.get('train_all'):
+            # network by network: a frozen network without a finetune entry comes from the checkpoint when the checkpoint
+            # holds it (written with every network in it: this trainer before round 4, or a train_all run continued
+            # frozen); one that is in neither place would silently run on its random initialisation — say so
+            for i in range(n - 1):
+                if i < len(external) and external[i] is not None:
+                    continue
+                if any(k.startswith(sc) for k in have for sc in network_scope(i)):
+                    files[i] = ckpt
+                elif not strict:
+                    import warnings
+                    warnings.warn("frozen network %d of spec %r is neither in params['finetune'] nor in %s: it keeps its "
+                                  "random initialisation" % (i, spec, ckpt))
+    else:
+        external = finetune
+    for i, f in enumerate(external):       # restored after the checkpoint, like the reference's second loop (:46-63)
+        if f is not None:
+            files[i] = f
+    if strict:
+        missing = [i for i, f in enumerate(files) if f is None]
+        if missing:
+            raise ValueError("network(s) %s of spec %r are neither in a checkpoint of %s nor in params['finetune']: nothing "
+                             "to restore them from" % (missing, spec, ckpt_dir))
+    return files, ckpt
+
+
 class StepRunner:
     """Runs training steps of an engine: hipGraph replay of forward + loss + backward (cut into parts when gradients are
     exchanged), bucketed RCCL all-reduce and bucketed Adam on a communication stream.  Used by bench.py and Trainer."""
@@ -224,37 +270,9 @@ class Trainer:
         again from finetune[:n-1] (the reference's checkpoint of a stacked run does not contain them).  Returns the checkpoint
         prefix or None."""
         from . import tf_checkpoint as T
-        from .input import restore_networks, network_scope
+        from .input import restore_networks
         engine = self.engine if engine is None else engine
-        n = len(engine.spec)
-        finetune = list(self.params.get('finetune') or [])
-        if len(finetune) > n:
-            raise ValueError("%d finetune entries for the %d networks of spec %r (train.py:31)" % (len(finetune), n, engine.spec))
-        ckpt = T.latest_checkpoint(ckpt_dir) if ckpt_dir is not None else None
-        files = [None] * n
-        if ckpt is not None:
-            have = set(T.checkpoint_entries(ckpt)[1])
-            for i in self._saved_networks():
-                files[i] = ckpt
-            external = [] if self.params.get('train_all') else finetune[:n - 1]
-            if not self.params.get('train_all'):
-                # network by network: a frozen network without a finetune entry comes from the checkpoint when the checkpoint
-                # holds it (written with every network in it: this trainer before round 4, or a train_all run continued
-                # frozen); one that is in neither place would silently run on its random initialisation — say so
-                for i in range(n - 1):
-                    if i < len(external) and external[i] is not None:
-                        continue
-                    if any(k.startswith(sc) for k in have for sc in network_scope(i)):
-                        files[i] = ckpt
-                    else:
-                        import warnings
-                        warnings.warn("frozen network %d of spec %r is neither in params['finetune'] nor in %s: it keeps its "
-                                      "random initialisation" % (i, engine.spec, ckpt))
-        else:
-            external = finetune
-        for i, f in enumerate(external):       # restored after the checkpoint, like the reference's second loop (:46-63)
-            if f is not None:
-                files[i] = f
+        files, ckpt = network_files(self.params, engine.spec, ckpt_dir)
         if any(f is not None for f in files):
             restore_networks(engine, self.params, files)
         if ckpt is not None and engine is self.engine:

@@ -4,6 +4,7 @@
 // streaming kernels: 16-byte accesses, grid-stride, >= 2048 workgroups when the data allows.
 #include "common.h"
 #include "igemm_shared.h"
+#include "resize_tf1.h"
 
 UNFLOW_API const char* unflow_status_string(int status) {
   switch (status) {
@@ -113,7 +114,7 @@ UNFLOW_API int unflow_copy(void* dst, const void* src, size_t bytes, unflow_stre
   return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, as_stream(stream)) == hipSuccess ? UNFLOW_OK : UNFLOW_ERR_LAUNCH;
 }
 
-// TF1 legacy bilinear: src = dst * (in/out); lo = floor(src); hi = min(lo+1, in-1); lerp x then y.
+// TF1 legacy bilinear (csrc/resize_tf1.h: the expression shared with the inference output kernel).
 __global__ void resize_bilinear_tf1_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int H, int W,
                                            int C, int OH, int OW, float sy, float sx, float scale) {
   const long n = (long)B * OH * OW * C;
@@ -121,15 +122,7 @@ __global__ void resize_bilinear_tf1_kernel(const float* __restrict__ in, float* 
     const int c = (int)(e % C);
     const int ox = (int)((e / C) % OW), oy = (int)((e / C / OW) % OH);
     const long b = e / ((long)C * OW * OH);
-    const float fy = (float)oy * sy, fx = (float)ox * sx;
-    const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-    const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
-    const float* base = in + b * H * W * C + c;
-    const float tl = base[((long)y0 * W + x0) * C], tr = base[((long)y0 * W + x1) * C];
-    const float bl = base[((long)y1 * W + x0) * C], br = base[((long)y1 * W + x1) * C];
-    const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;
-    out[e] = (top + (bot - top) * ly) * scale;
+    out[e] = resize_tf1_point(in + b * H * W * C + c, H, W, C, oy, ox, sy, sx) * scale;
   }
 }
 

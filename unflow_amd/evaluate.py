@@ -1,0 +1,114 @@
+"""python -m unflow_amd.evaluate: score a trained experiment on KITTI and write benchmark files — the non-GUI part of the
+reference's src/eval_gui.py, on core/inference.FlowEstimator (batched, graph-replayed, forward only).
+
+    python -m unflow_amd.evaluate --ex NAME [--variant train_2012] [--num 10] [--output_benchmark [--output_png]]
+
+The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives the network spec ([train] and
+[train_kitti]); the checkpoint is the experiment's latest — its logs folder first, then <dirs.checkpoints>/NAME
+(eval_gui.py:101-117).  Benchmark files go to <--out>/NAME/ beside a copy of the config: %06d_10.png (KITTI 16-bit) with
+--output_png, else %06d_10.flo.  Colour-wheel visualisations, backward flow and other datasets are not supported."""
+import argparse
+import os
+import shutil
+import sys
+
+VARIANTS = ('train_2012', 'train_2015', 'test_2012', 'test_2015')
+UNSUPPORTED = {'output_visual': "--output_visual (colour-wheel / error images) is not supported",
+               'output_backward': "--output_backward (backward-flow export) is not supported"}
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m unflow_amd.evaluate', description=__doc__.split('\n')[0])
+    ap.add_argument('--ex', required=True, help='experiment name')
+    ap.add_argument('--dataset', default='kitti', help="only 'kitti' is supported")
+    ap.add_argument('--variant', default='train_2012', choices=VARIANTS)
+    ap.add_argument('--num', type=int, default=10, help='examples to evaluate; -1: all (eval_gui.py --num)')
+    ap.add_argument('--output_benchmark', action='store_true', help='write the benchmark flow files')
+    ap.add_argument('--output_png', action='store_true', help='KITTI 16-bit PNG files (default: .flo)')
+    ap.add_argument('--output_visual', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--output_backward', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
+    ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
+    ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
+    ap.add_argument('--dims', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
+                    help='network input size (eval_gui.py: 384 1280)')
+    return ap
+
+
+def parse_args(argv=None):
+    """Parsed flags; refuses what this tool does not do with a clear message (SystemExit, status 2)."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    if a.dataset != 'kitti':
+        ap.error("--dataset %s is not supported (only kitti; sintel / chairs / mdb inputs are not part of this project)"
+                 % a.dataset)
+    for k, msg in UNSUPPORTED.items():
+        if getattr(a, k):
+            ap.error(msg)
+    if a.batch_size <= 0:
+        ap.error("--batch_size must be positive")
+    return a
+
+
+def experiment_paths(name, config_path):
+    """(experiment config path, checkpoint directory) as eval_gui.py:101-117 finds them: the experiment's own config.ini when
+    its logs folder has one (else the project config), and its logs folder when it holds a checkpoint (else
+    <dirs.checkpoints>/<name>)."""
+    from .core import tf_checkpoint as T
+    from .core.util import config_dict
+    dirs = config_dict(config_path).get('dirs', {})
+    exp_dir = os.path.join(dirs.get('log', ''), 'ex', name)
+    cfg = os.path.join(exp_dir, 'config.ini')
+    if not os.path.isfile(cfg):
+        cfg = config_path
+    if not os.path.isdir(exp_dir) or T.latest_checkpoint(exp_dir) is None:
+        exp_dir = os.path.join(dirs.get('checkpoints', ''), name)
+    if T.latest_checkpoint(exp_dir) is None:
+        raise SystemExit("Error: experiment must contain a checkpoint (looked in %s)" % exp_dir)
+    return cfg, exp_dir
+
+
+class _KITTIData:
+    """What KITTIInput needs of the reference's KITTIData: the data root (dirs.data)."""
+
+    def __init__(self, root):
+        self.current_dir = root
+
+    def get_raw_dirs(self):
+        return []
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from .core.util import config_dict, convert_input_strings
+    from .core.inference import FlowEstimator
+    from .kitti.input import KITTIInput
+    cfg_path, ckpt_dir = experiment_paths(a.ex, a.config)
+    config = config_dict(cfg_path)
+    params = dict(config.get('train', {}))
+    dirs = config_dict(a.config).get('dirs', {})
+    convert_input_strings(params, dirs)
+    params.update(config.get('train_' + a.dataset, {}))
+    est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch_size, net_size=tuple(a.dims))
+    kinput = KITTIInput(_KITTIData(dirs.get('data', '')), batch_size=a.batch_size, normalize=False, dims=tuple(a.dims))
+    batches = lambda: getattr(kinput, 'input_' + a.variant)()            # noqa: E731
+    num = None if a.num < 0 else a.num
+    print("-- evaluating %s (step %s) on kitti %s" % (a.ex, est.global_step, a.variant))
+    if a.variant.startswith('train'):
+        res = est.evaluate(batches(), num=num)
+        for k in res['names']:
+            print("%-24s %.4f" % (k, res[k]))
+        print("examples: %d" % res['num_examples'])
+    if a.output_benchmark:
+        out_dir = os.path.join(a.out, a.ex)
+        if os.path.isdir(out_dir):
+            shutil.rmtree(out_dir)
+        os.makedirs(out_dir)
+        shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
+        paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=num)
+        print("wrote %d files to %s" % (len(paths), out_dir))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
