@@ -594,6 +594,19 @@ int unflow_inference_output(const float* flow, int fh, int fw, float flow_scale,
                             int Wmax, float* out_flow, unsigned short* out_u16, const float* gt_flow, const float* gt_mask,
                             double* partial, unsigned* ticket, double* sums, int* counts, unflow_stream_t stream);
 
+/* flow_fw, flow_bw [B][Hmax][Wmax][2]: the frame-size forward and backward flows of unflow_inference_output -> for every sample b
+ * with desc h > 0 and every frame pixel (y < h, x < w), losses.occlusion (losses.py:125-134) in both directions:
+ *   bw_warped = image_warp(bw, fw), fw_warped = image_warp(fw, bw)  (clamped to the sample's (h, w), rows Wmax apart),
+ *   occ_fw = |fw + bw_warped|^2 > 0.01 (|fw|^2 + |bw|^2) + 0.5, occ_bw likewise with the roles swapped (unwarped magnitudes),
+ * every product and sum rounded on its own as the chained torch ops do.  occ_fw / occ_bw uint8 [B][Hmax][Wmax] get 0 / 1 at
+ * (b, y, x); nothing else is written.  gt_mask [2][B][Hmax][Wmax] (may be NULL), staged as for unflow_inference_output (map 0:
+ * occ, map 1: noc): for a sample with desc nmaps = 2, counts[b] = {TP, FP, FN} of occ_fw over the pixels with mask_occ = 1,
+ * positive where mask_noc = 0 (this project's KITTI occlusion scores).  counts [B][3] int32 (required with gt_mask) is zeroed
+ * on the stream first; exact integer sums. */
+int unflow_inference_occlusion(const float* flow_fw, const float* flow_bw, const int* desc, int B, int Hmax, int Wmax,
+                               const float* gt_mask, unsigned char* occ_fw, unsigned char* occ_bw, int* counts,
+                               unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Throughput of the forward-only estimator (core/inference.FlowEstimator) at the KITTI evaluation shape; one JSON line.
 
-    python tools/inference_bench.py [--iters 20] [--warmup 5] [--rocprof]
+    python tools/inference_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional]
 
 For FlowNetC and CSS at 384 x 1280, B in {1, 4, 8}, math modes bf16x3 and f16: ms per batch of the replayed graph (input
 kernel + forward + output kernel, device events around `iters` replays after `warmup`, staging excluded) and pairs/s.  Beside
 them: the unsupervised training step (StepRunner, FlowNetC, B = 4, bf16x3) at the same shape, and the device memory of the
 estimator against FlowNetEngine(supervised=True) at B = 8.  --rocprof: a separate child run under `rocprofv3 --kernel-trace
 --stats` of the two inference kernels alone (B = 8, uint8 KITTI frames, both GT maps) gives their kernel times and the fraction of 8 TB/s
-their bytes moved reach."""
+their bytes moved reach.  --bidirectional: also FlowEstimator(..., bidirectional=True) for C and CSS at B in {1, 4, 8}, bf16x3
+(both directions, the second output kernel and the occlusion kernel in the graph), and under --rocprof the occlusion kernel's time
+and the fraction of 8 TB/s its compulsory bytes reach (two frame-size flows read, two masks written, two GT maps read)."""
 import argparse
 import csv
 import glob
@@ -26,11 +28,11 @@ KITTI = [(375, 1242), (370, 1226), (376, 1241)]
 HBM = 8e12
 
 
-def _estimator(spec, B, math):
+def _estimator(spec, B, math, bidirectional=False):
     import torch
     os.environ['UNFLOW_CONV_MATH'] = math
     from unflow_amd.core.inference import FlowEstimator
-    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=torch.device('cuda:0'))
+    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=torch.device('cuda:0'), bidirectional=bidirectional)
     est.engine.init_params(seed=1)
     est._params_changed()
     return est
@@ -65,14 +67,17 @@ def time_replays(est, iters, warmup):
     return a.elapsed_time(b) / iters
 
 
-def estimator_case(spec, B, math, iters, warmup):
+def estimator_case(spec, B, math, iters, warmup, bidirectional=False):
     import torch
-    est = _estimator(spec, B, math)
+    est = _estimator(spec, B, math, bidirectional)
     _stage_once(est, B)
     ms = time_replays(est, iters, warmup)
     del est
     torch.cuda.empty_cache()
-    return dict(spec=spec, B=B, math=math, ms_per_batch=round(ms, 4), pairs_per_s=round(B * 1000.0 / ms, 2))
+    out = dict(spec=spec, B=B, math=math, ms_per_batch=round(ms, 4), pairs_per_s=round(B * 1000.0 / ms, 2))
+    if bidirectional:
+        out['bidirectional'] = True
+    return out
 
 
 def memory_case():
@@ -130,15 +135,17 @@ def kernel_bytes(B):
     px_frames = sum(KITTI[i % 3][0] * KITTI[i % 3][1] for i in range(B))
     inp = 2 * px_frames * 3 + 2 * B * H * W * (16 + 3 * 4 * 2)       # frames read; x0 + bf16x3 planes written
     out = B * (H // 4) * (W // 4) * 8 + px_frames * (8 + 6 + 2 * (8 + 4))   # flow2 read; flow + u16 written; 2 GT maps read
-    return inp, out
+    occ = px_frames * (2 * 8 + 2 * 1 + 2 * 4)          # both frame-size flows read; both uint8 masks written; 2 GT masks read
+    return inp, out, occ
 
 
-def kernels_only(iters):
-    """The child of --rocprof: the two inference kernels of a B = 8 batch with both GT maps staged, `iters` times each."""
+def kernels_only(iters, bidirectional=False):
+    """The child of --rocprof: the two inference kernels of a B = 8 batch with both GT maps staged, `iters` times each
+    (bidirectional: and the occlusion kernel on the two frame-size flows)."""
     import torch
     from unflow_amd import _lib
     from unflow_amd.core.inference import pack_desc
-    est = _estimator('C', 8, 'bf16x3')
+    est = _estimator('C', 8, 'bf16x3', bidirectional)
     desc = pack_desc([KITTI[i % 3] for i in range(8)], 8, staged=(H, W), nmaps=2, u8=True)
     est.desc.copy_(torch.from_numpy(desc))
     est.frames.random_(0, 255)
@@ -154,13 +161,17 @@ def kernels_only(iters):
                                              _lib.ptr(est.out_flow), _lib.ptr(est.out_u16), _lib.ptr(est.gt_flow),
                                              _lib.ptr(est.gt_mask), _lib.ptr(est.partial), _lib.ptr(est.ticket),
                                              _lib.ptr(est.sums), _lib.ptr(est.counts), e.stream()), "output")
+        if bidirectional:
+            _lib.check(L.unflow_inference_occlusion(_lib.ptr(est.out_flow), _lib.ptr(est.out_flow_bw), _lib.ptr(est.desc), 8, H, W,
+                                                    _lib.ptr(est.gt_mask), _lib.ptr(est.occ[0]), _lib.ptr(est.occ[1]),
+                                                    _lib.ptr(est.occ_counts), e.stream()), "occlusion")
     torch.cuda.synchronize()
 
 
-def rocprof_case(iters):
+def rocprof_case(iters, bidirectional=False):
     d = tempfile.mkdtemp(prefix='infprof_')
     cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '-o', 'run', '--', sys.executable, os.path.abspath(__file__),
-           '--kernels-only', '--iters', str(iters)]
+           '--kernels-only', '--iters', str(iters)] + (['--bidirectional'] if bidirectional else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     if r.returncode != 0:
         return dict(error="rocprofv3 exit %d" % r.returncode, tail=r.stdout.decode(errors='replace')[-400:])
@@ -169,12 +180,12 @@ def rocprof_case(iters):
         return dict(error="no kernel_stats.csv")
     avg = {}
     for row in csv.DictReader(open(stats[0])):
-        for k in ('inference_input_kernel', 'inference_output_kernel'):
+        for k in ('inference_input_kernel', 'inference_output_kernel', 'inference_occlusion_kernel'):
             if k in row['Name']:
                 avg[k] = float(row['AverageNs'])
-    bi, bo = kernel_bytes(8)
+    bi, bo, bocc = kernel_bytes(8)
     out = {}
-    for k, b in (('inference_input_kernel', bi), ('inference_output_kernel', bo)):
+    for k, b in (('inference_input_kernel', bi), ('inference_output_kernel', bo), ('inference_occlusion_kernel', bocc)):
         if k in avg:
             out[k] = dict(us=round(avg[k] / 1e3, 2), MB=round(b / 1e6, 2), TBps=round(b / avg[k] / 1e3, 3),
                           frac_of_8TBps=round(b / (avg[k] * 1e-9) / HBM, 3))
@@ -186,25 +197,30 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--rocprof', action='store_true')
+    ap.add_argument('--bidirectional', action='store_true', help='also the bidirectional estimator (bf16x3) and its occlusion kernel')
     ap.add_argument('--rocprof-only', action='store_true', help='only the kernel times of the rocprofv3 child run')
     ap.add_argument('--kernels-only', action='store_true', help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.kernels_only:
-        kernels_only(a.iters)
+        kernels_only(a.iters, a.bidirectional)
         return
     if a.rocprof_only:
-        print(json.dumps(dict(kernels_B8=rocprof_case(a.iters))))
+        print(json.dumps(dict(kernels_B8=rocprof_case(a.iters, a.bidirectional))))
         return
     res = dict(metric='inference_pairs_per_s', shape=[H, W], frames='KITTI uint8 (375x1242, 370x1226, 376x1241)', cases=[])
     for math in ('bf16x3', 'f16'):
         for spec in ('C', 'CSS'):
             for B in (1, 4, 8):
                 res['cases'].append(estimator_case(spec, B, math, a.iters, a.warmup))
+    if a.bidirectional:
+        for spec in ('C', 'CSS'):
+            for B in (1, 4, 8):
+                res['cases'].append(estimator_case(spec, B, 'bf16x3', a.iters, a.warmup, bidirectional=True))
     os.environ['UNFLOW_CONV_MATH'] = 'bf16x3'
     res['train_step_unsupervised'] = step_case(a.iters, a.warmup)
     res['memory_B8'] = memory_case()
     if a.rocprof:
-        res['kernels_B8'] = rocprof_case(a.iters)
+        res['kernels_B8'] = rocprof_case(a.iters, a.bidirectional)
     print(json.dumps(res))
 
 

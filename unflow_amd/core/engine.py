@@ -596,19 +596,27 @@ class FlowNetEngine:
     target (unflow_supervised_flow_loss per counted network)."""
 
     def __init__(self, batch, height, width, params=None, device=None, seed=0, layout_only=False, supervised=False,
-                 inference=False):
+                 inference=False, bidirectional=False):
         """layout_only: build the layer table and the flat parameter / gradient buffers (on `device`, which may then be the
         CPU) but no activations — for tools and the data-parallel tests that only need the flat layout and its buckets.
         inference: the forward-only engine (core/inference.py): the one-direction plan of supervised=True, and only what the
         forward pass reads — the parameters P (no G / M / V), no activation gradients, no loss buffers, and of the weight
         planes only the layout the forward kernels take (transposed for conv layers, direct for conv_transpose layers).  The
-        flat parameter layout is the training engine's, so load_tf_params / export_tf_params / checkpoints work unchanged."""
+        flat parameter layout is the training engine's, so load_tf_params / export_tf_params / checkpoints work unchanged.
+        bidirectional (with inference only): the forward-only engine on the training engine's plan — every buffer and op on
+        N = 2B rows, the directed batch into the correlation — so final_flows() / flows() give (fw, bw) row slices."""
         assert height % 64 == 0 and width % 64 == 0, "FlowNet needs H, W divisible by 64"
+        if bidirectional and supervised:
+            raise ValueError("FlowNetEngine: bidirectional is for the inference engine; the supervised engine is one-direction")
+        if bidirectional and not inference:
+            raise ValueError("FlowNetEngine: bidirectional needs inference=True (the training engine is bidirectional already)")
         if supervised and inference:
             raise ValueError("FlowNetEngine: supervised and inference are exclusive")
         self.supervised = bool(supervised)
         self.inference = bool(inference)
-        self.one_dir = self.supervised or self.inference     # FlowNetC tower on 2B rows, everything after it on B rows
+        self.bidirectional = bool(bidirectional)
+        # FlowNetC tower on 2B rows, everything after it on B rows
+        self.one_dir = self.supervised or (self.inference and not self.bidirectional)
         self.params = dict(DEFAULT_PARAMS) if params is None else dict(params)
         if self.params.get('mask_occlusion', '') not in ('', 'fb', 'disocc'):   # unsupervised.py:125-126
             raise ValueError("mask_occlusion must be one of 'fb', 'disocc', ''")
@@ -878,9 +886,9 @@ class FlowNetEngine:
         self.act.update(x0=self.x0, im01=self.im01)
         self.grad = last.grad
         if self.inference:
-            # the output of final_flows(); no targets, no loss pyramid, no masks
+            # the output of final_flows() (both directions: N rows); no targets, no loss pyramid, no masks
             self.lv = []
-            self.final_flow = z(self.B, H, W, 2)
+            self.final_flow = z(N if self.bidirectional else self.B, H, W, 2)
             self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
             return
         if self.supervised:
@@ -915,7 +923,7 @@ class FlowNetEngine:
         of the engine (so a captured hipGraph never holds a stale mask pointer): without augmentation it holds B copies of
         the static mask, with augmentation the per-sample warped masks."""
         from .. import ops
-        if self.one_dir:
+        if self.one_dir or self.inference:
             return                # no border mask in the supervised loss (supervised.py:12-65), no loss at all in inference
         H, W, B = self.H, self.W, self.B
         sz = int(math.ceil(min(H, W) * 0.1))
@@ -1508,7 +1516,8 @@ class FlowNetEngine:
 
     def final_flows(self):
         """final_flow_fw / _bw: resize_bilinear(flow2, im_shape) * 5 * 4 (unsupervised.py:103-104), or flow0 * 20 with
-        full_res (unsupervised.py:95-97).  One-direction (supervised, inference) engine: (final_flow_fw, None)."""
+        full_res (unsupervised.py:95-97).  One-direction (supervised, inference) engine: (final_flow_fw, None); bidirectional
+        inference engine: both, as the training engine."""
         if self.full_res:
             f0 = self.act['flow0']
             check(_lib.lib().unflow_scale(ptr(f0), cf(FLOW_SCALE * 4), ptr(self.final_flow), cl(f0.numel()), self.stream()), "scale")

@@ -11,7 +11,14 @@ table of per-sample frame geometry and one captured hipGraph on one stream:
 Every batch — any mix of frame sizes, a short last one — replays the same graph: the host rewrites the geometry table
 (csrc/inference.hip).  Host staging is double-buffered in pinned memory; before the host overwrites a slot it waits for the
 event recorded after the last replay that read it (and the copies that brought its outputs back).
+
+bidirectional=True: the engine runs both directions (FlowNetEngine(..., inference=True, bidirectional=True)) and the graph
+continues with the output kernel once more on the backward rows (no ground truth) and
+
+    unflow_inference_occlusion   both frame-size flows -> losses.occlusion's masks of both directions, integer TP / FP / FN
+                                 of the forward mask against KITTI's occluded pixels
 """
+import collections
 import itertools
 import os
 
@@ -24,6 +31,20 @@ from .engine import FLOW_SCALE, FlowNetEngine
 
 ENGINE_KEYS = ('flownet', 'train_all', 'full_res', 'pyramid_loss', 'border_mask', 'mask_occlusion')   # = Trainer.ENGINE_KEYS
 MAP_NAMES = {2: ('occluded', 'non-occluded'), 1: ('all',)}
+OCC_NAMES = ('occ/precision', 'occ/recall', 'occ/F1')
+
+# What estimate_bidirectional returns per pair: [h, w, 2] float32 flows, [h, w] bool occlusion masks (losses.occlusion)
+BidirectionalFlow = collections.namedtuple('BidirectionalFlow', ('flow_fw', 'flow_bw', 'occ_fw', 'occ_bw'))
+
+
+def occlusion_scores(counts):
+    """This project's KITTI occlusion scores (the reference prints none): the forward occlusion mask against KITTI's occluded
+    pixels — evaluated where mask_occ = 1, positive where mask_noc = 0 as well.  counts: per-example [tp, fp, fn]; pooled over
+    all examples from the summed counts: precision tp / (tp + fp), recall tp / (tp + fn), F1 2 tp / (2 tp + fp + fn), in %,
+    0 where a denominator is 0."""
+    tp, fp, fn = (int(v) for v in np.asarray(counts, dtype=np.int64).reshape(-1, 3).sum(0))
+    pct = lambda a, b: 100.0 * a / b if b else 0.0          # noqa: E731
+    return dict(zip(OCC_NAMES, (pct(tp, tp + fp), pct(tp, tp + fn), pct(2 * tp, 2 * tp + fp + fn))))
 
 
 # ------------------------------------------------------------------------------------------------- host batch packing
@@ -83,6 +104,12 @@ class _Slot:
         self.u16 = pin(B, Hm, Wm, 3, dtype=torch.int16)
         self.sums = pin(B, 2, 2, dtype=torch.float64)
         self.counts = pin(B, 2, dtype=torch.int32)
+        self.flow_bw = self.u16_bw = self.occ = self.occ_counts = None
+        if est.bidirectional:
+            self.flow_bw = pin(B, Hm, Wm, 2)
+            self.u16_bw = pin(B, Hm, Wm, 3, dtype=torch.int16)
+            self.occ = pin(2, B, Hm, Wm, dtype=torch.uint8)          # occ_fw, occ_bw
+            self.occ_counts = pin(B, 3, dtype=torch.int32)
         self.event = None
         self.pending = None
 
@@ -100,18 +127,21 @@ class _Slot:
 
 class FlowEstimator:
     """Frame-size optical flow of a trained FlowNet spec (params['flownet'], 'full_res', ...), `batch` pairs per replay at the
-    network size net_size = (H, W) (divisible by 64), frames of any size up to max_frame (default: net_size)."""
+    network size net_size = (H, W) (divisible by 64), frames of any size up to max_frame (default: net_size).
+    bidirectional: also the backward flow and the forward-backward occlusion masks (estimate_bidirectional, the occlusion
+    scores of evaluate, export's backward / occlusion files)."""
 
-    def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True):
+    def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False):
         self.params = dict(params)
         self.B = int(batch)
         self.H, self.W = (int(v) for v in net_size)
         self.Hmax, self.Wmax = (int(v) for v in (max_frame or net_size))
         self.dev = torch.device('cuda:0') if device is None else torch.device(device)
         self.use_graph = bool(use_graph)
+        self.bidirectional = bool(bidirectional)
         eng_params = {k: v for k, v in self.params.items() if k.endswith('_weight') or k in ENGINE_KEYS}
         self.engine = FlowNetEngine(self.B, self.H, self.W, params=eng_params or None, device=self.dev, seed=None,
-                                    inference=True)
+                                    inference=True, bidirectional=self.bidirectional)
         e = self.engine
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         L = _lib.lib()
@@ -127,8 +157,14 @@ class FlowEstimator:
             self.ticket = z(B, dtype=torch.int32)
             self.sums = z(B, 2, 2, dtype=torch.float64)
             self.counts = z(B, 2, dtype=torch.int32)
+            self.out_flow_bw = self.out_u16_bw = self.occ = self.occ_counts = None
+            if self.bidirectional:
+                self.out_flow_bw = z(B, Hm, Wm, 2)
+                self.out_u16_bw = z(B, Hm, Wm, 3, dtype=torch.int16)
+                self.occ = z(2, B, Hm, Wm, dtype=torch.uint8)        # occ_fw, occ_bw
+                self.occ_counts = z(B, 3, dtype=torch.int32)
         last = e.stages[-1]
-        self.flow_src = last.act['flow0'] if e.full_res else last.act['flow2']
+        self.flow_src = last.act['flow0'] if e.full_res else last.act['flow2']     # bidirectional: rows [0, B) fw, [B, 2B) bw
         self.in_planes = e.X0.pl if (e.X0.pl is not None and e.stages[0].is_c) else None
         self.slots = None
         self.graph = None
@@ -160,7 +196,8 @@ class FlowEstimator:
 
     # ------------------------------------------------------------------------------------------ device work
     def _launch(self):
-        """Input kernel, forward pass, output kernel on the current stream (what the graph holds)."""
+        """Input kernel, forward pass, output kernel on the current stream (what the graph holds); bidirectional: then the
+        output kernel on the backward rows and the occlusion kernel."""
         e = self.engine
         L = _lib.lib()
         st = e.stream()
@@ -172,6 +209,15 @@ class FlowEstimator:
                                         self.B, self.Hmax, self.Wmax, ptr(self.out_flow), ptr(self.out_u16), ptr(self.gt_flow),
                                         ptr(self.gt_mask), ptr(self.partial), ptr(self.ticket), ptr(self.sums),
                                         ptr(self.counts), st), "inference_output")
+        if not self.bidirectional:
+            return
+        fb = f[self.B:]
+        check(L.unflow_inference_output(ptr(fb), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(self.desc),
+                                        self.B, self.Hmax, self.Wmax, ptr(self.out_flow_bw), ptr(self.out_u16_bw), None, None,
+                                        None, None, None, None, st), "inference_output (backward)")
+        check(L.unflow_inference_occlusion(ptr(self.out_flow), ptr(self.out_flow_bw), ptr(self.desc), self.B, self.Hmax,
+                                           self.Wmax, ptr(self.gt_mask), ptr(self.occ[0]), ptr(self.occ[1]),
+                                           ptr(self.occ_counts), st), "inference_occlusion")
 
     def _run(self):
         e = self.engine
@@ -257,6 +303,14 @@ class FlowEstimator:
             if nmaps:
                 slot.sums.copy_(self.sums, non_blocking=True)
                 slot.counts.copy_(self.counts, non_blocking=True)
+            if 'flow_bw' in want:
+                slot.flow_bw.copy_(self.out_flow_bw, non_blocking=True)
+            if 'u16_bw' in want:
+                slot.u16_bw.copy_(self.out_u16_bw, non_blocking=True)
+            if 'occ' in want:
+                slot.occ.copy_(self.occ, non_blocking=True)
+            if 'occ_counts' in want and nmaps == 2:
+                slot.occ_counts.copy_(self.occ_counts, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -283,24 +337,43 @@ class FlowEstimator:
         return slot, shapes, nmaps, exs
 
     # ------------------------------------------------------------------------------------------ public API
-    def estimate(self, frames1, frames2):
-        """Flow of every pair (frames1[i] -> frames2[i]): frames [h_i, w_i, 3] uint8 or float32 in [0, 255], any size up to
-        max_frame (both frames of a pair the same size).  Returns a list of [h_i, w_i, 2] float32 arrays."""
+    @staticmethod
+    def _pairs(frames1, frames2, what):
         if len(frames1) != len(frames2):
-            raise ValueError("estimate: %d first frames, %d second frames" % (len(frames1), len(frames2)))
+            raise ValueError("%s: %d first frames, %d second frames" % (what, len(frames1), len(frames2)))
         exs = []
         for a, b in zip(frames1, frames2):
             a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
             b = np.asarray(b.cpu().numpy() if isinstance(b, torch.Tensor) else b)
             if a.shape != b.shape or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError("estimate: a pair must be two [h, w, 3] frames of one size, got %s and %s" % (a.shape, b.shape))
+                raise ValueError("%s: a pair must be two [h, w, 3] frames of one size, got %s and %s" % (what, a.shape, b.shape))
             if a.dtype != np.uint8:
                 a, b = a.astype(np.float32, copy=False), b.astype(np.float32, copy=False)
             exs.append((a, b, a.shape[:2]))
+        return exs
+
+    def estimate(self, frames1, frames2):
+        """Flow of every pair (frames1[i] -> frames2[i]): frames [h_i, w_i, 3] uint8 or float32 in [0, 255], any size up to
+        max_frame (both frames of a pair the same size).  Returns a list of [h_i, w_i, 2] float32 arrays."""
+        exs = self._pairs(frames1, frames2, 'estimate')
         out = []
         for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B)):
             fl = slot.flow.numpy()
             out += [fl[i, :h, :w].copy() for i, (h, w) in enumerate(shapes)]
+        return out
+
+    def estimate_bidirectional(self, frames1, frames2):
+        """estimate's pairs in both directions: one BidirectionalFlow(flow_fw, flow_bw, occ_fw, occ_bw) per pair — the flows
+        [h_i, w_i, 2] float32 (flow_fw = estimate's flow), the masks [h_i, w_i] bool: losses.occlusion(flow_fw, flow_bw)."""
+        if not self.bidirectional:
+            raise RuntimeError("estimate_bidirectional: a one-direction estimator; build it with FlowEstimator(..., "
+                               "bidirectional=True)")
+        exs = self._pairs(frames1, frames2, 'estimate_bidirectional')
+        out = []
+        for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B), want=('flow', 'flow_bw', 'occ')):
+            fl, fb, oc = slot.flow.numpy(), slot.flow_bw.numpy(), slot.occ.numpy()
+            out += [BidirectionalFlow(fl[i, :h, :w].copy(), fb[i, :h, :w].copy(), oc[0, i, :h, :w].astype(bool),
+                                      oc[1, i, :h, :w].astype(bool)) for i, (h, w) in enumerate(shapes)]
         return out
 
     def evaluate(self, batch_iter, num=None):
@@ -309,12 +382,15 @@ class FlowEstimator:
         KITTIInput layout (cropped / padded to its dims, normalize=False); the flow is scored at each frame's own size
         against the ground truth cropped back the same way (Trainer.eval's chain).  Returns the per-example averages of
         AEE/<map> and outliers/<map> (%) — map = occluded, non-occluded (or all) — num_examples and per_example (rows in
-        `names` order).  num: at most that many examples."""
-        names, rows = None, []
+        `names` order).  num: at most that many examples.
+        A bidirectional estimator on two-map input adds occlusion_scores' occ/precision, occ/recall and occ/F1 (%, pooled
+        over all examples) and occ_counts (per example [tp, fp, fn])."""
+        names, rows, occ_rows = None, [], []
         it = example_stream(batch_iter)
         if num is not None:
             it = (ex for i, ex in zip(range(int(num)), it))
-        for slot, shapes, nmaps, _ in self._pipeline_staged(it, (), lambda exs: (len(exs[0]) - 3) // 2):
+        want = ('occ_counts',) if self.bidirectional else ()
+        for slot, shapes, nmaps, _ in self._pipeline_staged(it, want, lambda exs: (len(exs[0]) - 3) // 2):
             if nmaps == 0:
                 raise ValueError("evaluate: the batches carry no ground truth (a test split); use export()")
             if names is None:
@@ -326,11 +402,16 @@ class FlowEstimator:
                     err, msk = float(sums[i, m, 0]), float(sums[i, m, 1])
                     row += [err / msk, 100.0 * float(counts[i, m]) / msk]
                 rows.append(row)
+            if self.bidirectional and nmaps == 2:
+                occ_rows += [[int(v) for v in slot.occ_counts.numpy()[i]] for i in range(len(shapes))]
         if not rows:
             raise ValueError("evaluate: the input yielded no examples")
         avg = np.mean(np.asarray(rows, dtype=np.float64), axis=0)
         out = {k: float(v) for k, v in zip(names, avg)}
         out.update(num_examples=len(rows), per_example=rows, names=names)
+        if occ_rows and len(occ_rows) == len(rows):
+            out.update(occlusion_scores(occ_rows))
+            out['occ_counts'] = occ_rows
         return out
 
     def _staged_examples(self, it):
@@ -354,25 +435,41 @@ class FlowEstimator:
         batches = chunks(itertools.chain([first], gen), self.B)
         yield from self._pipeline(batches, staged=tuple(self._dims), nmaps_of=nmaps_of, want=want)
 
-    def export(self, batch_iter, out_dir, fmt='png', num=None):
-        """The benchmark files of eval_gui.py --output_benchmark (:247-260): for the k-th example in iteration order,
+    def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False):
+        """The benchmark files of eval_gui.py --output_benchmark (:247-263): for the k-th example in iteration order,
         out_dir/%06d_10.png (KITTI 16-bit RGB, --output_png) or out_dir/%06d_10.flo.  Input: what
-        KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths."""
-        from .input import write_flo, write_kitti_flow_png
+        KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths (per example: _10, _01, _10_occ).
+        backward: also the backward flow, %06d_01.png / .flo (the file eval_gui.py --output_backward means); occlusion: the
+        forward occlusion mask, %06d_10_occ.png (8-bit grey, 255 = occluded).  Both need a bidirectional estimator."""
+        from .input import write_flo, write_kitti_flow_png, write_png_gray8
         if fmt not in ('png', 'flo'):
             raise ValueError("export: fmt must be 'png' or 'flo'")
+        if (backward or occlusion) and not self.bidirectional:
+            raise ValueError("export: backward / occlusion files need FlowEstimator(..., bidirectional=True)")
         os.makedirs(out_dir, exist_ok=True)
         it = example_stream(batch_iter)
         if num is not None:
             it = (ex for i, ex in zip(range(int(num)), it))
         paths = []
         want = ('u16',) if fmt == 'png' else ('flow',)
+        if backward:
+            want += ('u16_bw',) if fmt == 'png' else ('flow_bw',)
+        if occlusion:
+            want += ('occ',)
+        n = 0
         for slot, shapes, _, _ in self._pipeline_staged(it, want, lambda exs: 0):
             for i, (h, w) in enumerate(shapes):
-                path = os.path.join(out_dir, '%06d_10.%s' % (len(paths), fmt))
-                if fmt == 'png':
-                    write_kitti_flow_png(path, slot.u16.numpy()[i, :h, :w].view(np.uint16))
-                else:
-                    write_flo(path, slot.flow.numpy()[i, :h, :w])
-                paths.append(path)
+                flows = [('10', slot.u16, slot.flow)] + ([('01', slot.u16_bw, slot.flow_bw)] if backward else [])
+                for tag, u16, flow in flows:
+                    path = os.path.join(out_dir, '%06d_%s.%s' % (n, tag, fmt))
+                    if fmt == 'png':
+                        write_kitti_flow_png(path, u16.numpy()[i, :h, :w].view(np.uint16))
+                    else:
+                        write_flo(path, flow.numpy()[i, :h, :w])
+                    paths.append(path)
+                if occlusion:
+                    path = os.path.join(out_dir, '%06d_10_occ.png' % n)
+                    write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
+                    paths.append(path)
+                n += 1
         return paths

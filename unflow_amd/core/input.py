@@ -242,6 +242,28 @@ def write_kitti_flow_png(path, flow_u16):
     with open(path, 'wb') as f:
         f.write(encode_png16_rgb(a))
 
+
+def encode_png8_gray(arr):
+    """uint8 [H,W] -> 8-bit greyscale PNG bytes (filter 0, one IDAT)."""
+    a = np.ascontiguousarray(arr, dtype=np.uint8)
+    h, w = a.shape
+    raw = b''.join(b'\x00' + a[y].tobytes() for y in range(h))
+
+    def chunk(t, b):
+        return struct.pack('>I', len(b)) + t + b + struct.pack('>I', zlib.crc32(t + b) & 0xffffffff)
+    return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 0, 0, 0, 0)) + \
+        chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b'')
+
+
+def write_png_gray8(path, img):
+    """An 8-bit greyscale PNG of uint8 [H,W] (the occlusion maps of FlowEstimator.export); read_png_image reads it back
+    replicated to RGB."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise ValueError("write_png_gray8: expected uint8 [H,W], got %s %s" % (a.dtype, a.shape))
+    with open(path, 'wb') as f:
+        f.write(encode_png8_gray(a))
+
 # ----------------------------------------------------------------------------------------------------------- resizing
 def resize_bilinear_tf1(x, out_h, out_w):
     """tf.image.resize_bilinear, TF1 legacy (align_corners=False, no half-pixel centres): src = dst * in / out."""

@@ -14,13 +14,19 @@
 //   launches.  Optional: the KITTI 16-bit encoding (eval_gui.py flow_to_int16) and the EPE / outlier sums against up to two
 //   ground-truth maps, reduced in a fixed order (per-block fp64 partials; the last block of a sample, found by an integer
 //   ticket, sums them with a fixed thread-to-partial assignment and a fixed tree; no float atomics) — bit-identical from run to run and between graph replay and eager runs.
+// unflow_inference_occlusion: the frame-size forward and backward flows (two unflow_inference_output launches) -> both
+//   forward-backward occlusion masks of losses.occlusion (losses.py:125-134), image_warp's taps from csrc/image_warp.h, and
+//   integer TP / FP / FN of the forward mask against KITTI's occluded pixels (per-block integer sums, one integer atomicAdd per
+//   block and count: exact, hence the same from run to run).
 #include "common.h"
 #include "igemm_shared.h"
+#include "image_warp.h"
 #include "resize_tf1.h"
 
 namespace {
 
 constexpr int OUT_THREADS = 256;
+constexpr int OCC_THREADS = 256;
 constexpr int MAX_MAPS = 2;
 
 struct FrameDesc {
@@ -212,6 +218,75 @@ __global__ __launch_bounds__(OUT_THREADS) void inference_output_kernel(
   if (threadIdx.x == 0) ticket[b] = 0u;                // ready for the next launch (graph replays included)
 }
 
+// image_warp(im, flow) at frame pixel (x, y) of a sample whose frame is h x w, rows Wmax apart: the partner field `im` at
+// (x, y) + f, clamped to the frame — image_warp_fwd_kernel's taps and tap order (csrc/ops_warp.hip, flow_scale 1)
+__device__ __forceinline__ float2 warp_at(const float2* __restrict__ im, int x, int y, float2 f, int h, int w, int Wmax) {
+#pragma clang fp contract(off)
+  const IwTaps t = iw_sample(x, y, f.x, f.y, h, w, Wmax);
+  const float2 a = im[t.ia], b = im[t.ib], c = im[t.ic], d = im[t.id];
+  return make_float2(((t.wa * a.x + t.wb * b.x) + t.wc * c.x) + t.wd * d.x, ((t.wa * a.y + t.wb * b.y) + t.wc * c.y) + t.wd * d.y);
+}
+
+__global__ __launch_bounds__(OCC_THREADS) void inference_occlusion_kernel(
+    const float* __restrict__ flow_fw, const float* __restrict__ flow_bw, const int* __restrict__ desc, int B, int Hmax, int Wmax,
+    const float* __restrict__ gt_mask, unsigned char* __restrict__ occ_fw, unsigned char* __restrict__ occ_bw,
+    int* __restrict__ counts) {
+  // losses.occlusion is a chain of separate torch kernels: every product and sum below is rounded on its own (no FMA)
+#pragma clang fp contract(off)
+  __shared__ int red[3][OCC_THREADS / 64];
+  const int b = blockIdx.y;
+  const FrameDesc d = load_desc(desc, b);
+  const int h = min(max(d.h, 0), Hmax), w = min(max(d.w, 0), Wmax);    // never past the (Hmax, Wmax) rows
+  const bool score = gt_mask != nullptr && d.nmaps >= 2 && h > 0 && w > 0;
+  const long plane = (long)Hmax * Wmax;
+  const float2* fw = reinterpret_cast<const float2*>(flow_fw) + b * plane;
+  const float2* bw = reinterpret_cast<const float2*>(flow_bw) + b * plane;
+  int tp = 0, fp = 0, fn = 0;
+  const int npx = h * w;                               // < 2^31 (the host checks Hmax * Wmax)
+  for (int p = blockIdx.x * OCC_THREADS + threadIdx.x; p < npx; p += gridDim.x * OCC_THREADS) {
+    const int y = p / w, x = p - y * w;
+    const long q = (long)y * Wmax + x;
+    const float2 f = fw[q], g = bw[q];
+    const float2 gw = warp_at(bw, x, y, f, h, w, Wmax);     // image_warp(flow_bw, flow_fw)
+    const float2 fwp = warp_at(fw, x, y, g, h, w, Wmax);    // image_warp(flow_fw, flow_bw)
+    const float mag = (f.x * f.x + f.y * f.y) + (g.x * g.x + g.y * g.y);     // |fw|^2 + |bw|^2, unwarped
+    const float thr = 0.01f * mag + 0.5f;
+    const float dfx = f.x + gw.x, dfy = f.y + gw.y, dbx = g.x + fwp.x, dby = g.y + fwp.y;
+    const bool o_fw = dfx * dfx + dfy * dfy > thr, o_bw = dbx * dbx + dby * dby > thr;
+    occ_fw[b * plane + q] = o_fw ? 1 : 0;
+    occ_bw[b * plane + q] = o_bw ? 1 : 0;
+    if (score) {
+      // KITTI's maps at the frame's origin in its staging row (as the output kernel reads them): map 0 = occ, map 1 = noc
+      const int r = y + d.y0, c = x + d.x0;
+      if (r >= 0 && r < Hmax && c >= 0 && c < Wmax) {
+        const long s = (long)r * Wmax + c;
+        const float m_occ = gt_mask[(long)b * plane + s], m_noc = gt_mask[((long)B + b) * plane + s];
+        if (m_occ == 1.f) {                            // evaluated pixel; occluded in the ground truth: not in noc
+          const bool gt_occ = m_noc == 0.f;
+          tp += (o_fw && gt_occ) ? 1 : 0;
+          fp += (o_fw && !gt_occ) ? 1 : 0;
+          fn += (!o_fw && gt_occ) ? 1 : 0;
+        }
+      }
+    }
+  }
+  if (!score) return;                                  // uniform per sample: every block of it takes this branch
+  const int v[3] = {tp, fp, fn};
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    int s = v[k];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if (lane == 0) red[k][wid] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    int s = 0;
+    for (int i = 0; i < OCC_THREADS / 64; i++) s += red[threadIdx.x][i];
+    if (s) atomicAdd(counts + (long)b * 3 + threadIdx.x, s);
+  }
+}
+
 }  // namespace
 
 UNFLOW_API int unflow_inference_input(const void* frames, const int* desc, int B, int Hmax, int Wmax, int H, int W, float* net_in4,
@@ -251,5 +326,18 @@ UNFLOW_API int unflow_inference_output(const float* flow, int fh, int fw, float 
   inference_output_kernel<<<grid, OUT_THREADS, 0, as_stream(stream)>>>(flow, fh, fw, flow_scale, H, W, desc, B, Hmax, Wmax,
                                                                        out_flow, out_u16, gt_flow, gt_mask, partial, ticket, sums,
                                                                        counts);
+  return launch_status();
+}
+
+UNFLOW_API int unflow_inference_occlusion(const float* flow_fw, const float* flow_bw, const int* desc, int B, int Hmax, int Wmax,
+                                          const float* gt_mask, unsigned char* occ_fw, unsigned char* occ_bw, int* counts,
+                                          unflow_stream_t stream) {
+  if (!flow_fw || !flow_bw || !desc || !occ_fw || !occ_bw) return UNFLOW_ERR_NULL;
+  if (gt_mask && !counts) return UNFLOW_ERR_NULL;
+  if (B <= 0 || Hmax <= 0 || Wmax <= 0 || (long)Hmax * Wmax > 0x7fffffffL) return UNFLOW_ERR_SHAPE;
+  const hipStream_t st = as_stream(stream);
+  if (counts && hipMemsetAsync(counts, 0, sizeof(int) * 3 * (size_t)B, st) != hipSuccess) return UNFLOW_ERR_LAUNCH;
+  const dim3 grid(unflow_inference_output_blocks(Hmax, Wmax), B);
+  inference_occlusion_kernel<<<grid, OCC_THREADS, 0, st>>>(flow_fw, flow_bw, desc, B, Hmax, Wmax, gt_mask, occ_fw, occ_bw, counts);
   return launch_status();
 }

@@ -6,6 +6,7 @@
 //   forward_warp   <- ops/forward_warp_op.cu.cc:16-125    (gaussian splat, +-4 px)
 //   downsample     <- ops/downsample_op.cu.cc:15-49       (box mean)
 #include "common.h"
+#include "image_warp.h"
 
 // ------------------------------------------------------------------ backward_warp
 struct BwTaps {
@@ -192,30 +193,7 @@ UNFLOW_API int unflow_backward_warp_indices(const float* flows, int* xy0, int B,
 }
 
 // ------------------------------------------------------------------ image_warp
-struct IwTaps {
-  long ia, ib, ic, id;  // pixel indices within the batch (sample-relative, in pixels)
-  float xw, yw, wa, wb, wc, wd;
-};
-
-__device__ __forceinline__ IwTaps iw_sample(int px, int py, float u, float v, int H, int W) {
-  IwTaps t;
-  const float fu = floorf(u), fv = floorf(v);
-  t.xw = u - fu;
-  t.yw = v - fv;
-  t.wa = (1.f - t.xw) * (1.f - t.yw);
-  t.wb = (1.f - t.xw) * t.yw;
-  t.wc = t.xw * (1.f - t.yw);
-  t.wd = t.xw * t.yw;
-  const int xi = px + (int)fu, yi = py + (int)fv;
-  const int x0 = min(max(xi, 0), W - 1), x1 = min(max(xi + 1, 0), W - 1);
-  const int y0 = min(max(yi, 0), H - 1), y1 = min(max(yi + 1, 0), H - 1);
-  t.ia = (long)y0 * W + x0;
-  t.ib = (long)y1 * W + x0;
-  t.ic = (long)y0 * W + x1;
-  t.id = (long)y1 * W + x1;
-  return t;
-}
-
+// (the taps, iw_sample: csrc/image_warp.h)
 template <int CT>
 __global__ void image_warp_fwd_kernel(const float* __restrict__ im, int ld_im, const float* __restrict__ flow,
                                       float fscale, float* __restrict__ out, int* __restrict__ idx4, int shift,

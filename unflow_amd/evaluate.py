@@ -1,20 +1,24 @@
 """python -m unflow_amd.evaluate: score a trained experiment on KITTI and write benchmark files — the non-GUI part of the
 reference's src/eval_gui.py, on core/inference.FlowEstimator (batched, graph-replayed, forward only).
 
-    python -m unflow_amd.evaluate --ex NAME [--variant train_2012] [--num 10] [--output_benchmark [--output_png]]
+    python -m unflow_amd.evaluate --ex NAME [--variant train_2012] [--num 10] [--occlusion]
+                                  [--output_benchmark [--output_png] [--output_backward]]
 
 The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives the network spec ([train] and
 [train_kitti]); the checkpoint is the experiment's latest — its logs folder first, then <dirs.checkpoints>/NAME
 (eval_gui.py:101-117).  Benchmark files go to <--out>/NAME/ beside a copy of the config: %06d_10.png (KITTI 16-bit) with
---output_png, else %06d_10.flo.  Colour-wheel visualisations, backward flow and other datasets are not supported."""
+--output_png, else %06d_10.flo; with --output_backward also the backward flow, %06d_01.png / .flo (the file eval_gui.py's
+--output_backward branch means to write).  --occlusion runs both directions and adds the forward-backward occlusion mask
+(losses.occlusion): this project's occlusion precision / recall / F1 against KITTI's occluded pixels on train_* variants,
+and %06d_10_occ.png (8-bit, 255 = occluded) with --output_benchmark.  Colour-wheel visualisations and other datasets are
+not supported."""
 import argparse
 import os
 import shutil
 import sys
 
 VARIANTS = ('train_2012', 'train_2015', 'test_2012', 'test_2015')
-UNSUPPORTED = {'output_visual': "--output_visual (colour-wheel / error images) is not supported",
-               'output_backward': "--output_backward (backward-flow export) is not supported"}
+UNSUPPORTED = {'output_visual': "--output_visual (colour-wheel / error images) is not supported"}
 
 
 def parser():
@@ -26,7 +30,10 @@ def parser():
     ap.add_argument('--output_benchmark', action='store_true', help='write the benchmark flow files')
     ap.add_argument('--output_png', action='store_true', help='KITTI 16-bit PNG files (default: .flo)')
     ap.add_argument('--output_visual', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('--output_backward', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--output_backward', action='store_true',
+                    help='with --output_benchmark: also write the backward flow (%%06d_01.png / .flo)')
+    ap.add_argument('--occlusion', action='store_true',
+                    help='forward-backward occlusion: scores on train_* variants, %%06d_10_occ.png with --output_benchmark')
     ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
     ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
@@ -45,6 +52,8 @@ def parse_args(argv=None):
     for k, msg in UNSUPPORTED.items():
         if getattr(a, k):
             ap.error(msg)
+    if a.output_backward and not a.output_benchmark:      # eval_gui.py reads the flag inside its output_benchmark branch
+        ap.error("--output_backward requires --output_benchmark")
     if a.batch_size <= 0:
         ap.error("--batch_size must be positive")
     return a
@@ -81,7 +90,7 @@ class _KITTIData:
 def main(argv=None):
     a = parse_args(argv)
     from .core.util import config_dict, convert_input_strings
-    from .core.inference import FlowEstimator
+    from .core.inference import OCC_NAMES, FlowEstimator
     from .kitti.input import KITTIInput
     cfg_path, ckpt_dir = experiment_paths(a.ex, a.config)
     config = config_dict(cfg_path)
@@ -89,14 +98,16 @@ def main(argv=None):
     dirs = config_dict(a.config).get('dirs', {})
     convert_input_strings(params, dirs)
     params.update(config.get('train_' + a.dataset, {}))
-    est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch_size, net_size=tuple(a.dims))
+    est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch_size, net_size=tuple(a.dims),
+                                        bidirectional=a.output_backward or a.occlusion)
     kinput = KITTIInput(_KITTIData(dirs.get('data', '')), batch_size=a.batch_size, normalize=False, dims=tuple(a.dims))
     batches = lambda: getattr(kinput, 'input_' + a.variant)()            # noqa: E731
     num = None if a.num < 0 else a.num
     print("-- evaluating %s (step %s) on kitti %s" % (a.ex, est.global_step, a.variant))
     if a.variant.startswith('train'):
         res = est.evaluate(batches(), num=num)
-        for k in res['names']:
+        names = res['names'] + [k for k in OCC_NAMES if a.occlusion and k in res]
+        for k in names:
             print("%-24s %.4f" % (k, res[k]))
         print("examples: %d" % res['num_examples'])
     if a.output_benchmark:
@@ -105,7 +116,8 @@ def main(argv=None):
             shutil.rmtree(out_dir)
         os.makedirs(out_dir)
         shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
-        paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=num)
+        paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=num, backward=a.output_backward,
+                           occlusion=a.occlusion)
         print("wrote %d files to %s" % (len(paths), out_dir))
     return 0
 
