@@ -607,6 +607,48 @@ int unflow_inference_occlusion(const float* flow_fw, const float* flow_bw, const
                                const float* gt_mask, unsigned char* occ_fw, unsigned char* occ_bw, int* counts,
                                unflow_stream_t stream);
 
+/* ===================================================================== */
+/* flow visualisation (csrc/visual.hip, core/flow_util.py, core/inference.py) */
+/* ===================================================================== */
+
+/* Every image is fp32 [..][3] in [0, 1] (out_f32) and / or uint8 (out_u8), at least one of them:
+ *   byte = floor(min(max(x * 255, 0), 255) + 0.5), round to nearest, evaluated exactly (fp64) from the fp32 value. */
+
+/* flow_util.py:5-43 on dense tensors: flow [B,H,W,2], mask [B,H,W,1] or NULL (= ones) -> out [B,H,W,3]:
+ *   hue = floormod(angle / 2 pi + 1, 1) with the reference's atan2 table (u == 0: +-pi; u == v == 0: hue 0, the pixel is white),
+ *   saturation = clip(|flow| * 8 / max_flow, 0, 1) (max_flow == 0: 0), value 1, tf.image.hsv_to_rgb, times mask.
+ * max_flow: a HOST pointer to the scale (used as max(max_flow[0], 1)), or NULL: max |flow * mask| over the whole batch, formed on
+ * the stream in max_bits (an integer max of bit patterns: exact, order-free): two DEVICE uint32 of scratch, required then,
+ * zero-initialised and left zero by every launch. */
+int unflow_flow_to_color(const float* flow, const float* mask, const float* max_flow, int B, int H, int W, float* out_f32,
+                         unsigned char* out_u8, unsigned* max_bits, unflow_stream_t stream);
+
+/* flow_util.py:46-95: flow_1, flow_2 (the ground truth) [B,H,W,2], mask_occ [B,H,W,1], mask_noc [B,H,W,1] or NULL (= ones).
+ * log_colors != 0: error = min(|f1 - f2| / 3, 20 |f1 - f2| / |f2|) (|f2| == 0: the first term) -> the KITTI devkit's ten-bin colour
+ * map ([lo, hi) -> rgb / 255; black from 1e9 on), halved where mask_noc == 0, times mask_occ.  log_colors == 0:
+ * e = min(|f1 - f2|, 5) / 5 * mask_occ -> (e, e * mask_noc, e * mask_noc). */
+int unflow_flow_error_image(const float* flow_1, const float* flow_2, const float* mask_occ, const float* mask_noc, int log_colors,
+                            int B, int H, int W, float* out_f32, unsigned char* out_u8, unflow_stream_t stream);
+
+/* The pictures of one inference batch, geometry from desc: frames as for unflow_inference_input, flow [B][Hmax][Wmax][2] the
+ * frame-size flow of unflow_inference_output, gt_flow / gt_mask as for unflow_inference_output (both NULL: none).  For every
+ * sample b with desc h > 0 and every frame pixel (y < h, x < w), into image k of out [UNFLOW_VISUAL_IMAGES][B][Hmax][Wmax][3]
+ * (nothing else is written):
+ *   0 overlay            (0.5 im1 + 0.5 im2) / 255, im = the frame resized to (H, W) and back to (h, w) (eval_gui.py:125-134),
+ *                        bit-identical to two unflow_resize_bilinear_tf1 launches;
+ *   1 brightness error   |im1 - image_warp(im2, flow)| / 255, unflow_image_warp_fwd's taps and tap order;
+ *   2 flow colours       flow_to_color(flow), max_flow per sample;
+ * and for a sample with desc nmaps > 0 (map 0: flow_occ / mask_occ, map 1: mask_noc; one map: mask_noc = ones):
+ *   3 error image        flow_error_image(flow, flow_occ, mask_occ, mask_noc), log colours;
+ *   4 gt colours         flow_to_color(flow_occ, mask_occ), max_flow per sample.
+ * shown: scratch of 2 * B * Hmax * Wmax * 4 floats (the resized frames, 16-byte aligned); max_bits: 3 * B uint32 of scratch (two
+ * maxima per sample, then B tickets), zero-initialised and left zero by every launch (graph replays included: the last block
+ * of a sample cleans up, no memset node).  Deterministic: no float atomics. */
+#define UNFLOW_VISUAL_IMAGES 5
+int unflow_inference_visual(const void* frames, const int* desc, int B, int Hmax, int Wmax, int H, int W, const float* flow,
+                            const float* gt_flow, const float* gt_mask, float* shown, unsigned* max_bits, unsigned char* out_u8,
+                            float* out_f32, unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

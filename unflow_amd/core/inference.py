@@ -17,6 +17,11 @@ continues with the output kernel once more on the backward rows (no ground truth
 
     unflow_inference_occlusion   both frame-size flows -> losses.occlusion's masks of both directions, integer TP / FP / FN
                                  of the forward mask against KITTI's occluded pixels
+
+visual=True: the graph ends with the pictures of eval_gui.py's window (csrc/visual.hip), as 8-bit images:
+
+    unflow_inference_visual      staged frames, frame-size flow, staged ground truth -> overlay, brightness error, flow colours,
+                                 and with ground truth the KITTI error image and the ground truth's colours
 """
 import collections
 import itertools
@@ -35,6 +40,16 @@ OCC_NAMES = ('occ/precision', 'occ/recall', 'occ/F1')
 
 # What estimate_bidirectional returns per pair: [h, w, 2] float32 flows, [h, w] bool occlusion masks (losses.occlusion)
 BidirectionalFlow = collections.namedtuple('BidirectionalFlow', ('flow_fw', 'flow_bw', 'occ_fw', 'occ_bw'))
+# What visualize returns per pair: uint8 [h, w, 3] images — eval_gui.py:199-204's slots (the overlay in place of the first image)
+FlowVisual = collections.namedtuple('FlowVisual', ('overlay', 'warp_error', 'flow'))
+# The images of unflow_inference_visual, in its order, and the file each is exported to (%06d_<tag>.png)
+VISUAL_IMAGES = ('overlay', 'warp_error', 'flow', 'error', 'gt')
+VISUAL_TAGS = ('img', 'diff', 'flow', 'err', 'gt')
+
+
+def visual_files(n, has_gt):
+    """The picture files of example n, in the order they are written: [(index into VISUAL_IMAGES, file name)]."""
+    return [(k, '%06d_%s.png' % (n, VISUAL_TAGS[k])) for k in (0, 2, 1) + ((3, 4) if has_gt else ())]
 
 
 def occlusion_scores(counts):
@@ -110,6 +125,7 @@ class _Slot:
             self.u16_bw = pin(B, Hm, Wm, 3, dtype=torch.int16)
             self.occ = pin(2, B, Hm, Wm, dtype=torch.uint8)          # occ_fw, occ_bw
             self.occ_counts = pin(B, 3, dtype=torch.int32)
+        self.vis = pin(len(VISUAL_IMAGES), B, Hm, Wm, 3, dtype=torch.uint8) if est.visual else None
         self.event = None
         self.pending = None
 
@@ -129,9 +145,11 @@ class FlowEstimator:
     """Frame-size optical flow of a trained FlowNet spec (params['flownet'], 'full_res', ...), `batch` pairs per replay at the
     network size net_size = (H, W) (divisible by 64), frames of any size up to max_frame (default: net_size).
     bidirectional: also the backward flow and the forward-backward occlusion masks (estimate_bidirectional, the occlusion
-    scores of evaluate, export's backward / occlusion files)."""
+    scores of evaluate, export's backward / occlusion files).  visual: also the 8-bit pictures of every batch (visualize,
+    export(visual=True))."""
 
-    def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False):
+    def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
+                 visual=False):
         self.params = dict(params)
         self.B = int(batch)
         self.H, self.W = (int(v) for v in net_size)
@@ -139,6 +157,7 @@ class FlowEstimator:
         self.dev = torch.device('cuda:0') if device is None else torch.device(device)
         self.use_graph = bool(use_graph)
         self.bidirectional = bool(bidirectional)
+        self.visual = bool(visual)
         eng_params = {k: v for k, v in self.params.items() if k.endswith('_weight') or k in ENGINE_KEYS}
         self.engine = FlowNetEngine(self.B, self.H, self.W, params=eng_params or None, device=self.dev, seed=None,
                                     inference=True, bidirectional=self.bidirectional)
@@ -163,6 +182,11 @@ class FlowEstimator:
                 self.out_u16_bw = z(B, Hm, Wm, 3, dtype=torch.int16)
                 self.occ = z(2, B, Hm, Wm, dtype=torch.uint8)        # occ_fw, occ_bw
                 self.occ_counts = z(B, 3, dtype=torch.int32)
+            self.vis = self.vis_shown = self.vis_max = None
+            if self.visual:
+                self.vis = z(len(VISUAL_IMAGES), B, Hm, Wm, 3, dtype=torch.uint8)
+                self.vis_shown = z(2, B, Hm, Wm, 4)                  # the frames as shown: resized to the network and back
+                self.vis_max = z(3 * B, dtype=torch.int32)           # bit patterns of max |flow|, max |gt * mask|; B tickets
         last = e.stages[-1]
         self.flow_src = last.act['flow0'] if e.full_res else last.act['flow2']     # bidirectional: rows [0, B) fw, [B, 2B) bw
         self.in_planes = e.X0.pl if (e.X0.pl is not None and e.stages[0].is_c) else None
@@ -197,7 +221,7 @@ class FlowEstimator:
     # ------------------------------------------------------------------------------------------ device work
     def _launch(self):
         """Input kernel, forward pass, output kernel on the current stream (what the graph holds); bidirectional: then the
-        output kernel on the backward rows and the occlusion kernel."""
+        output kernel on the backward rows and the occlusion kernel; visual: then the pictures."""
         e = self.engine
         L = _lib.lib()
         st = e.stream()
@@ -209,8 +233,15 @@ class FlowEstimator:
                                         self.B, self.Hmax, self.Wmax, ptr(self.out_flow), ptr(self.out_u16), ptr(self.gt_flow),
                                         ptr(self.gt_mask), ptr(self.partial), ptr(self.ticket), ptr(self.sums),
                                         ptr(self.counts), st), "inference_output")
-        if not self.bidirectional:
-            return
+        if self.bidirectional:
+            self._launch_backward(f, st)
+        if self.visual:
+            check(L.unflow_inference_visual(ptr(self.frames), ptr(self.desc), self.B, self.Hmax, self.Wmax, self.H, self.W,
+                                            ptr(self.out_flow), ptr(self.gt_flow), ptr(self.gt_mask), ptr(self.vis_shown),
+                                            ptr(self.vis_max), ptr(self.vis), None, st), "inference_visual")
+
+    def _launch_backward(self, f, st):
+        L = _lib.lib()
         fb = f[self.B:]
         check(L.unflow_inference_output(ptr(fb), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(self.desc),
                                         self.B, self.Hmax, self.Wmax, ptr(self.out_flow_bw), ptr(self.out_u16_bw), None, None,
@@ -311,6 +342,9 @@ class FlowEstimator:
                 slot.occ.copy_(self.occ, non_blocking=True)
             if 'occ_counts' in want and nmaps == 2:
                 slot.occ_counts.copy_(self.occ_counts, non_blocking=True)
+            if 'vis' in want:                     # the error image and the gt colours exist only with ground truth
+                nv = len(VISUAL_IMAGES) if nmaps else len(FlowVisual._fields)
+                slot.vis[:nv].copy_(self.vis[:nv], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -376,6 +410,34 @@ class FlowEstimator:
                                       oc[1, i, :h, :w].astype(bool)) for i, (h, w) in enumerate(shapes)]
         return out
 
+    def visualize(self, frames1, frames2):
+        """estimate's pairs as pictures: one FlowVisual(overlay, warp_error, flow) per pair, uint8 [h_i, w_i, 3] — the slots of
+        eval_gui.py:199-204 (:160-165): (0.5 im1 + 0.5 im2) / 255 and |im1 - image_warp(im2, flow)| / 255 on the frames as the
+        reference shows them (resized to the network's size and back), and flow_to_color(flow) with max_flow per pair; bytes
+        rounded to nearest."""
+        if not self.visual:
+            raise RuntimeError("visualize: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
+        exs = self._pairs(frames1, frames2, 'visualize')
+        out = []
+        for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B), want=('vis',)):
+            v = slot.vis.numpy()
+            out += [FlowVisual(*(v[k, i, :h, :w].copy() for k in range(3))) for i, (h, w) in enumerate(shapes)]
+        return out
+
+    def pictures(self, batch_iter, num=None):
+        """The pictures of what KITTIInput.input_{train,test}_{2012,2015}() yields, one dict per example in iteration order:
+        VISUAL_IMAGES' names -> uint8 [h, w, 3]; 'error' and 'gt' only when the input carries ground truth (two maps:
+        flow_error_image(flow, flow_occ, mask_occ, mask_noc) and flow_to_color(flow_occ, mask_occ); one map: mask_noc = ones)."""
+        if not self.visual:
+            raise RuntimeError("pictures: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
+        it = example_stream(batch_iter)
+        if num is not None:
+            it = (ex for i, ex in zip(range(int(num)), it))
+        for slot, shapes, nmaps, _ in self._pipeline_staged(it, ('vis',), lambda exs: (len(exs[0]) - 3) // 2):
+            v = slot.vis.numpy()
+            for i, (h, w) in enumerate(shapes):
+                yield {name: v[k, i, :h, :w].copy() for k, name in enumerate(VISUAL_IMAGES) if k < 3 or nmaps}
+
     def evaluate(self, batch_iter, num=None):
         """Scores on what KITTIInput.input_train_{2012,2015}() yields — (im1, im2, input_shape, flow_occ, mask_occ, flow_noc,
         mask_noc) — or the 2-map form (im1, im2, input_shape, flow_gt, mask), any batch size.  The frames are the
@@ -435,17 +497,25 @@ class FlowEstimator:
         batches = chunks(itertools.chain([first], gen), self.B)
         yield from self._pipeline(batches, staged=tuple(self._dims), nmaps_of=nmaps_of, want=want)
 
-    def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False):
+    def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False, visual=False):
         """The benchmark files of eval_gui.py --output_benchmark (:247-263): for the k-th example in iteration order,
         out_dir/%06d_10.png (KITTI 16-bit RGB, --output_png) or out_dir/%06d_10.flo.  Input: what
-        KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths (per example: _10, _01, _10_occ).
+        KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths (per example: _10, _01, _10_occ, then
+        the pictures).
         backward: also the backward flow, %06d_01.png / .flo (the file eval_gui.py --output_backward means); occlusion: the
-        forward occlusion mask, %06d_10_occ.png (8-bit grey, 255 = occluded).  Both need a bidirectional estimator."""
-        from .input import write_flo, write_kitti_flow_png, write_png_gray8
+        forward occlusion mask, %06d_10_occ.png (8-bit grey, 255 = occluded).  Both need a bidirectional estimator.
+        visual (an estimator built with visual=True): after those, the 8-bit pictures of eval_gui.py --output_visual:
+        %06d_img.png (overlay), %06d_flow.png (flow colours), %06d_diff.png (brightness error) and, when the input carries
+        ground truth (two maps or one), %06d_err.png (the KITTI error image) and %06d_gt.png (the ground truth's colours).
+        eval_gui.py:248-254 writes the brightness error into _flow.png and the flow colours into _err.png and never writes the
+        error image; the names' evident meaning is followed here."""
+        from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         if fmt not in ('png', 'flo'):
             raise ValueError("export: fmt must be 'png' or 'flo'")
         if (backward or occlusion) and not self.bidirectional:
             raise ValueError("export: backward / occlusion files need FlowEstimator(..., bidirectional=True)")
+        if visual and not self.visual:
+            raise ValueError("export: the pictures need FlowEstimator(..., visual=True)")
         os.makedirs(out_dir, exist_ok=True)
         it = example_stream(batch_iter)
         if num is not None:
@@ -456,8 +526,12 @@ class FlowEstimator:
             want += ('u16_bw',) if fmt == 'png' else ('flow_bw',)
         if occlusion:
             want += ('occ',)
+        if visual:
+            want += ('vis',)
         n = 0
-        for slot, shapes, _, _ in self._pipeline_staged(it, want, lambda exs: 0):
+        # the ground truth is staged only for the pictures that show it
+        nmaps_of = (lambda exs: (len(exs[0]) - 3) // 2) if visual else (lambda exs: 0)
+        for slot, shapes, nmaps, _ in self._pipeline_staged(it, want, nmaps_of):
             for i, (h, w) in enumerate(shapes):
                 flows = [('10', slot.u16, slot.flow)] + ([('01', slot.u16_bw, slot.flow_bw)] if backward else [])
                 for tag, u16, flow in flows:
@@ -471,5 +545,11 @@ class FlowEstimator:
                     path = os.path.join(out_dir, '%06d_10_occ.png' % n)
                     write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
                     paths.append(path)
+                if visual:
+                    vis = slot.vis.numpy()
+                    for k, name in visual_files(n, nmaps > 0):               # _img, _flow, _diff, _err, _gt
+                        path = os.path.join(out_dir, name)
+                        write_png_rgb8(path, vis[k, i, :h, :w])
+                        paths.append(path)
                 n += 1
         return paths

@@ -264,6 +264,16 @@ def write_png_gray8(path, img):
     with open(path, 'wb') as f:
         f.write(encode_png8_gray(a))
 
+
+def write_png_rgb8(path, img):
+    """An 8-bit RGB PNG of uint8 [H,W,3] (the pictures of FlowEstimator.export(visual=True))."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_png_rgb8: expected uint8 [H,W,3], got %s %s" % (a.dtype, a.shape))
+    with open(path, 'wb') as f:
+        f.write(encode_png8_rgb(a))
+
+
 # ----------------------------------------------------------------------------------------------------------- resizing
 def resize_bilinear_tf1(x, out_h, out_w):
     """tf.image.resize_bilinear, TF1 legacy (align_corners=False, no half-pixel centres): src = dst * in / out."""

@@ -10,15 +10,16 @@ The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives
 --output_png, else %06d_10.flo; with --output_backward also the backward flow, %06d_01.png / .flo (the file eval_gui.py's
 --output_backward branch means to write).  --occlusion runs both directions and adds the forward-backward occlusion mask
 (losses.occlusion): this project's occlusion precision / recall / F1 against KITTI's occluded pixels on train_* variants,
-and %06d_10_occ.png (8-bit, 255 = occluded) with --output_benchmark.  Colour-wheel visualisations and other datasets are
-not supported."""
+and %06d_10_occ.png (8-bit, 255 = occluded) with --output_benchmark.  The pictures (colour wheel, error map, overlay) are
+python -m unflow_amd.visualize's; other datasets are not supported."""
 import argparse
 import os
 import shutil
 import sys
 
 VARIANTS = ('train_2012', 'train_2015', 'test_2012', 'test_2015')
-UNSUPPORTED = {'output_visual': "--output_visual (colour-wheel / error images) is not supported"}
+UNSUPPORTED = {'output_visual': "--output_visual is not supported here: python -m unflow_amd.visualize writes the colour-wheel / "
+                                "error images"}
 
 
 def parser():
