@@ -578,6 +578,32 @@ int unflow_flow_error_sums(const float* f1, const float* f2, const float* mask /
 int unflow_inference_input(const void* frames, const int* desc, int B, int Hmax, int Wmax, int H, int W, float* net_in4,
                            const float* mean3, const unflow_planes* net_pl, unflow_stream_t stream);
 
+/* Sequence mode (FlowEstimator(..., sequence=True)), one frame per row: frames [F][Hmax][Wmax][3] (uint8 or fp32 per desc u8),
+ * desc [F][8] -> net_in4 [F][H][W][4], row r from frame r with desc slot r.  net_in4 and net_pl point at the FIRST row to write
+ * (the estimator passes row 1 of the engine's F + 1 input rows); exactly F rows are written, nothing else.  The value of every
+ * pixel and of its operand planes is unflow_inference_input's: a row is bit-identical to the row that entry writes for the
+ * same frame and desc.  A slot with h = 0 writes zeros. */
+int unflow_inference_input_frames(const void* frames, const int* desc, int F, int Hmax, int Wmax, int H, int W, float* net_in4,
+                                  const float* mean3, const unflow_planes* net_pl, unflow_stream_t stream);
+
+/* One buffer of unflow_sequence_carry: sample rows of `pixels` pixels, `stride` bytes apart, starting at base (row 0); of every
+ * pixel the first `bytes` bytes are copied (bytes < stride: one channel segment of a wider concat buffer, the other channels
+ * are left alone).  base, bytes and stride must be even; 16-byte vector accesses are used where all three are multiples of 16
+ * (else 8, 4 or 2 bytes). */
+typedef struct {
+  void* base;
+  long pixels;
+  int bytes;
+  int stride;
+} unflow_carry_buf;
+#define UNFLOW_CARRY_MAX 16
+
+/* Sequence mode: in each of the n_bufs (<= UNFLOW_CARRY_MAX) buffers of the HOST array bufs, copy sample row src to row 0, in
+ * one launch.  src = *src_row is read from DEVICE memory at run time (an int32 the host rewrites with the desc tables; a
+ * captured graph keeps its address): 0 = nothing to carry, a no-op, as is a value outside [1, max_row] (max_row: the last row
+ * every buffer has).  Rows other than row 0 are never written. */
+int unflow_sequence_carry(const unflow_carry_buf* bufs, int n_bufs, const int* src_row, int max_row, unflow_stream_t stream);
+
 /* flow [B][fh][fw][2] (the last network's flow2, or flow0 at (H, W) with full_res) -> for every sample b with desc h > 0 and
  * every frame pixel (y < h, x < w):
  *   f = resize_tf1(resize_tf1(flow, H, W) * flow_scale, h, w) (full_res: resize_tf1(flow * flow_scale, h, w)),

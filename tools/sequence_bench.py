@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
+
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof]
+
+For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
+of the replayed graph of FlowEstimator(..., sequence=True) in its steady state (a carried frame and B new frames: B pairs per
+replay) and of the pair-mode estimator (B pairs per replay) — device events around every one of `iters` replays after `warmup`,
+staging excluded; mean, standard deviation, minimum and maximum over the replays, and the ratio sequence / pair mode of the
+means.  Beside them the device memory of both estimators.  --rocprof: child runs under `rocprofv3 --kernel-trace --stats` give the
+times of the two sequence kernels at B = 8 (with the bytes they must move) and, for FlowNetC at B = 4, the kernels of ten
+replays of either graph, heaviest first — where the time of a replay goes in each mode."""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W = 384, 1280
+FRAME = (375, 1242)
+
+
+def _frames(n):
+    import numpy as np
+    rs = np.random.RandomState(0)
+    a = rs.randint(0, 256, size=FRAME + (3,)).astype(np.uint8)
+    return [np.roll(a, 2 * i, 1) for i in range(n)]
+
+
+def _estimator(spec, B, sequence):
+    import torch
+    os.environ['UNFLOW_CONV_MATH'] = 'bf16x3'
+    from unflow_amd.core.inference import FlowEstimator
+    import gc
+    dev = torch.device('cuda:0')
+    gc.collect()                               # an earlier case's estimator is freed now, not inside this measurement
+    torch.cuda.synchronize()
+    m0 = torch.cuda.memory_allocated(dev)
+    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence)
+    torch.cuda.synchronize()
+    mem = torch.cuda.memory_allocated(dev) - m0
+    est.engine.init_params(seed=1)
+    est._params_changed()
+    fr = _frames(3 * B + 1)
+    if sequence:
+        est.estimate_sequence(fr[:3 * B])      # the last replay: a carried frame and B new ones, every pair slot valid
+    else:
+        est.estimate(fr[:B], fr[1:B + 1])
+    return est, mem
+
+
+def time_replays(est, iters, warmup):
+    """ms of each of `iters` replays (device events between consecutive replays)."""
+    import torch
+    for _ in range(warmup):
+        est.graph.replay()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(iters + 1)]
+    ev[0].record()
+    for i in range(iters):
+        est.graph.replay()
+        ev[i + 1].record()
+    ev[-1].synchronize()
+    return [ev[i].elapsed_time(ev[i + 1]) for i in range(iters)]
+
+
+def _stats(ms, B):
+    return dict(ms_per_pair=round(statistics.mean(ms) / B, 4), std=round(statistics.pstdev(ms) / B, 4),
+                min=round(min(ms) / B, 4), max=round(max(ms) / B, 4))
+
+
+def case(spec, B, iters, warmup):
+    import gc
+    import torch
+    out = dict(spec=spec, B=B)
+    for name, seq in (('pair', False), ('sequence', True)):
+        est, mem = _estimator(spec, B, seq)
+        out[name] = _stats(time_replays(est, iters, warmup), B)
+        out[name]['estimator_MB'] = round(mem / 1e6, 1)
+        del est
+        gc.collect()
+        torch.cuda.empty_cache()
+    out['sequence_over_pair'] = round(out['sequence']['ms_per_pair'] / out['pair']['ms_per_pair'], 4)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------- rocprofv3 children
+def kernels_only(iters):
+    """Child: the two sequence kernels of a FlowNetC estimator at B = 8, `iters` times each (carry source B)."""
+    import torch
+    est, _ = _estimator('C', 8, True)
+    e = est.engine
+    for _ in range(iters):
+        e.sequence_carry(est.tab[16 * 8:])
+        e.sequence_input(est.frames, est.tab, est.Hmax, est.Wmax)
+    torch.cuda.synchronize()
+
+
+def graph_only(sequence, iters):
+    """Child: `iters` replays of the FlowNetC graph at B = 4 in one mode."""
+    import torch
+    est, _ = _estimator('C', 4, sequence)
+    for _ in range(iters):
+        est.graph.replay()
+    torch.cuda.synchronize()
+
+
+def _rocprof(args):
+    d = tempfile.mkdtemp(prefix='seqprof_')
+    cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '-o', 'run', '--', sys.executable,
+           os.path.abspath(__file__)] + args
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    if r.returncode != 0:
+        return None, dict(error="rocprofv3 exit %d" % r.returncode, tail=r.stdout.decode(errors='replace')[-400:])
+    stats = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
+    if not stats:
+        return None, dict(error="no kernel_stats.csv")
+    return list(csv.DictReader(open(stats[0]))), None
+
+
+def carry_bytes(B=8):
+    """Bytes unflow_sequence_carry reads plus writes for FlowNetC at (H, W), bf16x3: one row of x0, of c3 and of the conv2
+    segment of cat2, fp32 and three planes each (x0: fp32 only)."""
+    x0 = H * W * 16
+    c3 = (H // 8) * (W // 8) * 256 * (4 + 3 * 2)
+    cat2 = (H // 4) * (W // 4) * 128 * (4 + 3 * 2)
+    return 2 * (x0 + c3 + cat2)
+
+
+def input_bytes(B=8):
+    """Bytes unflow_inference_input_frames must move: B uint8 frames read, B rows of x0 and of its three planes written."""
+    return B * FRAME[0] * FRAME[1] * 3 + B * H * W * (16 + 3 * 4 * 2)
+
+
+def rocprof_cases(iters):
+    out = {}
+    rows, err = _rocprof(['--kernels-only', '--iters', str(iters)])
+    if err:
+        out['kernels_B8'] = err
+    else:
+        k = {}
+        for name, nbytes in (('sequence_carry_kernel', carry_bytes()), ('inference_input_frames_kernel', input_bytes())):
+            for row in rows:
+                if name in row['Name']:
+                    ns = float(row['AverageNs'])
+                    k[name] = dict(us=round(ns / 1e3, 2), MB=round(nbytes / 1e6, 2), TBps=round(nbytes / ns / 1e3, 3))
+        out['kernels_B8'] = k
+    for mode in ('pair', 'sequence'):
+        rows, err = _rocprof(['--graph-only', mode, '--iters', '10'])
+        if err:
+            out['graph_C_B4_' + mode] = err
+            continue
+        rows.sort(key=lambda r: -float(r['TotalDurationNs']))
+        total = sum(float(r['TotalDurationNs']) for r in rows)
+        out['graph_C_B4_' + mode] = dict(
+            note='whole child run: 10 timed replays plus set-up (one eager pass, the capture pass, two replays)',
+            total_ms=round(total / 1e6, 3),
+            top=[dict(kernel=r['Name'][:72], calls=int(r['Calls']), total_ms=round(float(r['TotalDurationNs']) / 1e6, 3),
+                      avg_us=round(float(r['AverageNs']) / 1e3, 2)) for r in rows[:14]])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--rocprof', action='store_true', help='also the kernel times of rocprofv3 child runs')
+    ap.add_argument('--kernels-only', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--graph-only', choices=('pair', 'sequence'), help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.kernels_only:
+        return kernels_only(a.iters)
+    if a.graph_only:
+        return graph_only(a.graph_only == 'sequence', a.iters)
+    res = dict(metric='sequence_ms_per_pair_over_pair_mode', shape=[H, W], frames='uint8 %dx%d' % FRAME, math='bf16x3',
+               iters=a.iters, warmup=a.warmup, predicted=dict(C=0.75, CSS='closer to 1'), cases=[])
+    for spec in ('C', 'CSS'):
+        for B in (1, 4, 8):
+            res['cases'].append(case(spec, B, a.iters, a.warmup))
+    if a.rocprof:
+        res.update(rocprof_cases(a.iters))
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -125,6 +125,11 @@ def planes_of(pl, scale=0.0):
     return ctypes.byref(Planes(pl.data_ptr(), pl.stride(0), pl.stride(-2), pl.shape[0], float(scale)))
 
 
+class CarryBuf(ctypes.Structure):
+    """unflow_carry_buf of include/unflow_hip.h (one buffer of unflow_sequence_carry)."""
+    _fields_ = [('base', ctypes.c_void_p), ('pixels', ctypes.c_long), ('bytes', ctypes.c_int), ('stride', ctypes.c_int)]
+
+
 class PyrLevel(ctypes.Structure):
     """unflow_pyr_level of include/unflow_hip.h (argument of unflow_loss_pyramid_default)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ('im', 'flow', 'gray1', 'gray2w', 'mask', 'dist', 'd_flow')] + \

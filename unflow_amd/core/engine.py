@@ -135,11 +135,12 @@ class ActView(dict):
 
 
 class _Op:
-    """One forward launch of a stage: a layer (src slice -> dst slice) or the correlation; n: the samples (rows) it runs on."""
-    __slots__ = ('kind', 'l', 'src', 'dst', 'n')
+    """One forward launch of a stage: a layer (src slice -> dst slice) or the correlation; n: the samples (rows) it runs on,
+    r0: the first of them (0 everywhere but in the feature tower of a sequence engine, which computes rows [1, B + 1))."""
+    __slots__ = ('kind', 'l', 'src', 'dst', 'n', 'r0')
 
     def __init__(self, kind, l, src, dst):
-        self.kind, self.l, self.src, self.dst, self.n = kind, l, src, dst, 0
+        self.kind, self.l, self.src, self.dst, self.n, self.r0 = kind, l, src, dst, 0, 0
 
 
 def _rows(t, n):
@@ -147,6 +148,13 @@ def _rows(t, n):
     if t.t.shape[0] == n:
         return t
     return L.PT(t.t[:n], None if t.pl is None else t.pl[:, :n], t.scale)
+
+
+def _row_range(t, r0, n):
+    """Samples [r0, r0 + n) of a PT (fp32 tensor and planes); r0 = 0 is _rows(t, n)."""
+    if r0 == 0:
+        return _rows(t, n)
+    return L.PT(t.t[r0:r0 + n], None if t.pl is None else t.pl[:, r0:r0 + n], t.scale)
 
 
 class _Stage:
@@ -269,11 +277,19 @@ class _Stage:
         one_dir = getattr(eng, 'one_dir', False)
         # (a stage built for its layer table alone, without an engine's shape, counts rows in units of B)
         nB, nN = (eng.B, eng.N) if hasattr(eng, 'N') else (1, 2)
+        # Sequence engine (one-direction, forward only): F = B + 1 frame rows, pair i = (row i, row i + 1).  The network input
+        # and the tower buffers of a first-stage FlowNetC have F rows; the tower layers compute rows [1, F) — the new frames of
+        # a replay — and row 0 is carried over from the previous replay (unflow_sequence_carry), never computed
+        seq = getattr(eng, 'sequence', False)
+        if seq:
+            nN = nB + 1
         self.rows = {name: (nN if (not one_dir or name in enc) else nB) for name in B}
         self.rows['x0'] = nN
         for op in self.ops:
             # (the correlation reads and, backward, writes all rows of c3: both frames' features)
             op.n = self.rows['c3'] if op.kind == 'corr' else min(self.rows[op.src[0]], self.rows[op.dst[0]])
+            if seq and op.kind == 'layer' and op.dst[0] in enc and op.l.name.split('/')[-1] in ('conv1', 'conv2', 'conv3'):
+                op.n, op.r0 = nB, 1
         self._plan_backward()
 
     # -------------------------------------------------------------- backward plan
@@ -403,8 +419,9 @@ class _Stage:
             x0s = self.act['x0s']
             pf = prev_flow2
             ph, pw = (0, 0) if pf is None else (pf.shape[1], pf.shape[2])
-            if e.one_dir:         # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B)
-                check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[:B]), ptr(e.x0[B:]), ptr(pf), ptr(x0s), x0s.stride(2), B,
+            if e.one_dir:         # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B); sequence: rows [1, B + 1)
+                r1 = 1 if e.sequence else B
+                check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[:B]), ptr(e.x0[r1:]), ptr(pf), ptr(x0s), x0s.stride(2), B,
                                                          e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
             else:
                 check(_lib.lib().unflow_stack_input(ptr(e.x0), ptr(pf), ptr(x0s), x0s.stride(2), B, N, e.H, e.W, ph, pw,
@@ -420,8 +437,9 @@ class _Stage:
                 h8, w8 = e.H // 8, e.W // 8
                 pl = self._corr_planes(c3, refresh=True)                      # bf16 x 3 planes: the matrix-core path
                 if e.one_dir:         # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
-                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, B:]))
-                    check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[:B]), ptr(c3.t[B:]), c3.t.stride(2), p0, p1, 0,
+                    r1 = 1 if e.sequence else B           # sequence: the second frame of pair i is row i + 1
+                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, r1:]))
+                    check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[:B]), ptr(c3.t[r1:]), c3.t.stride(2), p0, p1, 0,
                                                                     ptr(out.t), out.t.stride(2), B, C, h8, w8, 1, 20, 20, 1, 2,
                                                                     e.stream()), "correlation")
                 else:
@@ -433,7 +451,7 @@ class _Stage:
                     L.planes_from_f32(out.t, out.pl)
                 continue
             l = op.l
-            x, y = _rows(self.pt(op.src), op.n), _rows(self.pt(op.dst), op.n)
+            x, y = _row_range(self.pt(op.src), op.r0, op.n), _row_range(self.pt(op.dst), op.r0, op.n)
             if l.cout_p != l.cout:
                 y = L.PT(y.t.as_strided(y.t.shape[:3] + (l.cout_p,), y.t.stride(), y.t.storage_offset()),
                          None if y.pl is None else y.pl)
@@ -596,7 +614,7 @@ class FlowNetEngine:
     target (unflow_supervised_flow_loss per counted network)."""
 
     def __init__(self, batch, height, width, params=None, device=None, seed=0, layout_only=False, supervised=False,
-                 inference=False, bidirectional=False):
+                 inference=False, bidirectional=False, sequence=False):
         """layout_only: build the layer table and the flat parameter / gradient buffers (on `device`, which may then be the
         CPU) but no activations — for tools and the data-parallel tests that only need the flat layout and its buckets.
         inference: the forward-only engine (core/inference.py): the one-direction plan of supervised=True, and only what the
@@ -604,7 +622,11 @@ class FlowNetEngine:
         planes only the layout the forward kernels take (transposed for conv layers, direct for conv_transpose layers).  The
         flat parameter layout is the training engine's, so load_tf_params / export_tf_params / checkpoints work unchanged.
         bidirectional (with inference only): the forward-only engine on the training engine's plan — every buffer and op on
-        N = 2B rows, the directed batch into the correlation — so final_flows() / flows() give (fw, bw) row slices."""
+        N = 2B rows, the directed batch into the correlation — so final_flows() / flows() give (fw, bw) row slices.
+        sequence (with inference only, one direction): flow along a clip, every frame encoded once.  The network input and the
+        feature tower of a first-stage FlowNetC hold F = B + 1 frame rows, pair i is (row i, row i + 1): the tower runs on rows
+        [1, F) — B rows where the pair engine runs 2B — and row 0 is the previous replay's last frame, copied there by
+        sequence_carry().  set_frames() / sequence_input() fill rows [1, F)."""
         assert height % 64 == 0 and width % 64 == 0, "FlowNet needs H, W divisible by 64"
         if bidirectional and supervised:
             raise ValueError("FlowNetEngine: bidirectional is for the inference engine; the supervised engine is one-direction")
@@ -612,9 +634,13 @@ class FlowNetEngine:
             raise ValueError("FlowNetEngine: bidirectional needs inference=True (the training engine is bidirectional already)")
         if supervised and inference:
             raise ValueError("FlowNetEngine: supervised and inference are exclusive")
+        if sequence and (bidirectional or supervised or not inference):
+            raise ValueError("FlowNetEngine: sequence needs inference=True and is one-direction (neither bidirectional nor "
+                             "supervised)")
         self.supervised = bool(supervised)
         self.inference = bool(inference)
         self.bidirectional = bool(bidirectional)
+        self.sequence = bool(sequence)
         # FlowNetC tower on 2B rows, everything after it on B rows
         self.one_dir = self.supervised or (self.inference and not self.bidirectional)
         self.params = dict(DEFAULT_PARAMS) if params is None else dict(params)
@@ -628,9 +654,12 @@ class FlowNetEngine:
         if self.supervised and self.full_res and self.train_all:
             raise ValueError("supervised full_res with train_all: the reference subtracts the earlier networks' quarter-size "
                              "flow2 * 20 from the full-size ground truth (supervised.py:50-60), a shape error")
+        if sequence and self.full_res:
+            raise ValueError("FlowNetEngine: sequence with full_res is not built (DESIGN 7.5)")
         self.spec = spec
         self.B, self.H, self.W = batch, height, width
         self.N = 2 * batch
+        self.F = batch + 1                # sequence engine: frame rows of the network input and the tower
         self.dev = torch.device('cuda:0') if device is None else torch.device(device)
         self.math = conv_math_mode()
         # filter gradients on a second stream, in groups of wgrad_group layers (UNFLOW_WGRAD_GROUP=0: inline)
@@ -871,9 +900,10 @@ class FlowNetEngine:
     def _alloc_activations(self):
         N, H, W, dev = self.N, self.H, self.W, self.dev
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        n0 = self.F if self.sequence else N           # rows of the network input
         # mean-subtracted network input (4th channel zero) + its operand planes.  Row length 4 when W is even: a 16-byte
         # K granule of conv1 is then two pixels (rgb4_form of csrc/conv_planes.hip), else 8 (one zero-padded pixel)
-        self.X0 = L.PT(z(N, H, W, 4), torch.zeros(self.n_planes, N, H, W, 4 if (W % 2 == 0 and RGB4_FORM) else 8, dtype=torch.int16, device=dev)
+        self.X0 = L.PT(z(n0, H, W, 4), torch.zeros(self.n_planes, n0, H, W, 4 if (W % 2 == 0 and RGB4_FORM) else 8, dtype=torch.int16, device=dev)
                        if self.n_planes else None)
         self.x0 = self.X0.t
         self.im01 = None if self.inference else z(N, H, W, 3)     # images in [0,1] for the losses
@@ -890,6 +920,7 @@ class FlowNetEngine:
             self.lv = []
             self.final_flow = z(N if self.bidirectional else self.B, H, W, 2)
             self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
+            self._seq_tab = None
             return
         if self.supervised:
             # engine-owned targets (fixed addresses for the captured graphs; set_input copies into them); no loss pyramid
@@ -1044,6 +1075,8 @@ class FlowNetEngine:
         core/inference.py stages and resizes frames of any size with unflow_inference_input instead)."""
         if augment is not None or target is not None:
             raise ValueError("set_input: the inference engine takes neither augmentation draws nor a target")
+        if self.sequence:
+            raise RuntimeError("set_input: a sequence engine takes frames, not pairs: set_frames(frames, carry)")
         B, H, W = self.B, self.H, self.W
         im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
         im2 = torch.as_tensor(im2).to(device=self.dev, dtype=torch.float32).contiguous()
@@ -1053,6 +1086,65 @@ class FlowNetEngine:
         pl = self.X0.pl if (self.X0.pl is not None and self.stages[0].is_c) else None
         check(_lib.lib().unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(None), self.mean_host,
                                                    _lib.planes_of(pl), self.stream()), "prepare_image_pair")
+
+    # ------------------------------------------------------------------ sequence engine: rows [1, F) and the carried row 0
+    def carry_list(self):
+        """What unflow_sequence_carry moves to row 0: the network input (the first frame of pair 0 for FlowNetS stages) and, of
+        a first-stage FlowNetC, conv3's output and the conv2 segment of cat2 — each as fp32 and as every operand plane.  (c1 is
+        read by conv2 alone, on rows [1, F): its row 0 is never read.)  fp16 mode: the correlation's bf16 x 3 side planes are
+        re-split from all F fp32 rows of c3 by every forward pass, after the carry."""
+        bufs = []
+
+        def add(t, pl, lo, n):
+            """channels [lo, lo + n) of the fp32 tensor t [F, h, w, C] and of its planes pl [P, F, h, w, Cp]"""
+            px = t.shape[1] * t.shape[2]
+            bufs.append(_lib.CarryBuf(t[0, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4))
+            for p in ([] if pl is None else range(pl.shape[0])):
+                bufs.append(_lib.CarryBuf(pl[p, 0, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
+        add(self.x0, None, 0, 4)
+        st = self.stages[0]
+        if st.is_c:
+            for name, seg in (('c3', 'conv3'), ('cat2', 'conv2')):
+                lo, n = st.bufs[name][1][seg]
+                add(st.A[name].t, st.A[name].pl, lo, pad4(n))
+        return bufs
+
+    def sequence_carry(self, src_dev):
+        """Row *src_dev -> row 0 of every buffer of carry_list(); src_dev: a device int32 (0: nothing to carry)."""
+        if not self.sequence:
+            raise RuntimeError("sequence_carry: not a sequence engine (FlowNetEngine(..., inference=True, sequence=True))")
+        bufs = self.carry_list()
+        arr = (_lib.CarryBuf * len(bufs))(*bufs)
+        check(_lib.lib().unflow_sequence_carry(arr, len(bufs), ptr(src_dev), self.B, self.stream()), "sequence_carry")
+
+    def sequence_input(self, frames, desc, Hmax, Wmax):
+        """Staged frames [B][Hmax][Wmax][3] with the device table desc [B][8] -> rows [1, F) of the network input (and of
+        conv1's operand planes for a first-stage FlowNetC)."""
+        if not self.sequence:
+            raise RuntimeError("sequence_input: not a sequence engine (FlowNetEngine(..., inference=True, sequence=True))")
+        pl = self.X0.pl[:, 1:] if (self.X0.pl is not None and self.stages[0].is_c) else None
+        check(_lib.lib().unflow_inference_input_frames(ptr(frames), ptr(desc), self.B, Hmax, Wmax, self.H, self.W, ptr(self.x0[1:]),
+                                                       self.mean_host, _lib.planes_of(pl), self.stream()), "inference_input_frames")
+
+    def set_frames(self, frames, carry=0):
+        """The eager form of one replay's input (tests, tools): carry > 0 first moves row `carry` to row 0, then frames
+        [k <= B, H, W, 3] float32 in [0, 255] become rows [1, k + 1) (the rest of the rows: zeros).  Pair i = (row i, row i + 1)
+        is a pair of the clip when both rows hold its frames."""
+        frames = torch.as_tensor(frames).to(device=self.dev, dtype=torch.float32).contiguous()
+        k = frames.shape[0]
+        if not 1 <= k <= self.B or tuple(frames.shape[1:]) != (self.H, self.W, 3):
+            raise ValueError("set_frames: expected 1..%d frames [%d,%d,3], got %s" % (self.B, self.H, self.W, tuple(frames.shape)))
+        if not 0 <= int(carry) <= self.B:
+            raise ValueError("set_frames: carry must be a row in [0, %d]" % self.B)
+        tab = torch.zeros(self.B * 8 + 4, dtype=torch.int32)
+        tab[:8 * k].view(k, 8)[:, 0] = self.H
+        tab[:8 * k].view(k, 8)[:, 1] = self.W
+        tab[8 * self.B] = int(carry)
+        self._seq_tab = tab.to(self.dev)
+        staged = torch.zeros(self.B, self.H, self.W, 3, device=self.dev)
+        staged[:k] = frames
+        self.sequence_carry(self._seq_tab[8 * self.B:])
+        self.sequence_input(staged, self._seq_tab, self.H, self.W)
 
     def _no_training(self, what):
         if self.inference:

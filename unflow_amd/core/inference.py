@@ -22,6 +22,17 @@ visual=True: the graph ends with the pictures of eval_gui.py's window (csrc/visu
 
     unflow_inference_visual      staged frames, frame-size flow, staged ground truth -> overlay, brightness error, flow colours,
                                  and with ground truth the KITTI error image and the ground truth's colours
+
+sequence=True: flow along a clip f0 .. fT-1, every frame uploaded once and encoded once.  The engine
+(FlowNetEngine(..., inference=True, sequence=True)) keeps F = B + 1 frame rows, pair i = (row i, row i + 1), and the graph is
+
+    unflow_sequence_carry          row `src` (the previous replay's last frame) -> row 0 of the input and of the tower's outputs
+    unflow_inference_input_frames  up to B new staged frames -> rows [1, F)
+    engine.forward_net()
+    unflow_inference_output        driven by a per-PAIR table: a slot whose two rows do not both hold frames of the clip has h = 0
+
+with the frame table, the pair table and src in one device int32 buffer the host rewrites before each replay (push,
+estimate_sequence, export_sequence; sequence_tables is the host packing).
 """
 import collections
 import itertools
@@ -84,6 +95,42 @@ def pack_desc(shapes, batch, staged=None, nmaps=0, u8=False):
     return d
 
 
+def sequence_tables(shape, k, batch, carry, u8=False):
+    """The device tables of one sequence replay, one int32 array [16 * batch + 4]: the frame table [batch][8] (pack_desc: the k
+    new frames of size `shape` in rows 1 .. k of the engine, slots [0, k)), the pair table [batch][8] (slot i = rows i, i + 1:
+    valid when both hold frames of this clip — slot 0 needs a carried frame, slot i >= 1 needs i + 1 <= k) and the carry source
+    (row of the previous replay's last frame; 0: a clip's first replay, nothing carried).  Returns (table, slots of the valid
+    pairs in order, the next replay's carry source = k)."""
+    batch, k, carry = int(batch), int(k), int(carry)
+    if not 1 <= k <= batch:
+        raise ValueError("a sequence replay takes 1 to %d new frames, got %d" % (batch, k))
+    if not 0 <= carry <= batch:
+        raise ValueError("the carry source is a row in [0, %d], got %d" % (batch, carry))
+    tab = np.zeros(16 * batch + 4, dtype=np.int32)
+    tab[:8 * batch] = pack_desc([shape] * k, batch, u8=u8).reshape(-1)
+    valid = [i for i in range(batch) if i + 1 <= k and (i > 0 or carry > 0)]
+    pair = np.zeros((batch, 8), dtype=np.int32)
+    for i in valid:
+        pair[i] = (int(shape[0]), int(shape[1]), 0, 0, 0, int(bool(u8)), 0, 0)
+    tab[8 * batch:16 * batch] = pair.reshape(-1)
+    tab[16 * batch] = carry
+    return tab, valid, k
+
+
+def sequence_replays(num_frames, batch, shape=(1, 1), u8=False):
+    """The replays of a clip of num_frames frames pushed `batch` at a time (estimate_sequence's plan): a list of
+    (first new frame, k, table, valid pair slots).  Fewer than two frames give no pair: ValueError."""
+    if int(num_frames) < 2:
+        raise ValueError("a clip needs at least two frames, got %d" % num_frames)
+    out, carry = [], 0
+    for n0 in range(0, int(num_frames), int(batch)):
+        k = min(int(batch), int(num_frames) - n0)
+        tab, valid, nxt = sequence_tables(shape, k, batch, carry, u8)
+        out.append((n0, k, tab, valid))
+        carry = nxt
+    return out
+
+
 def example_stream(batch_iter):
     """Examples of what KITTIInput.input_{train,test}_{2012,2015}() yields, one tuple per example: batches of
     (im1, im2, input_shape[, flow_occ, mask_occ, flow_noc, mask_noc]) or the 2-map form (..., flow_gt, mask)."""
@@ -112,8 +159,10 @@ class _Slot:
     def __init__(self, est):
         B, Hm, Wm = est.B, est.Hmax, est.Wmax
         pin = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, pin_memory=True)   # noqa: E731
-        self.frames = pin(2 * B * Hm * Wm * 3 * 4, dtype=torch.uint8)        # fp32-sized; uint8 frames use the first quarter
+        nfr = 1 if est.sequence else 2                                       # sequence: B new frames per replay, not 2B
+        self.frames = pin(nfr * B * Hm * Wm * 3 * 4, dtype=torch.uint8)      # fp32-sized; uint8 frames use the first quarter
         self.desc = pin(B, 8, dtype=torch.int32)
+        self.tab = pin(16 * B + 4, dtype=torch.int32) if est.sequence else None   # sequence_tables
         self.gt_flow = self.gt_mask = None
         self.flow = pin(B, Hm, Wm, 2)
         self.u16 = pin(B, Hm, Wm, 3, dtype=torch.int16)
@@ -146,10 +195,18 @@ class FlowEstimator:
     network size net_size = (H, W) (divisible by 64), frames of any size up to max_frame (default: net_size).
     bidirectional: also the backward flow and the forward-backward occlusion masks (estimate_bidirectional, the occlusion
     scores of evaluate, export's backward / occlusion files).  visual: also the 8-bit pictures of every batch (visualize,
-    export(visual=True))."""
+    export(visual=True)).
+    sequence: the estimator of a clip — reset / push / estimate_sequence / export_sequence: the flow from every frame to the
+    next, each frame uploaded and encoded once; the pair methods (estimate, evaluate, export, ...) then raise RuntimeError, as
+    the sequence methods do on a pair estimator.  Not with bidirectional (the backward pair's first frame is row i + 1: the
+    decoder's skip connection is no longer row-aligned) nor visual (that kernel reads the [2][B] frame layout)."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
-                 visual=False):
+                 visual=False, sequence=False):
+        if sequence and (bidirectional or visual):
+            raise ValueError("FlowEstimator: sequence=True is one-direction and without pictures (bidirectional / visual "
+                             "sequence mode is not built)")
+        self.sequence = bool(sequence)
         self.params = dict(params)
         self.B = int(batch)
         self.H, self.W = (int(v) for v in net_size)
@@ -160,15 +217,17 @@ class FlowEstimator:
         self.visual = bool(visual)
         eng_params = {k: v for k, v in self.params.items() if k.endswith('_weight') or k in ENGINE_KEYS}
         self.engine = FlowNetEngine(self.B, self.H, self.W, params=eng_params or None, device=self.dev, seed=None,
-                                    inference=True, bidirectional=self.bidirectional)
+                                    inference=True, bidirectional=self.bidirectional, sequence=self.sequence)
         e = self.engine
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         L = _lib.lib()
         with torch.cuda.device(self.dev):
             z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.dev)   # noqa: E731
-            self.frames = z(2 * B * Hm * Wm * 3 * 4, dtype=torch.uint8)
+            self.frames = z((1 if self.sequence else 2) * B * Hm * Wm * 3 * 4, dtype=torch.uint8)
             self.desc = z(B, 8, dtype=torch.int32)
-            self.gt_flow, self.gt_mask = z(2, B, Hm, Wm, 2), z(2, B, Hm, Wm)
+            # sequence: frame table, pair table and carry source in one buffer (sequence_tables); no ground truth
+            self.tab = z(16 * B + 4, dtype=torch.int32) if self.sequence else None
+            self.gt_flow, self.gt_mask = (None, None) if self.sequence else (z(2, B, Hm, Wm, 2), z(2, B, Hm, Wm))
             self.out_flow = z(B, Hm, Wm, 2)
             self.out_u16 = z(B, Hm, Wm, 3, dtype=torch.int16)
             nb = int(L.unflow_inference_output_blocks(Hm, Wm))
@@ -194,6 +253,9 @@ class FlowEstimator:
         self.graph = None
         self.global_step = None
         self._dims = None             # the staged (KITTIInput) frame size of the current evaluate / export pass
+        self._carry = 0               # sequence: the row that holds the clip's last frame (0: none yet)
+        self._clip = None             # sequence: (h, w, dtype is uint8) of the clip's frames
+        self._seq_k = 0               # sequence: replays submitted (the pinned slot alternates)
 
     # ------------------------------------------------------------------------------------------ parameters
     @classmethod
@@ -225,6 +287,8 @@ class FlowEstimator:
         e = self.engine
         L = _lib.lib()
         st = e.stream()
+        if self.sequence:
+            return self._launch_sequence()
         check(L.unflow_inference_input(ptr(self.frames), ptr(self.desc), self.B, self.Hmax, self.Wmax, self.H, self.W,
                                        ptr(e.x0), e.mean_host, _lib.planes_of(self.in_planes), st), "inference_input")
         e.forward_net()
@@ -239,6 +303,18 @@ class FlowEstimator:
             check(L.unflow_inference_visual(ptr(self.frames), ptr(self.desc), self.B, self.Hmax, self.Wmax, self.H, self.W,
                                             ptr(self.out_flow), ptr(self.gt_flow), ptr(self.gt_mask), ptr(self.vis_shown),
                                             ptr(self.vis_max), ptr(self.vis), None, st), "inference_visual")
+
+    def _launch_sequence(self):
+        """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds)."""
+        e, B = self.engine, self.B
+        L = _lib.lib()
+        e.sequence_carry(self.tab[16 * B:])
+        e.sequence_input(self.frames, self.tab, self.Hmax, self.Wmax)
+        e.forward_net()
+        f = self.flow_src
+        check(L.unflow_inference_output(ptr(f), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W,
+                                        ptr(self.tab[8 * B:]), B, self.Hmax, self.Wmax, ptr(self.out_flow), ptr(self.out_u16), None,
+                                        None, None, None, None, None, e.stream()), "inference_output")
 
     def _launch_backward(self, f, st):
         L = _lib.lib()
@@ -259,6 +335,8 @@ class FlowEstimator:
             e.refresh_weight_planes(force=True)
             e.planes_external = True          # the weights are static: the graph does not re-split them
             self._launch()                    # eager pass first: grows the shared workspaces outside the capture
+            # (sequence: the eager pass and the first replay both run the carry; the graph is built by an estimator's first
+            # replay ever, whose carry source is 0 — a no-op both times)
             torch.cuda.current_stream(self.dev).synchronize()
             s = torch.cuda.Stream(self.dev)
             s.wait_stream(torch.cuda.current_stream(self.dev))
@@ -371,6 +449,15 @@ class FlowEstimator:
         return slot, shapes, nmaps, exs
 
     # ------------------------------------------------------------------------------------------ public API
+    def _pair_mode(self, what):
+        if self.sequence:
+            raise RuntimeError("%s: a sequence estimator takes the frames of a clip (push, estimate_sequence, "
+                               "export_sequence); build a pair estimator without sequence=True" % what)
+
+    def _sequence_mode(self, what):
+        if not self.sequence:
+            raise RuntimeError("%s: a pair estimator; build it with FlowEstimator(..., sequence=True)" % what)
+
     @staticmethod
     def _pairs(frames1, frames2, what):
         if len(frames1) != len(frames2):
@@ -389,6 +476,7 @@ class FlowEstimator:
     def estimate(self, frames1, frames2):
         """Flow of every pair (frames1[i] -> frames2[i]): frames [h_i, w_i, 3] uint8 or float32 in [0, 255], any size up to
         max_frame (both frames of a pair the same size).  Returns a list of [h_i, w_i, 2] float32 arrays."""
+        self._pair_mode('estimate')
         exs = self._pairs(frames1, frames2, 'estimate')
         out = []
         for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B)):
@@ -399,6 +487,7 @@ class FlowEstimator:
     def estimate_bidirectional(self, frames1, frames2):
         """estimate's pairs in both directions: one BidirectionalFlow(flow_fw, flow_bw, occ_fw, occ_bw) per pair — the flows
         [h_i, w_i, 2] float32 (flow_fw = estimate's flow), the masks [h_i, w_i] bool: losses.occlusion(flow_fw, flow_bw)."""
+        self._pair_mode('estimate_bidirectional')
         if not self.bidirectional:
             raise RuntimeError("estimate_bidirectional: a one-direction estimator; build it with FlowEstimator(..., "
                                "bidirectional=True)")
@@ -415,6 +504,7 @@ class FlowEstimator:
         eval_gui.py:199-204 (:160-165): (0.5 im1 + 0.5 im2) / 255 and |im1 - image_warp(im2, flow)| / 255 on the frames as the
         reference shows them (resized to the network's size and back), and flow_to_color(flow) with max_flow per pair; bytes
         rounded to nearest."""
+        self._pair_mode('visualize')
         if not self.visual:
             raise RuntimeError("visualize: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
         exs = self._pairs(frames1, frames2, 'visualize')
@@ -428,6 +518,7 @@ class FlowEstimator:
         """The pictures of what KITTIInput.input_{train,test}_{2012,2015}() yields, one dict per example in iteration order:
         VISUAL_IMAGES' names -> uint8 [h, w, 3]; 'error' and 'gt' only when the input carries ground truth (two maps:
         flow_error_image(flow, flow_occ, mask_occ, mask_noc) and flow_to_color(flow_occ, mask_occ); one map: mask_noc = ones)."""
+        self._pair_mode('pictures')
         if not self.visual:
             raise RuntimeError("pictures: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
         it = example_stream(batch_iter)
@@ -447,6 +538,7 @@ class FlowEstimator:
         `names` order).  num: at most that many examples.
         A bidirectional estimator on two-map input adds occlusion_scores' occ/precision, occ/recall and occ/F1 (%, pooled
         over all examples) and occ_counts (per example [tp, fp, fn])."""
+        self._pair_mode('evaluate')
         names, rows, occ_rows = None, [], []
         it = example_stream(batch_iter)
         if num is not None:
@@ -510,6 +602,7 @@ class FlowEstimator:
         eval_gui.py:248-254 writes the brightness error into _flow.png and the flow colours into _err.png and never writes the
         error image; the names' evident meaning is followed here."""
         from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
+        self._pair_mode('export')
         if fmt not in ('png', 'flo'):
             raise ValueError("export: fmt must be 'png' or 'flo'")
         if (backward or occlusion) and not self.bidirectional:
@@ -552,4 +645,120 @@ class FlowEstimator:
                         write_png_rgb8(path, vis[k, i, :h, :w])
                         paths.append(path)
                 n += 1
+        return paths
+
+    # ------------------------------------------------------------------------------------------ sequence mode
+    def reset(self):
+        """Start a new clip: the next push has no previous frame (nothing is carried across reset)."""
+        self._sequence_mode('reset')
+        self._carry, self._clip = 0, None
+
+    def _clip_frames(self, frames, what):
+        out = []
+        for a in frames:
+            a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("%s: a frame is [h, w, 3], got %s" % (what, a.shape))
+            if a.dtype != np.uint8:
+                a = a.astype(np.float32, copy=False)
+            clip = (a.shape[0], a.shape[1], a.dtype == np.uint8)
+            if clip[0] > self.Hmax or clip[1] > self.Wmax:
+                raise ValueError("%s: a %dx%d frame exceeds max_frame %dx%d" % (what, clip[0], clip[1], self.Hmax, self.Wmax))
+            if self._clip is None:
+                self._clip = clip
+            elif clip != self._clip:
+                raise ValueError("%s: the frames of a clip have one size and type (%s, then %s); reset() starts a new clip"
+                                 % (what, self._clip, clip))
+            out.append(a)
+        return out
+
+    def _submit_sequence(self, frames, want=('flow',)):
+        """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns (slot, valid
+        pair slots)."""
+        B, Hm, Wm = self.B, self.Hmax, self.Wmax
+        if not 1 <= len(frames) <= B:
+            raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
+        frames = self._clip_frames(frames, 'push')
+        h, w, u8 = self._clip
+        slot = self._slot(self._seq_k)
+        self._seq_k += 1
+        slot.wait()
+        nbytes = B * Hm * Wm * 3 * (1 if u8 else 4)
+        fr = slot.frames[:nbytes].numpy().view(np.uint8 if u8 else np.float32).reshape(B, Hm, Wm, 3)
+        for i, a in enumerate(frames):
+            fr[i, :h, :w] = a
+        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8)
+        slot.tab.numpy()[:] = tab
+        with torch.cuda.device(self.dev):
+            cur = torch.cuda.current_stream(self.dev)
+            self.tab.copy_(slot.tab, non_blocking=True)
+            self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
+            self._run()
+            if 'flow' in want:
+                slot.flow.copy_(self.out_flow, non_blocking=True)
+            if 'u16' in want:
+                slot.u16.copy_(self.out_u16, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+        slot.event = ev
+        slot.pending = ([(h, w)] * len(valid), 0)
+        return slot, valid
+
+    def push(self, frames):
+        """The next 1..B frames of the clip ([h, w, 3] uint8 or float32 in [0, 255], all of the clip's size).  Returns one
+        [h, w, 2] float32 flow per new pair, in order: from the frame before each new frame to it — len(frames) flows, or
+        len(frames) - 1 for the first push after reset() (its first frame has no predecessor)."""
+        self._sequence_mode('push')
+        slot, valid = self._submit_sequence(list(frames))
+        slot.wait()
+        h, w, _ = self._clip
+        fl = slot.flow.numpy()
+        return [fl[i, :h, :w].copy() for i in valid]
+
+    def _pipeline_sequence(self, frames, want):
+        """reset, then pipelined pushes of B frames: yields (slot, valid pair slots) per replay; replay k + 1 is staged and
+        queued before replay k is handed out."""
+        self.reset()
+        prev, total = None, 0
+        for chunk in chunks(frames, self.B):
+            total += len(chunk)
+            cur = self._submit_sequence(chunk, want)
+            if prev is not None:
+                prev[0].wait()
+                yield prev
+            prev = cur
+        if total < 2:
+            raise ValueError("a clip needs at least two frames, got %d" % total)
+        prev[0].wait()
+        yield prev
+
+    def estimate_sequence(self, frames):
+        """Flow along a clip: frames = T >= 2 frames (a list or an iterator; [h, w, 3] uint8 or float32 in [0, 255], one size)
+        -> T - 1 flows [h, w, 2] float32, frame n -> frame n + 1."""
+        self._sequence_mode('estimate_sequence')
+        out = []
+        for slot, valid in self._pipeline_sequence(frames, ('flow',)):
+            h, w, _ = self._clip
+            fl = slot.flow.numpy()
+            out += [fl[i, :h, :w].copy() for i in valid]
+        return out
+
+    def export_sequence(self, frames, out_dir, fmt='png'):
+        """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
+        -> frame n + 1), with export's writers.  Returns the written paths."""
+        from .input import write_flo, write_kitti_flow_png
+        self._sequence_mode('export_sequence')
+        if fmt not in ('png', 'flo'):
+            raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
+        os.makedirs(out_dir, exist_ok=True)
+        paths = []
+        for slot, valid in self._pipeline_sequence(frames, ('u16',) if fmt == 'png' else ('flow',)):
+            h, w, _ = self._clip
+            for i in valid:
+                path = os.path.join(out_dir, '%06d_10.%s' % (len(paths), fmt))
+                if fmt == 'png':
+                    write_kitti_flow_png(path, slot.u16.numpy()[i, :h, :w].view(np.uint16))
+                else:
+                    write_flo(path, slot.flow.numpy()[i, :h, :w])
+                paths.append(path)
         return paths

@@ -8,6 +8,8 @@
 //   network pixel: the TF1 legacy bilinear resample of the sample's (h, w) frame region (origin (y0, x0) in its staging
 //   row; outside the buffer reads as zero: resize_input's crop / pad of the KITTIInput layout), /255, minus the channel mean
 //   (unflow_prepare_image_pair's arithmetic); rows [0, B) = im1, [B, 2B) = im2, plus the operand planes of a FlowNetC's conv1.
+// unflow_inference_input_frames: the same per pixel for sequence mode's layout, staged frames [F][Hmax][Wmax][3] -> F consecutive
+//   rows of the network input (and of conv1's planes) from the row pointer the caller passes (csrc/sequence.hip: the carry).
 // unflow_inference_output: the last network's flow2 (or flow0 with full_res) -> the frame-size flow of every sample: the
 //   composed resize (final_flows()' resize * 20 to (H, W), then resize_output_flow's resize to (h, w) and per-axis rescale)
 //   evaluated at the four points each frame pixel needs, with csrc/resize_tf1.h's expression: bit-identical to the chained
@@ -53,6 +55,30 @@ __global__ __launch_bounds__(256) void inference_input_kernel(const void* __rest
                : input_pixel(reinterpret_cast<const float*>(frames) + off, d, Hmax, Wmax, H, W, oy, ox, m0, m1, m2);
     }
     reinterpret_cast<float4*>(net4)[i] = v;            // one 16-byte store; planes: one 8-byte store per plane
+    igemm::store_planes4(pl, (size_t)i, 0, v);
+  }
+}
+
+// Sequence mode: one frame per row.  Row r of the launch is frame r of the staging buffer with desc slot r; index i of net4 /
+// pl counts from the row pointer the caller passed, so nothing outside the F rows is touched.  The value of a pixel is
+// inference_input_kernel's expression (input_pixel, store_planes4): a row is bit-identical to the pair kernel's row.
+__global__ __launch_bounds__(256) void inference_input_frames_kernel(const void* __restrict__ frames, const int* __restrict__ desc,
+                                                                     int F, int Hmax, int Wmax, int H, int W,
+                                                                     float* __restrict__ net4, igemm::PlaneOut pl, float m0, float m1,
+                                                                     float m2) {
+  const long per = (long)H * W, n = (long)F * per;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / per;                          // [0, F)
+    const int p = (int)(i - row * per);
+    const int oy = p / W, ox = p - oy * W;
+    const FrameDesc d = load_desc(desc, (int)row);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (d.h > 0 && d.w > 0) {
+      const long off = row * (long)Hmax * Wmax * 3;
+      v = d.u8 ? input_pixel(reinterpret_cast<const unsigned char*>(frames) + off, d, Hmax, Wmax, H, W, oy, ox, m0, m1, m2)
+               : input_pixel(reinterpret_cast<const float*>(frames) + off, d, Hmax, Wmax, H, W, oy, ox, m0, m1, m2);
+    }
+    reinterpret_cast<float4*>(net4)[i] = v;
     igemm::store_planes4(pl, (size_t)i, 0, v);
   }
 }
@@ -275,6 +301,26 @@ UNFLOW_API int unflow_inference_input(const void* frames, const int* desc, int B
   const float m0 = mean3[0] / 255.0f, m1 = mean3[1] / 255.0f, m2 = mean3[2] / 255.0f;
   inference_input_kernel<<<stream_grid(2L * B * H * W), 256, 0, as_stream(stream)>>>(frames, desc, B, Hmax, Wmax, H, W, net_in4, pl,
                                                                                     m0, m1, m2);
+  return launch_status();
+}
+
+UNFLOW_API int unflow_inference_input_frames(const void* frames, const int* desc, int F, int Hmax, int Wmax, int H, int W,
+                                             float* net_in4, const float* mean3, const unflow_planes* net_pl,
+                                             unflow_stream_t stream) {
+  if (!frames || !desc || !net_in4 || !mean3) return UNFLOW_ERR_NULL;
+  if (F <= 0 || Hmax <= 0 || Wmax <= 0 || H <= 0 || W <= 0) return UNFLOW_ERR_SHAPE;
+  igemm::PlaneOut pl{};
+  if (net_pl && net_pl->base) {
+    if ((net_pl->n_planes != 1 && net_pl->n_planes != 3) || net_pl->ld < 4 || net_pl->ld % 4 != 0 ||
+        (reinterpret_cast<uintptr_t>(net_pl->base) & 7) != 0)
+      return UNFLOW_ERR_UNSUPPORTED;
+    pl.base = reinterpret_cast<unsigned short*>(net_pl->base);
+    pl.plane_stride = net_pl->plane_stride;
+    pl.ld = net_pl->ld; pl.lo = 0; pl.hi = 4; pl.n_planes = net_pl->n_planes;
+  }
+  const float m0 = mean3[0] / 255.0f, m1 = mean3[1] / 255.0f, m2 = mean3[2] / 255.0f;
+  inference_input_frames_kernel<<<stream_grid((long)F * H * W), 256, 0, as_stream(stream)>>>(frames, desc, F, Hmax, Wmax, H, W,
+                                                                                            net_in4, pl, m0, m1, m2);
   return launch_status();
 }
 

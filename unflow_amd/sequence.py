@@ -1,0 +1,105 @@
+"""python -m unflow_amd.sequence: the flow along a clip of frames with a trained experiment — every frame uploaded and encoded
+once (core/inference.FlowEstimator(..., sequence=True)).
+
+    python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W]
+
+The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  The
+experiment's config and latest checkpoint are found as python -m unflow_amd.evaluate finds them.  Files go to <--out>/NAME/:
+%06d_10.png (KITTI 16-bit flow) or, with --flo, %06d_10.flo."""
+import argparse
+import os
+import sys
+
+
+def read_frame(path):
+    """One 8-bit RGB PNG as uint8 [h, w, 3] (the project's own decoder); anything else: ValueError naming the file."""
+    import numpy as np
+    from .core.input import decode_png
+    try:
+        with open(path, 'rb') as f:
+            a = decode_png(f.read())
+    except Exception as err:                      # a broken file: say which one
+        raise ValueError("%s: not a readable PNG (%s)" % (path, err))
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("%s: not an 8-bit RGB PNG (%s %s)" % (path, a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def frame_files(folder):
+    return [os.path.join(folder, n) for n in sorted(os.listdir(folder)) if n.lower().endswith('.png')]
+
+
+def png_size(path):
+    """(h, w) from a PNG's IHDR, without decoding it."""
+    import struct
+    with open(path, 'rb') as f:
+        head = f.read(24)
+    if len(head) < 24 or head[:8] != b'\x89PNG\r\n\x1a\n':
+        raise ValueError("%s: not a PNG file" % path)
+    w, h = struct.unpack('>II', head[16:24])
+    return h, w
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m unflow_amd.sequence', description=__doc__.split('\n')[0])
+    ap.add_argument('--ex', required=True, help='experiment name')
+    ap.add_argument('--frames', required=True, metavar='DIR', help='folder of 8-bit RGB PNG frames (sorted order)')
+    ap.add_argument('--out', default='../out', metavar='DIR', help='output root: files go to <out>/<ex>/')
+    ap.add_argument('--flo', action='store_true', help='write %%06d_10.flo (default: KITTI 16-bit %%06d_10.png)')
+    ap.add_argument('--batch', type=int, default=4, metavar='B', help='new frames per graph replay')
+    ap.add_argument('--net_size', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
+                    help='network input size (multiples of 64)')
+    ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
+    return ap
+
+
+def parse_args(argv=None):
+    """Parsed flags plus a.files; a folder that holds no clip is an argparse error (SystemExit, status 2)."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    if a.batch <= 0:
+        ap.error("--batch must be positive")
+    if a.net_size[0] % 64 or a.net_size[1] % 64 or min(a.net_size) <= 0:
+        ap.error("--net_size: H and W must be positive multiples of 64")
+    if not os.path.isdir(a.frames):
+        ap.error("--frames %s: not a folder" % a.frames)
+    a.files = frame_files(a.frames)
+    if len(a.files) < 2:
+        ap.error("--frames %s: a clip needs at least two PNG frames, found %d%s"
+                 % (a.frames, len(a.files), (" (%s)" % a.files[0]) if a.files else ""))
+    try:
+        sizes = [png_size(p) for p in a.files]
+    except ValueError as err:
+        ap.error(str(err))
+    for p, s in zip(a.files, sizes):
+        if s != sizes[0]:
+            ap.error("%s: a %dx%d frame in a clip of %dx%d frames (%s)" % (p, s[0], s[1], sizes[0][0], sizes[0][1], a.files[0]))
+    a.frame_size = sizes[0]
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from .core.inference import FlowEstimator
+    from .core.util import config_dict, convert_input_strings
+    from .evaluate import experiment_paths
+    cfg_path, ckpt_dir = experiment_paths(a.ex, a.config)
+    config = config_dict(cfg_path)
+    params = dict(config.get('train', {}))
+    convert_input_strings(params, config_dict(a.config).get('dirs', {}))
+    params.update(config.get('train_kitti', {}))
+    est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
+                                        sequence=True)
+    out_dir = os.path.join(a.out, a.ex)
+    print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
+                                                           a.frames))
+    try:
+        paths = est.export_sequence((read_frame(p) for p in a.files), out_dir, fmt='flo' if a.flo else 'png')
+    except ValueError as err:
+        raise SystemExit("Error: %s" % err)
+    print("wrote %d files to %s" % (len(paths), out_dir))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
