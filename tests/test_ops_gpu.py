@@ -310,6 +310,64 @@ def test_warp_linearity_full_size(dev):
     assert torch.equal(ident, a)     # zero flow is the identity, bit-exact
 
 
+@pytest.mark.parametrize("kind", ["normal", "oob"])
+def test_warps_chunked_tile_walk_vs_oracle(kind, dev, oracle_lib):
+    """The warps past one grid pass, against the oracle at the small-shape tolerances (1e-6 forward, 1e-5 gradients, indices
+    exact).  2 x 333 x 795 is 529,470 pixels in 2184 tiles of 64 x 4, over the 2048-block cap: tile_first()..tile_last() hands
+    every block a chunk of 2 tiles and leaves the last 956 blocks an empty one, the streaming kernels (indices) make a second
+    grid-stride pass, and both axes are ragged against the tile."""
+    from unflow_amd import ops
+    from unflow_amd.core.image_warp import image_warp, image_warp_indices
+    from oracle import model_ref as M
+    rs = np.random.RandomState(31)
+    B, H, W = 2, 333, 795
+    assert B * H * W > 2048 * 256 and B * -(-H // 4) * -(-W // 64) == 2184
+    fl = _flows(rs, B, H, W, kind)
+    worst, bounds = {}, []
+
+    def closer(name, a, b, tol):
+        a = a.detach().cpu().numpy()
+        worst[name] = float(np.max(np.abs(a - b) / (tol + tol * np.abs(b))))      # <= 1 passes np.testing.assert_allclose
+        close(a, b, tol)
+
+    for C in (1, 3):
+        im = rs.rand(B, H, W, C).astype(np.float32)
+        go = rs.randn(B, H, W, C).astype(np.float32)
+        tim, tfl = t(im, dev), t(fl, dev).requires_grad_()
+        out = ops.backward_warp(tim, tfl)
+        closer("backward_warp C%d" % C, out, oracle_lib.backward_warp(im, fl), 1e-6)
+        out.backward(t(go, dev))
+        closer("backward_warp d_flow C%d" % C, tfl.grad, oracle_lib.backward_warp_grad(go, im, fl), 1e-5)
+    assert np.array_equal(ops.backward_warp_indices(t(fl, dev)).cpu().numpy(), oracle_lib.backward_warp_indices(fl))
+    for C in (2, 3):
+        im = rs.rand(B, H, W, C).astype(np.float32)
+        go = rs.randn(B, H, W, C).astype(np.float32)
+        tim, tfl = t(im, dev).requires_grad_(), t(fl, dev).requires_grad_()
+        out = image_warp(tim, tfl)
+        ref, idx = oracle_lib.image_warp(im, fl, return_indices=True)
+        closer("image_warp C%d" % C, out, ref, 1e-6)
+        assert np.array_equal(image_warp_indices(tim.detach(), tfl.detach()).cpu().numpy(), idx)
+        out.backward(t(go, dev))
+        d_im, d_fl = oracle_lib.image_warp_grad(go, im, fl)
+        # d_im is a scatter-add: where the torn field clamps ~600 sources onto one corner pixel, the order of the fp32 adds
+        # (float atomics here, sequential in the C oracle) decides the 5th digit, and the oracle's own distance from fp64 passes
+        # 1e-5.  Compared with fp64 autograd of the oracle's image_warp at max(1e-5, 2 x the C oracle's own error against it).
+        t64, f64 = torch.tensor(im).double().requires_grad_(), torch.tensor(fl).double()
+        M.image_warp(t64, f64).backward(torch.tensor(go).double())
+        r64 = t64.grad.numpy()
+        own = float(np.max(np.abs(d_im - r64) / (1.0 + np.abs(r64))))
+        tol = max(1e-5, 2.0 * own)
+        bounds.append("d_im C%d: fp32 oracle's own error %.1e -> %s" % (C, own, "1e-5" if tol == 1e-5 else "2 x own = %.1e" % tol))
+        closer("image_warp d_im C%d" % C, tim.grad, r64, tol)
+        closer("image_warp d_flow C%d" % C, tfl.grad, d_fl, 1e-5)
+    tfl = t(fl, dev).requires_grad_()
+    out = ops.forward_warp(tfl, deterministic=True)
+    go = rs.randn(B, H, W, 1).astype(np.float32)
+    out.backward(t(go, dev))
+    closer("forward_warp d_flow", tfl.grad, oracle_lib.forward_warp_grad(go, fl), 1e-5)
+    print("%s: worst |err| / (tol + tol |ref|): %s; %s" % (kind, ", ".join("%s %.2f" % kv for kv in worst.items()), "; ".join(bounds)))
+
+
 def test_empty_batch_is_a_no_op(dev):
     """Empty inputs (B = 0): outputs of the right shape, nothing launched, no error."""
     from unflow_amd import ops
