@@ -675,6 +675,36 @@ int unflow_inference_visual(const void* frames, const int* desc, int B, int Hmax
                             const float* gt_flow, const float* gt_mask, float* shown, unsigned* max_bits, unsigned char* out_u8,
                             float* out_f32, unflow_stream_t stream);
 
+/* ===================================================================== */
+/* PNG decode on the device (csrc/png_decode.hip, core/png_device.py)      */
+/* ===================================================================== */
+
+/* Per-image geometry of both entries: a DEVICE table desc[n][8] of int64 =
+ *   {src, dst, h, w, bpp, sample_bytes, oy, ox}: byte offset of the image's inflated stream in `raw` (h rows of 1 + w * bpp
+ *   bytes, the filter byte 0..4 first), byte offset of its decoded bytes in `decoded` (h * w * bpp, tightly packed), its size,
+ *   bytes per pixel (1, 2, 3, 4, 6 or 8: 8 / 16-bit grey, grey + alpha, RGB, RGBA), bytes per sample (1 or 2; channels = bpp /
+ *   sample_bytes) and the crop origin of unflow_png_to_batch.  unflow_png_unfilter reads the first five fields,
+ *   unflow_png_to_batch all but the first.  Images of one launch may differ in every field.  An entry that does not fit its
+ *   buffers (or whose crop leaves the frame) is skipped by the kernels; the caller validates the table, and the filter bytes,
+ *   on the host (core/png_device.py). */
+
+/* Rows of one image that unflow_png_unfilter decodes together (its skewed wavefront; bands of this many rows run one after
+ * another).  Host only. */
+int unflow_png_unfilter_rows(void);
+
+/* PNG scanline reconstruction (filters None, Sub, Up, Average, Paeth) of n images in one launch, one workgroup per image:
+ * raw [raw_bytes] -> decoded [decoded_bytes], both DEVICE buffers, geometry from desc.  Exact: every byte equals the PNG
+ * specification's reconstruction (mod 256, Average on the 9-bit sum, Paeth ties in the order left, up, upper left). */
+int unflow_png_unfilter(const unsigned char* raw, long raw_bytes, unsigned char* decoded, long decoded_bytes, const long* desc,
+                        int n, unflow_stream_t stream);
+
+/* decoded frames (unflow_png_unfilter's output) -> out [n][H][W][3] fp32: image i is the (H, W) window at (oy, ox) of frame i
+ * (zero origin with (H, W) = (h, w): the whole frame) under read_png_image's channel rule — grey is replicated to RGB, alpha is
+ * dropped, a 16-bit sample gives its high byte.  mean3 (a HOST pointer, may be NULL = no normalisation): out = (v - mean3[c]) /
+ * stddev in fp32 with a correctly rounded division, bit-identical to numpy's float32 (a - mean) / stddev. */
+int unflow_png_to_batch(const unsigned char* decoded, long decoded_bytes, const long* desc, int n, int H, int W,
+                        const float* mean3, float stddev, float* out, unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

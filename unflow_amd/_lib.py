@@ -45,6 +45,7 @@ def lib():
         _lib.unflow_weight_planes_elems.restype = ctypes.c_size_t
         _lib.unflow_forward_warp_workspace_bytes.restype = ctypes.c_size_t
         _lib.unflow_option_names.restype = ctypes.c_char_p
+        _lib.unflow_png_unfilter_rows.restype = ctypes.c_int
         _apply_env_options(_lib)
     return _lib
 
@@ -123,6 +124,14 @@ def planes_of(pl, scale=0.0):
     if pl is None:
         return None
     return ctypes.byref(Planes(pl.data_ptr(), pl.stride(0), pl.stride(-2), pl.shape[0], float(scale)))
+
+
+PNG_DESC_FIELDS = 8      # int64 per image of the PNG entries' table (include/unflow_hip.h): src, dst, h, w, bpp, sample_bytes, oy, ox
+
+
+def png_unfilter_rows():
+    """unflow_png_unfilter_rows: rows of an image that unflow_png_unfilter decodes together (host only)."""
+    return int(lib().unflow_png_unfilter_rows())
 
 
 class CarryBuf(ctypes.Structure):

@@ -479,11 +479,19 @@ class Input:
         names = names[len(names) - k:] + names[:len(names) - k]
         return list(zip(names[0::2], names[1::2]))
 
-    def input_raw(self, swap_images=True, sequence=True, needs_crop=True, shift=0, seed=0, center_crop=False, skip=0):
+    def input_raw(self, swap_images=True, sequence=True, needs_crop=True, shift=0, seed=0, center_crop=False, skip=0,
+                  device=None, workers=8, prefetch=2):
         """input_raw (input.py:121-205): an iterator of (image_1, image_2) batches [B,H,W,3] float32.  `shift`: examples to skip
-        at the start — the reference resumes training with shift = batch_size * iterations done (train.py / run.py)."""
+        at the start — the reference resumes training with shift = batch_size * iterations done (train.py / run.py).
+        device: None = numpy batches decoded on the host (RawPairBatches); a GPU device = the same batches, bit for bit, as
+        device tensors decoded by the library's PNG kernels with `workers` inflate threads and `prefetch` batches in flight
+        (core/png_device.py::DevicePairBatches)."""
         pairs = self.raw_pairs(swap_images=swap_images, sequence=sequence, shift=shift, seed=seed, skip=skip)
         print("Training on {} frame pairs.".format(len(pairs) // (2 if swap_images else 1)))
+        if device is not None:
+            from .png_device import DevicePairBatches
+            return DevicePairBatches(pairs, self.batch_size, self.dims, needs_crop, self.normalize, self.mean, self.stddev, seed,
+                                     device=device, workers=workers, prefetch=prefetch)
         return RawPairBatches(pairs, self.batch_size, self.dims, needs_crop, self.normalize, self.mean, self.stddev, seed)
 
     def test_pairs(self, image_dir, hold_out_inv=None):
