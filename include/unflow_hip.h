@@ -705,6 +705,22 @@ int unflow_png_unfilter(const unsigned char* raw, long raw_bytes, unsigned char*
 int unflow_png_to_batch(const unsigned char* decoded, long decoded_bytes, const long* desc, int n, int H, int W,
                         const float* mean3, float stddev, float* out, unflow_stream_t stream);
 
+/* The window entries read the same table with oy, ox SIGNED: output pixel (y, x) of image i, y < Hs, x < Ws, is frame pixel
+ * (y + oy, x + ox) where that lies inside (h, w) and 0 elsewhere — a crop (oy, ox >= 0), the zero padding of
+ * resize_image_with_crop_or_pad (oy = -pad) and any mix of the two per axis.  An entry that does not fit `decoded` (or has
+ * the wrong bpp / sample_bytes) is skipped and its output left untouched; the caller validates on the host.
+ *
+ * unflow_png_to_window: unflow_png_to_batch's channel rule and normalisation on such a window -> out [n][Hs][Ws][3] fp32.  A
+ * padded pixel is 0 BEFORE the normalisation (it comes out as (0 - mean3[c]) / stddev), as Input._preprocess_image pads first. */
+int unflow_png_to_window(const unsigned char* decoded, long decoded_bytes, const long* desc, int n, int Hs, int Ws,
+                         const float* mean3, float stddev, float* out, unflow_stream_t stream);
+
+/* KITTI flow maps, 16-bit RGB only (bpp = 6, sample_bytes = 2): flow [n][Hs][Ws][2] = (u16 - 32768) / 64 of channels 0 and 1,
+ * mask [n][Hs][Ws] = float(channel 2) (the raw sample, as read_kitti_flow_png returns it); both exact in fp32.  A padded pixel
+ * has flow 0 and mask 0. */
+int unflow_png_to_flow_gt(const unsigned char* decoded, long decoded_bytes, const long* desc, int n, int Hs, int Ws, float* flow,
+                          float* mask, unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,8 @@ def lib():
         _lib.unflow_forward_warp_workspace_bytes.restype = ctypes.c_size_t
         _lib.unflow_option_names.restype = ctypes.c_char_p
         _lib.unflow_png_unfilter_rows.restype = ctypes.c_int
+        _lib.unflow_png_to_window.restype = ctypes.c_int
+        _lib.unflow_png_to_flow_gt.restype = ctypes.c_int
         _apply_env_options(_lib)
     return _lib
 

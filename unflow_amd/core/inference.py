@@ -391,19 +391,58 @@ class FlowEstimator:
         slot.desc.numpy()[:] = pack_desc(shapes, B, staged, nmaps, u8)
         return shapes, nbytes
 
-    def _submit(self, k, examples, staged=None, nmaps=0, want=('flow',)):
-        """Stage batch k into its slot, copy it in, run, and queue the copies back; returns the slot."""
+    def _stage_device(self, slot, batch, n, staged, nmaps):
+        """_stage for the first n examples of a batch whose tensors are already on this device (core/png_device.py's
+        iterators): the same descriptor table, and device-to-device copies on the current stream into the fp32 layout of
+        self.frames, self.gt_flow and self.gt_mask with the same zeroing outside the staged region — the buffers the host
+        path would have uploaded.  Returns the frames' shapes."""
+        B, Hm, Wm = self.B, self.Hmax, self.Wmax
+        hs, ws = staged
+        if hs > Hm or ws > Wm:
+            raise ValueError("a staged frame of %dx%d exceeds max_frame %dx%d" % (hs, ws, Hm, Wm))
+        if isinstance(batch[2], torch.Tensor) and batch[2].device.type != 'cpu':
+            raise ValueError("input_shape of a device batch must stay on the host (reading it would wait for the device)")
+        shp = np.asarray(batch[2])
+        shapes = [(int(shp[i][0]), int(shp[i][1])) for i in range(n)]
+        for h, w in shapes:
+            if h > Hm or w > Wm:
+                raise ValueError("a %dx%d frame exceeds max_frame %dx%d" % (h, w, Hm, Wm))
+        slot.desc.numpy()[:] = pack_desc(shapes, B, staged, nmaps, False)
+
+        def put(dst, src):                   # dst [n, Hm, Wm(, c)] <- src [n, hs, ws(, c)]; zero outside
+            dst[:, :hs, :ws].copy_(src, non_blocking=True)
+            if hs < Hm:
+                dst[:, hs:].zero_()
+            if ws < Wm:
+                dst[:, :hs, ws:].zero_()
+        with torch.cuda.device(self.dev):
+            self.desc.copy_(slot.desc, non_blocking=True)
+            fr = self.frames.view(torch.float32).view(2, B, Hm, Wm, 3)
+            for k in range(2):
+                put(fr[k, :n], batch[k][:n])
+            for m in range(nmaps):
+                put(self.gt_flow[m, :n], batch[3 + 2 * m][:n])
+                put(self.gt_mask[m, :n], batch[4 + 2 * m][:n].reshape(n, hs, ws))
+        return shapes
+
+    def _submit(self, k, examples, staged=None, nmaps=0, want=('flow',), device_batch=None):
+        """Stage batch k into its slot, copy it in, run, and queue the copies back; returns the slot.  device_batch: (batch,
+        n) — the first n examples of a batch of device tensors instead of `examples`."""
         slot = self._slot(k)
         slot.wait()                               # the last replay that read this slot's buffers (and its copies back) is done
-        shapes, nbytes = self._stage(slot, examples, staged, nmaps)
+        if device_batch is not None:
+            shapes = self._stage_device(slot, device_batch[0], device_batch[1], staged, nmaps)
+        else:
+            shapes, nbytes = self._stage(slot, examples, staged, nmaps)
         with torch.cuda.device(self.dev):
             cur = torch.cuda.current_stream(self.dev)
-            self.desc.copy_(slot.desc, non_blocking=True)
-            self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
-            if nmaps:
-                gf, gm = slot.gt(self)
-                self.gt_flow[:nmaps].copy_(gf[:nmaps], non_blocking=True)
-                self.gt_mask[:nmaps].copy_(gm[:nmaps], non_blocking=True)
+            if device_batch is None:
+                self.desc.copy_(slot.desc, non_blocking=True)
+                self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
+                if nmaps:
+                    gf, gm = slot.gt(self)
+                    self.gt_flow[:nmaps].copy_(gf[:nmaps], non_blocking=True)
+                    self.gt_mask[:nmaps].copy_(gm[:nmaps], non_blocking=True)
             self._run()
             if 'flow' in want:
                 slot.flow.copy_(self.out_flow, non_blocking=True)
@@ -521,10 +560,7 @@ class FlowEstimator:
         self._pair_mode('pictures')
         if not self.visual:
             raise RuntimeError("pictures: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
-        it = example_stream(batch_iter)
-        if num is not None:
-            it = (ex for i, ex in zip(range(int(num)), it))
-        for slot, shapes, nmaps, _ in self._pipeline_staged(it, ('vis',), lambda exs: (len(exs[0]) - 3) // 2):
+        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, ('vis',), lambda exs: (len(exs[0]) - 3) // 2):
             v = slot.vis.numpy()
             for i, (h, w) in enumerate(shapes):
                 yield {name: v[k, i, :h, :w].copy() for k, name in enumerate(VISUAL_IMAGES) if k < 3 or nmaps}
@@ -540,11 +576,8 @@ class FlowEstimator:
         over all examples) and occ_counts (per example [tp, fp, fn])."""
         self._pair_mode('evaluate')
         names, rows, occ_rows = None, [], []
-        it = example_stream(batch_iter)
-        if num is not None:
-            it = (ex for i, ex in zip(range(int(num)), it))
         want = ('occ_counts',) if self.bidirectional else ()
-        for slot, shapes, nmaps, _ in self._pipeline_staged(it, want, lambda exs: (len(exs[0]) - 3) // 2):
+        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, lambda exs: (len(exs[0]) - 3) // 2):
             if nmaps == 0:
                 raise ValueError("evaluate: the batches carry no ground truth (a test split); use export()")
             if names is None:
@@ -589,6 +622,57 @@ class FlowEstimator:
         batches = chunks(itertools.chain([first], gen), self.B)
         yield from self._pipeline(batches, staged=tuple(self._dims), nmaps_of=nmaps_of, want=want)
 
+    def _on_device(self, batch):
+        t = batch[0]
+        return isinstance(t, torch.Tensor) and t.is_cuda and \
+            t.device == torch.device('cuda', torch.cuda.current_device() if self.dev.index is None else self.dev.index)
+
+    def _pipeline_device(self, batches, num, want, nmaps_of):
+        """_pipeline over batches of device tensors (DeviceEvalBatches): each is consumed as it comes, never re-chunked —
+        its tensors are valid only until the iterator's next next(), and batch k is staged (copies enqueued on the current
+        stream) before batch k + 1 is asked for."""
+        self._dims = None
+        prev, done = None, 0
+        for k, batch in enumerate(batches):
+            if len(batch) not in (3, 5, 7):
+                raise ValueError("a batch is (im1, im2, input_shape) + 0, 1 or 2 (flow, mask) pairs; got %d arrays" % len(batch))
+            n = int(batch[0].shape[0])
+            if n > self.B:
+                raise ValueError("a device batch of %d examples for an estimator of batch %d: device batches are consumed "
+                                 "whole (build the input with batch_size <= %d)" % (n, self.B, self.B))
+            if num is not None:
+                n = min(n, int(num) - done)
+                if n <= 0:
+                    break
+            dims = tuple(int(v) for v in batch[0].shape[1:3])
+            if self._dims is None:
+                self._dims = dims
+            elif dims != tuple(self._dims):
+                raise ValueError("evaluate / export: the input's frames changed size (%s, then %s)" % (self._dims, dims))
+            slot = self._submit(k, None, dims, nmaps_of([batch]), want, device_batch=(batch, n))
+            done += n
+            if prev is not None:
+                yield self._collect(*prev)
+            prev = (slot, None)
+        if prev is not None:
+            yield self._collect(*prev)
+
+    def _staged_input(self, batch_iter, num, want, nmaps_of):
+        """The batches of evaluate / export / pictures: host arrays go example by example through _pipeline_staged; batches of
+        tensors on this estimator's device through _pipeline_device."""
+        batch_iter = iter(batch_iter)
+        first = next(batch_iter, None)
+        if first is None:
+            return
+        batches = itertools.chain([first], batch_iter)
+        if self._on_device(first):
+            yield from self._pipeline_device(batches, num, want, nmaps_of)
+            return
+        it = example_stream(batches)
+        if num is not None:
+            it = (ex for i, ex in zip(range(int(num)), it))
+        yield from self._pipeline_staged(it, want, nmaps_of)
+
     def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False, visual=False):
         """The benchmark files of eval_gui.py --output_benchmark (:247-263): for the k-th example in iteration order,
         out_dir/%06d_10.png (KITTI 16-bit RGB, --output_png) or out_dir/%06d_10.flo.  Input: what
@@ -610,9 +694,6 @@ class FlowEstimator:
         if visual and not self.visual:
             raise ValueError("export: the pictures need FlowEstimator(..., visual=True)")
         os.makedirs(out_dir, exist_ok=True)
-        it = example_stream(batch_iter)
-        if num is not None:
-            it = (ex for i, ex in zip(range(int(num)), it))
         paths = []
         want = ('u16',) if fmt == 'png' else ('flow',)
         if backward:
@@ -624,7 +705,7 @@ class FlowEstimator:
         n = 0
         # the ground truth is staged only for the pictures that show it
         nmaps_of = (lambda exs: (len(exs[0]) - 3) // 2) if visual else (lambda exs: 0)
-        for slot, shapes, nmaps, _ in self._pipeline_staged(it, want, nmaps_of):
+        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, nmaps_of):
             for i, (h, w) in enumerate(shapes):
                 flows = [('10', slot.u16, slot.flow)] + ([('01', slot.u16_bw, slot.flow_bw)] if backward else [])
                 for tag, u16, flow in flows:
@@ -656,12 +737,20 @@ class FlowEstimator:
     def _clip_frames(self, frames, what):
         out = []
         for a in frames:
-            a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
-            if a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError("%s: a frame is [h, w, 3], got %s" % (what, a.shape))
-            if a.dtype != np.uint8:
-                a = a.astype(np.float32, copy=False)
-            clip = (a.shape[0], a.shape[1], a.dtype == np.uint8)
+            if isinstance(a, torch.Tensor) and self._on_device((a,)):      # stays on the device: staged with a device copy
+                if a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError("%s: a frame is [h, w, 3], got %s" % (what, tuple(a.shape)))
+                if a.dtype != torch.uint8:
+                    a = a.float()
+                u8 = a.dtype == torch.uint8
+            else:
+                a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+                if a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError("%s: a frame is [h, w, 3], got %s" % (what, a.shape))
+                if a.dtype != np.uint8:
+                    a = a.astype(np.float32, copy=False)
+                u8 = a.dtype == np.uint8
+            clip = (int(a.shape[0]), int(a.shape[1]), bool(u8))
             if clip[0] > self.Hmax or clip[1] > self.Wmax:
                 raise ValueError("%s: a %dx%d frame exceeds max_frame %dx%d" % (what, clip[0], clip[1], self.Hmax, self.Wmax))
             if self._clip is None:
@@ -685,14 +774,21 @@ class FlowEstimator:
         slot.wait()
         nbytes = B * Hm * Wm * 3 * (1 if u8 else 4)
         fr = slot.frames[:nbytes].numpy().view(np.uint8 if u8 else np.float32).reshape(B, Hm, Wm, 3)
+        on_dev = [(i, a) for i, a in enumerate(frames) if isinstance(a, torch.Tensor)]
         for i, a in enumerate(frames):
-            fr[i, :h, :w] = a
+            if not isinstance(a, torch.Tensor):
+                fr[i, :h, :w] = a
         tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8)
         slot.tab.numpy()[:] = tab
         with torch.cuda.device(self.dev):
             cur = torch.cuda.current_stream(self.dev)
             self.tab.copy_(slot.tab, non_blocking=True)
-            self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
+            if len(on_dev) < len(frames):
+                self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
+            if on_dev:                            # frames already on this device: device copies behind the upload, no host trip
+                dv = self.frames[:nbytes].view(torch.uint8 if u8 else torch.float32).view(B, Hm, Wm, 3)
+                for i, a in on_dev:
+                    dv[i, :h, :w].copy_(a, non_blocking=True)
             self._run()
             if 'flow' in want:
                 slot.flow.copy_(self.out_flow, non_blocking=True)

@@ -508,9 +508,18 @@ class Input:
             pairs = pairs[:hold_out_inv]
         return pairs
 
-    def input_test(self, image_dir, hold_out_inv=None):
-        """_input_test (input.py:110-116): batches of (image_1, image_2, input_shape), one epoch, a smaller final batch allowed."""
-        pairs = self.test_pairs(image_dir, hold_out_inv)
+    def input_test(self, image_dir, hold_out_inv=None, device=None, workers=8, prefetch=2):
+        """_input_test (input.py:110-116): batches of (image_1, image_2, input_shape), one epoch, a smaller final batch allowed.
+        device: None = numpy batches decoded on the host; a GPU device = the same batches, bit for bit, as device tensors
+        (input_shape stays a host array) from the library's PNG kernels (core/png_device.py::DeviceEvalBatches)."""
+        if device is not None:
+            from .png_device import DeviceEvalBatches
+            return DeviceEvalBatches(self.test_pairs(image_dir, hold_out_inv), self.batch_size, self.dims, self.normalize, self.mean,
+                                     self.stddev, device=device, workers=workers, prefetch=prefetch)
+        return self._input_test_host(image_dir, hold_out_inv)
+
+    def _input_test_host(self, image_dir, hold_out_inv):
+        pairs = self.test_pairs(image_dir, hold_out_inv)     # a generator: the directory is listed at the first next(), as ever
         for b0 in range(0, len(pairs), self.batch_size):
             im1, im2, shp = [], [], []
             for fn1, fn2 in pairs[b0:b0 + self.batch_size]:

@@ -5,10 +5,15 @@ frame).  Here the host only parses chunks and inflates (zlib releases the GIL, s
 rest (csrc/png_decode.hip):
 
   * unflow_png_unfilter   the five PNG row filters for a whole batch of images in one launch;
-  * unflow_png_to_batch   read_png_image's channel rule, the crop and the normalisation -> float32 [n,H,W,3].
+  * unflow_png_to_batch   read_png_image's channel rule, the crop and the normalisation -> float32 [n,H,W,3];
+  * unflow_png_to_window  the same on a window with a signed origin: crop, central crop and zero padding in one rule;
+  * unflow_png_to_flow_gt KITTI's 16-bit flow maps on such a window -> flow [n,H,W,2] and mask [n,H,W,1].
 
 png_scanlines / decode_png_device are the building blocks; DevicePairBatches is the device twin of RawPairBatches (same pair
 order, same crop draws, bit-identical batches) with the next batches in flight on a side stream while the step runs.
+DeviceGTBatches is the twin of KITTIInput.input_train_gt (supervised fine-tuning) and DeviceEvalBatches of the evaluation
+readers (KITTIInput.input_train_2012 / 2015, input_test_*): the same pipeline over a list of files per batch, each with a
+role (frame or ground truth) and an origin.
 There is no host fallback: without the library's kernels these raise."""
 import collections
 import ctypes
@@ -122,10 +127,14 @@ def _to_batch(dec_dev, n_dec, table_dev, n, H, W, mean, stddev, out, stream):
 def decode_png_device(datas, device=None):
     """[PNG bytes, ...] -> [device tensor uint8 / uint16 [h, w, ch], ...], each equal to decode_png(data) exactly; one
     unflow_png_unfilter launch on the current stream serves the whole list."""
+    return decode_scanlines_device([png_scanlines(data) for data in datas], device)
+
+
+def decode_scanlines_device(scans, device=None):
+    """decode_png_device behind the inflate: scans = [png_scanlines(data), ...] (which a thread pool can produce ahead)."""
     dev = _device(device)
     metas, raws, rows, src, dst = [], [], [], 0, 0
-    for data in datas:
-        h, w, depth, ctype, raw = png_scanlines(data)
+    for h, w, depth, ctype, raw in scans:
         n_in, n_out = h * (w * _bpp(depth, ctype) + 1), h * w * _bpp(depth, ctype)
         metas.append((h, w, depth, ctype, dst, n_out))
         raws.append(np.frombuffer(raw, dtype=np.uint8, count=n_in))
@@ -149,6 +158,17 @@ def decode_png_device(datas, device=None):
                 a = a.view(h, w, ch)
             out.append(a)
     return out
+
+
+def _to_window(dec_dev, n_dec, table_dev, n, H, W, mean, stddev, out, stream):
+    mean_host = None if mean is None else (ctypes.c_float * 3)(*[float(m) for m in mean])
+    check(_lib.lib().unflow_png_to_window(ptr(dec_dev), _lib.cl(n_dec), ptr(table_dev), n, H, W, mean_host,
+                                          _lib.cf(0.0 if stddev is None else stddev), ptr(out), _stream_ptr(stream)), "png_to_window")
+
+
+def _to_flow_gt(dec_dev, n_dec, table_dev, n, H, W, flow, mask, stream):
+    check(_lib.lib().unflow_png_to_flow_gt(ptr(dec_dev), _lib.cl(n_dec), ptr(table_dev), n, H, W, ptr(flow), ptr(mask),
+                                           _stream_ptr(stream)), "png_to_flow_gt")
 
 
 class PairPlanner:
@@ -201,16 +221,109 @@ def _inflate_into(path, meta, dst):
     return time.perf_counter() - t0
 
 
+FRAME, GT = 'frame', 'gt'        # a file's role: through unflow_png_to_batch / _to_window, or through unflow_png_to_flow_gt
+
+
+def window_origin(n, size):
+    """Where the window of resize_image_with_crop_or_pad(frame, size) starts in a frame axis of n pixels: its central-crop offset
+    (n > size) or minus its zero-padding offset (n <= size; the odd extra goes to the bottom / right, as in TF).  The negative
+    of core/inference.frame_origin."""
+    return (n - size) // 2 if n > size else -((size - n) // 2)
+
+
+def check_gt_header(path, meta):
+    """A KITTI flow map is 16-bit RGB; anything else: ValueError naming the file."""
+    if (meta[2], meta[3]) != (16, 2):
+        raise ValueError("%s: not a 16-bit RGB flow map (depth %d, colour type %d)" % (path, meta[2], meta[3]))
+
+
+def check_window_inside(path, meta, oy, ox, dims):
+    """The (h, w) window at (oy, ox) must lie inside the file's frame (the crops of training); else ValueError naming the file."""
+    h, w = dims
+    if oy < 0 or ox < 0 or oy + h > meta[0] or ox + w > meta[1]:
+        raise ValueError("%s is %d x %d: the %d x %d window at (%d, %d) leaves it" % (path, meta[0], meta[1], h, w, oy, ox))
+
+
+class GTPlanner(PairPlanner):
+    """The host-only half of DeviceGTBatches: walks KITTIInput.train_gt_files' (im1, im2, gt) list as input_train_gt does — from
+    `shift`, in order, cyclically — and draws oy, then ox, per example from np.random.RandomState(seed) with limits from im1's
+    header.  The window must lie inside all three files and the ground truth must be 16-bit RGB."""
+
+    def __init__(self, files, batch_size, dims, seed, shift=0):
+        super().__init__(files, batch_size, dims, True, seed)
+        self.pos = int(shift)
+
+    def next_batch(self):
+        """[(im1, im2, gt, header 1, header 2, header gt, oy, ox), ...] of the next batch."""
+        h, w = self.dims
+        out = []
+        for _ in range(self.batch_size):
+            fn1, fn2, fgt = self.pairs[self.pos % len(self.pairs)]
+            self.pos += 1
+            m1, m2, mg = self.header(fn1), self.header(fn2), self.header(fgt)
+            check_gt_header(fgt, mg)
+            check_window_inside(fn1, m1, 0, 0, self.dims)
+            oy = int(self.rng.randint(0, m1[0] - h + 1))
+            ox = int(self.rng.randint(0, m1[1] - w + 1))
+            for fn, m in ((fn2, m2), (fgt, mg)):
+                check_window_inside(fn, m, oy, ox, self.dims)
+            out.append((fn1, fn2, fgt, m1, m2, mg, oy, ox))
+        return out
+
+    def files(self, examples):
+        return [(e[0], e[3], FRAME, e[6], e[7]) for e in examples] + [(e[1], e[4], FRAME, e[6], e[7]) for e in examples] + \
+               [(e[2], e[5], GT, e[6], e[7]) for e in examples]
+
+
+class EvalPlanner(PairPlanner):
+    """The host-only half of DeviceEvalBatches: one pass over the pair list, `batch_size` examples per batch (a short last one),
+    ground-truth files position by position as KITTIInput._input_train pairs them; every file gets the origin of
+    resize_image_with_crop_or_pad for its OWN size (window_origin)."""
+
+    def __init__(self, pairs, batch_size, dims, gt_lists=()):
+        super().__init__(pairs, batch_size, dims, False, 0)
+        self.gt_lists = [list(g) for g in gt_lists]
+        for g in self.gt_lists:
+            if len(g) != len(self.pairs):
+                raise ValueError("%d ground-truth files for %d pairs" % (len(g), len(self.pairs)))
+
+    def _file(self, path, role):
+        m = self.header(path)
+        if role == GT:
+            check_gt_header(path, m)
+        return (path, m, role, window_origin(m[0], self.dims[0]), window_origin(m[1], self.dims[1]))
+
+    def next_batch(self):
+        """[[file of im1, of im2, of every ground-truth list], ...] per example — (path, header, role, oy, ox) each — or None
+        behind the last pair."""
+        if self.pos >= len(self.pairs):
+            return None
+        out = []
+        for k in range(self.pos, min(self.pos + self.batch_size, len(self.pairs))):
+            fn1, fn2 = self.pairs[k]
+            out.append([self._file(fn1, FRAME), self._file(fn2, FRAME)] + [self._file(g[k], GT) for g in self.gt_lists])
+        self.pos += len(out)
+        return out
+
+    @staticmethod
+    def files(examples):
+        """Column-major: all first frames, all second frames, then each ground-truth list."""
+        return [ex[c] for c in range(len(examples[0])) for ex in examples]
+
+
 class _Slot:
     """Staging and output of one batch in flight.  Every buffer is allocated (and grown) on the CONSUMER's thread, see
-    DevicePairBatches._schedule."""
+    _DeviceBatches._schedule."""
 
-    def __init__(self, n, H, W, dev):
+    def __init__(self, n_frames, n_gt, H, W, dev):
+        n = n_frames + n_gt
         self.staging = None                       # pinned uint8: the batch's inflated streams, back to back
         self.table_host = torch.empty(n, _lib.PNG_DESC_FIELDS, dtype=torch.int64).pin_memory()
         self.table = torch.empty(n, _lib.PNG_DESC_FIELDS, dtype=torch.int64, device=dev)
         self.raw = self.dec = None                # device: inflated streams, decoded frames
-        self.out = torch.empty(2, n // 2, H, W, 3, dtype=torch.float32, device=dev)
+        self.out = torch.empty(n_frames, H, W, 3, dtype=torch.float32, device=dev)
+        self.flow = torch.empty(n_gt, H, W, 2, dtype=torch.float32, device=dev) if n_gt else None
+        self.mask = torch.empty(n_gt, H, W, 1, dtype=torch.float32, device=dev) if n_gt else None
         self.uploaded = None                      # side-stream event: the pinned buffers have been read
 
     def reserve(self, n_raw, n_dec, dev):
@@ -226,16 +339,17 @@ class _Slot:
 
 
 class _Job:
-    """One batch: its slot, its frames [(file, header, oy, ox)] (first frames, then second frames), the kernels' table rows, each
-    frame's span in the staging buffer, the byte totals, the workers' futures and the event behind which the slot may be
-    rewritten."""
+    """One batch: its slot, its files [(file, header, role, oy, ox)] (the frames first, then the ground-truth maps), the kernels'
+    table rows, each file's span in the staging buffer, the byte totals, the workers' futures and the event behind which the slot
+    may be rewritten.  `plan` is what the planner returned (the iterator builds its result from it)."""
 
-    def __init__(self, slot, examples):
-        self.slot = slot
-        self.frames = [(fn1, m1, oy, ox) for fn1, _, m1, _, oy, ox in examples] + \
-                      [(fn2, m2, oy, ox) for _, fn2, _, m2, oy, ox in examples]
+    def __init__(self, slot, files, plan=None):
+        self.slot, self.files, self.plan = slot, files, plan
+        self.n_frames = sum(1 for f in files if f[2] == FRAME)
+        self.n_gt = len(files) - self.n_frames
+        assert all(f[2] == FRAME for f in files[:self.n_frames]) and all(f[2] == GT for f in files[self.n_frames:])
         self.rows, self.spans, src, dst = [], [], 0, 0
-        for _, (h, w, depth, ctype), oy, ox in self.frames:
+        for _, (h, w, depth, ctype), _, oy, ox in self.files:
             n_in, n_out = h * (w * _bpp(depth, ctype) + 1), h * w * _bpp(depth, ctype)
             self.rows.append(_table_row(src, dst, h, w, depth, ctype, oy, ox))
             self.spans.append((src, n_in))
@@ -249,14 +363,15 @@ class _Job:
 
 class _Pipeline:
     """What the producer thread owns: the worker pool, the side stream and the launches.  It does not refer to the iterator, so
-    dropping the iterator stops it (DevicePairBatches.__del__).
+    dropping the iterator stops it (_DeviceBatches.__del__).
 
-    The producer thread only enqueues on the side stream (waits on events, asynchronous copies from pinned memory, the two
+    The producer thread only enqueues on the side stream (waits on events, asynchronous copies from pinned memory, the
     kernels, event records): it never allocates and never synchronises, so it may run while the consumer's thread captures a
-    hipGraph of the training step (allocations and synchronising calls of ANY thread are errors during a capture)."""
+    hipGraph of the training step (allocations and synchronising calls of ANY thread are errors during a capture).
+    window: the frames go through unflow_png_to_window (signed origins, zero padding) instead of unflow_png_to_batch."""
 
-    def __init__(self, dev, dims, mean, stddev, workers, timing):
-        self.dev, self.dims, self.mean, self.stddev, self.timing = dev, dims, mean, stddev, timing
+    def __init__(self, dev, dims, mean, stddev, workers, timing, window=False):
+        self.dev, self.dims, self.mean, self.stddev, self.timing, self.window = dev, dims, mean, stddev, timing, window
         self.pool = ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS)), thread_name_prefix="png-inflate")
         self.side = torch.cuda.Stream(dev)
         self.jobs = queue.Queue()
@@ -279,25 +394,30 @@ class _Pipeline:
 
     def _produce(self, job):
         slot, (H, W) = job.slot, self.dims
-        slot.table_host.copy_(torch.tensor(job.rows, dtype=torch.int64))
+        n, nf = len(job.rows), job.n_frames
+        slot.table_host[:n].copy_(torch.tensor(job.rows, dtype=torch.int64))
         errors = [f.exception() for f in job.futures]         # waits for every worker: none is left writing into the slot
         job.times['inflate_s'] = time.perf_counter() - job.submitted          # submit -> last frame staged
         for e in errors:
             if e is not None:
                 raise e
         job.times['worker_s'] = sum(f.result() for f in job.futures)          # thread-seconds of the batch's frames
-        marks = [torch.cuda.Event(enable_timing=self.timing) for _ in range(4)]
+        marks = [torch.cuda.Event(enable_timing=self.timing) for _ in range(5)]
         with torch.cuda.stream(self.side):
             self.side.wait_event(job.free_event)               # the consumer has passed the batch this slot held
             marks[0].record(self.side)
             slot.raw[:job.n_raw].copy_(slot.staging[:job.n_raw], non_blocking=True)
-            slot.table.copy_(slot.table_host, non_blocking=True)
+            slot.table[:n].copy_(slot.table_host[:n], non_blocking=True)
             marks[1].record(self.side)
-            _unfilter(slot.raw, job.n_raw, slot.dec, job.n_dec, slot.table, len(job.rows), self.side)
+            _unfilter(slot.raw, job.n_raw, slot.dec, job.n_dec, slot.table, n, self.side)
             marks[2].record(self.side)
-            _to_batch(slot.dec, job.n_dec, slot.table, len(job.rows), H, W, self.mean, self.stddev, slot.out, self.side)
+            to_frames = _to_window if self.window else _to_batch
+            to_frames(slot.dec, job.n_dec, slot.table, nf, H, W, self.mean, self.stddev, slot.out, self.side)
             marks[3].record(self.side)
-        slot.uploaded, job.marks, job.ready = marks[1], marks, marks[3]
+            if job.n_gt:
+                _to_flow_gt(slot.dec, job.n_dec, slot.table[nf:], job.n_gt, H, W, slot.flow, slot.mask, self.side)
+            marks[4].record(self.side)
+        slot.uploaded, job.marks, job.ready = marks[1], marks, marks[4]
 
     def close(self):
         if self.closed:
@@ -310,38 +430,36 @@ class _Pipeline:
         self.side.synchronize()
 
 
-class DevicePairBatches:
-    """The device twin of RawPairBatches: an iterator of (image_1, image_2), two float32 DEVICE tensors [B,H,W,3] that equal what
-    RawPairBatches.__next__ returns for the same files and seed, bit for bit.
+class _DeviceBatches:
+    """The loader ring that the three iterators share.  A subclass plans a batch on the consumer's thread (_plan: the files of
+    the next batch with their roles and origins, or None when a finite input is exhausted) and names what next() returns
+    (_result: views of the slot's tensors).
 
-    Up to `workers` (at most 16) threads read the files and inflate them into pinned staging; the upload and the two kernels run
+    Up to `workers` (at most 16) threads read the files and inflate them into pinned staging; the upload and the kernels run
     on one side stream; `prefetch` batches are in flight while the consumer works.  next() makes the current stream wait for the
-    batch's event, so kernels launched on the current stream afterwards (the engine's) see the batch.  The two tensors belong
+    batch's event, so kernels launched on the current stream afterwards (the engine's) see the batch.  The tensors belong
     to a ring of prefetch + 1 slots: they stay valid for work enqueued on the current stream before the NEXT next() call (which is
     what Trainer.train does: set_input copies them into the engine's buffers); copy them to keep them longer.  A slot is
     rewritten only behind an event recorded on the current stream at that later next().  next() also plans the batch that
-    takes the freed slot (pair order and crop draws: PairPlanner), grows the slot's buffers if the batch needs it, waits
-    until the slot's last upload has left the pinned staging and hands the batch's files to the workers — everything that
-    allocates or synchronises happens on the consumer's thread, between steps.  close() (and garbage collection) stops the
-    threads.  Threads only: no other process opens the GPU."""
+    takes the freed slot, grows the slot's buffers if the batch needs it, waits until the slot's last upload has left the pinned
+    staging and hands the batch's files to the workers — everything that allocates or synchronises happens on the consumer's
+    thread, between steps.  close() (and garbage collection) stops the threads.  Threads only: no other process opens the GPU."""
 
-    def __init__(self, pairs, batch_size, dims, needs_crop, normalize, mean, stddev, seed, device=None, workers=8, prefetch=2,
-                 timing=False):
+    def __init__(self, n_frames, n_gt, dims, mean, stddev, device, workers, prefetch, timing, window):
         if prefetch < 1:
             raise ValueError("prefetch must be at least 1")
         self.device = _device(device)
-        self.planner = PairPlanner(pairs, batch_size, dims, needs_crop, seed)
-        self.batch_size, self.dims, self.prefetch = batch_size, tuple(dims), prefetch
+        self.dims, self.prefetch = tuple(dims), prefetch
         _lib.lib()                                  # a missing library is an error here, not in the producer thread
-        mean = np.asarray(mean, dtype=np.float32) if normalize else None
-        self._pipe = _Pipeline(self.device, self.dims, mean, np.float32(stddev) if normalize else None, workers, bool(timing))
+        self._pipe = _Pipeline(self.device, self.dims, mean, stddev, workers, bool(timing), window)
         self._inflight = collections.deque()
         self._held = None                           # the slot whose tensors the consumer holds
+        self._exhausted = False                     # a finite input: the planner has no further batch
         self.stage_times = collections.deque(maxlen=64)     # timing=True: per-batch dicts, filled by next()
         self._timed = collections.deque()
         try:
             with torch.cuda.device(self.device):
-                slots = [_Slot(2 * batch_size, self.dims[0], self.dims[1], self.device) for _ in range(prefetch + 1)]
+                slots = [_Slot(n_frames, n_gt, self.dims[0], self.dims[1], self.device) for _ in range(prefetch + 1)]
             # (slot, event on the current stream behind which the side stream may write it)
             self._free = collections.deque((s, self._mark()) for s in slots)
             for _ in range(prefetch):
@@ -350,14 +468,26 @@ class DevicePairBatches:
             self._pipe.close()
             raise
 
+    def _plan(self):
+        raise NotImplementedError
+
+    def _result(self, job):
+        raise NotImplementedError
+
     def _mark(self):
         e = torch.cuda.Event()
         e.record(torch.cuda.current_stream(self.device))
         return e
 
     def _schedule(self):
+        if self._exhausted:
+            return False
+        planned = self._plan()
+        if planned is None:
+            self._exhausted = True
+            return False
         slot, free_event = self._free[0]
-        job = _Job(slot, self.planner.next_batch())
+        job = _Job(slot, *planned)
         self._free.popleft()
         if slot.uploaded is not None:
             slot.uploaded.synchronize()             # the slot's previous batch has left the pinned buffers: workers may write them
@@ -368,17 +498,20 @@ class DevicePairBatches:
         # the workers start now, so the frames of every batch in flight share the pool; the producer thread takes the batches in order
         stage = slot.staging.numpy()
         job.submitted = time.perf_counter()
-        job.futures = [self._pipe.pool.submit(_inflate_into, fn, meta, stage[o:o + n])
-                       for (fn, meta, _, _), (o, n) in zip(job.frames, job.spans)]
+        job.futures = [self._pipe.pool.submit(_inflate_into, f[0], f[1], stage[o:o + n]) for f, (o, n) in zip(job.files, job.spans)]
         self._inflight.append(job)
         self._pipe.jobs.put(job)
+        return True
 
     def __iter__(self):
         return self
 
     def __next__(self):
-        if self._pipe.closed:
-            raise RuntimeError("DevicePairBatches is closed")
+        if self._pipe.closed and not (self._exhausted and not self._inflight):
+            raise RuntimeError("%s is closed" % type(self).__name__)
+        if not self._inflight:                      # a finite input, fully handed out
+            self.close()
+            raise StopIteration
         job = self._inflight.popleft()
         job.done.wait()
         if job.error is not None:
@@ -390,22 +523,25 @@ class DevicePairBatches:
             self._free.append((self._held, self._mark()))       # behind the mark: everything the consumer did with that batch
         self._held = job.slot
         try:
-            while self._free and len(self._inflight) < self.prefetch:
-                self._schedule()
+            while self._free and len(self._inflight) < self.prefetch and self._schedule():
+                pass
         except BaseException:
             self.close()
             raise
         if self._pipe.timing:
             self._collect(job)
-        return job.slot.out[0], job.slot.out[1]
+        return self._result(job)
 
     def _collect(self, job):
         self._timed.append(job)
-        while self._timed and self._timed[0].marks[3].query():
+        while self._timed and self._timed[0].marks[4].query():
             j = self._timed.popleft()
             m = j.marks
-            self.stage_times.append(dict(j.times, upload_ms=m[0].elapsed_time(m[1]), unfilter_ms=m[1].elapsed_time(m[2]),
-                                         to_batch_ms=m[2].elapsed_time(m[3])))
+            t = dict(j.times, upload_ms=m[0].elapsed_time(m[1]), unfilter_ms=m[1].elapsed_time(m[2]),
+                     to_batch_ms=m[2].elapsed_time(m[3]))
+            if j.n_gt:
+                t['flow_gt_ms'] = m[3].elapsed_time(m[4])
+            self.stage_times.append(t)
 
     def close(self):
         self._pipe.close()
@@ -415,3 +551,79 @@ class DevicePairBatches:
             self._pipe.close()
         except Exception:
             pass
+
+
+def _norm(normalize, mean, stddev):
+    return (np.asarray(mean, dtype=np.float32), np.float32(stddev)) if normalize else (None, None)
+
+
+class DevicePairBatches(_DeviceBatches):
+    """The device twin of RawPairBatches: an iterator of (image_1, image_2), two float32 DEVICE tensors [B,H,W,3] that equal what
+    RawPairBatches.__next__ returns for the same files and seed, bit for bit (pair order and crop draws: PairPlanner; the ring,
+    the threads and the lifetime of the tensors: _DeviceBatches)."""
+
+    def __init__(self, pairs, batch_size, dims, needs_crop, normalize, mean, stddev, seed, device=None, workers=8, prefetch=2,
+                 timing=False):
+        self.planner = PairPlanner(pairs, batch_size, dims, needs_crop, seed)
+        self.batch_size = batch_size
+        mean, stddev = _norm(normalize, mean, stddev)
+        super().__init__(2 * batch_size, 0, dims, mean, stddev, device, workers, prefetch, timing, window=False)
+
+    def _plan(self):
+        examples = self.planner.next_batch()
+        files = [(fn1, m1, FRAME, oy, ox) for fn1, _, m1, _, oy, ox in examples] + \
+                [(fn2, m2, FRAME, oy, ox) for _, fn2, _, m2, oy, ox in examples]
+        return files, examples
+
+    def _result(self, job):
+        B = self.batch_size
+        return job.slot.out[:B], job.slot.out[B:]
+
+
+class DeviceGTBatches(_DeviceBatches):
+    """The device twin of KITTIInput.input_train_gt: an endless iterator of (im1, im2, flow_gt, mask_gt), float32 DEVICE tensors
+    [B,h,w,3] x 2, [B,h,w,2], [B,h,w,1], bit-identical to the host iterator for the same file list, seed and shift (GTPlanner).
+    A window that leaves one of an example's three files, or a ground-truth file that is not 16-bit RGB, raises ValueError
+    naming the file (from the constructor or from next(), whichever plans the batch)."""
+
+    def __init__(self, files, batch_size, dims, normalize, mean, stddev, seed=0, shift=0, device=None, workers=8, prefetch=2,
+                 timing=False):
+        self.planner = GTPlanner(files, batch_size, dims, seed, shift)
+        self.batch_size = batch_size
+        mean, stddev = _norm(normalize, mean, stddev)
+        super().__init__(2 * batch_size, batch_size, dims, mean, stddev, device, workers, prefetch, timing, window=True)
+
+    def _plan(self):
+        examples = self.planner.next_batch()
+        return self.planner.files(examples), examples
+
+    def _result(self, job):
+        B, s = self.batch_size, job.slot
+        return s.out[:B], s.out[B:], s.flow, s.mask
+
+
+class DeviceEvalBatches(_DeviceBatches):
+    """The device twin of KITTIInput._input_train (gt_lists = the flow_occ and flow_noc files) and Input.input_test (no ground
+    truth): one pass, a short last batch, the host iterator's tuples — im1, im2 [n,Hs,Ws,3] on the device, input_shape [n,3]
+    int32 on the HOST (from im1's IHDR) and per ground-truth list flow [n,Hs,Ws,2], mask [n,Hs,Ws,1] — every tensor equal to the
+    host's bit for bit (crop or zero padding per file as resize_image_with_crop_or_pad, normalisation after the padding)."""
+
+    def __init__(self, pairs, batch_size, dims, normalize, mean, stddev, gt_lists=(), device=None, workers=8, prefetch=2,
+                 timing=False):
+        self.planner = EvalPlanner(pairs, batch_size, dims, gt_lists)
+        self.batch_size = batch_size
+        mean, stddev = _norm(normalize, mean, stddev)
+        super().__init__(2 * batch_size, len(self.planner.gt_lists) * batch_size, dims, mean, stddev, device, workers, prefetch,
+                         timing, window=True)
+
+    def _plan(self):
+        examples = self.planner.next_batch()
+        return None if examples is None else (self.planner.files(examples), examples)
+
+    def _result(self, job):
+        n, s = len(job.plan), job.slot
+        shapes = np.asarray([(ex[0][1][0], ex[0][1][1], 3) for ex in job.plan], dtype=np.int32)
+        out = [s.out[:n], s.out[n:2 * n], shapes]
+        for g in range(len(self.planner.gt_lists)):
+            out += [s.flow[g * n:(g + 1) * n], s.mask[g * n:(g + 1) * n]]
+        return tuple(out)

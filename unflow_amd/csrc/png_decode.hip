@@ -203,6 +203,78 @@ __global__ __launch_bounds__(256) void png_to_batch_kernel(const unsigned char* 
   }
 }
 
+// The window entries share one geometry rule: output pixel (y, x) is frame pixel (y + oy, x + ox) when that lies inside (h, w),
+// else 0 — oy, ox signed, so one rule is the random crop, the central crop and resize_image_with_crop_or_pad's zero padding.
+constexpr long PNG_MAX_SIDE = 1 << 24;
+
+struct PngWindow {
+  const unsigned char* base;
+  long h, w, oy, ox;
+  int bpp, sb;
+};
+
+// False: the entry is skipped (it does not fit `dec`, or its fields are out of range).
+__device__ __forceinline__ bool png_window_of(const long* d, const unsigned char* dec, long dec_bytes, PngWindow& g) {
+  const long off = d[1], h = d[2], w = d[3], bpp = d[4], sb = d[5], oy = d[6], ox = d[7];
+  if (h <= 0 || w <= 0 || h > PNG_MAX_SIDE || w > PNG_MAX_SIDE || bpp < 1 || bpp > 8 || (sb != 1 && sb != 2) || bpp % sb != 0 ||
+      bpp / sb > 4)                        // 1 to 4 channels of 1 or 2 bytes: 1, 2, 3, 4, 6 or 8 bytes per pixel
+    return false;
+  if (oy < -PNG_MAX_SIDE || oy > PNG_MAX_SIDE || ox < -PNG_MAX_SIDE || ox > PNG_MAX_SIDE) return false;
+  if (off < 0 || off > dec_bytes || h * w * bpp > dec_bytes - off) return false;
+  g = PngWindow{dec + off, h, w, oy, ox, (int)bpp, (int)sb};
+  return true;
+}
+
+__global__ __launch_bounds__(256) void png_to_window_kernel(const unsigned char* __restrict__ dec, long dec_bytes,
+                                                            const long* __restrict__ table, int Hs, int Ws, Norm nm,
+                                                            float* __restrict__ out) {
+  PngWindow g;
+  if (!png_window_of(table + (long)blockIdx.y * PNG_DESC, dec, dec_bytes, g)) return;
+  const int ch = g.bpp / g.sb;
+  const unsigned n3 = (unsigned)Hs * (unsigned)Ws * 3u;            // < 2^31 (the host checks)
+  float* o = out + (long)blockIdx.y * n3;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n3; i += gridDim.x * blockDim.x) {
+    const unsigned pix = i / 3u, c = i - pix * 3u;
+    const unsigned y = pix / (unsigned)Ws, x = pix - y * (unsigned)Ws;
+    const long fy = (long)y + g.oy, fx = (long)x + g.ox;
+    const unsigned sc = ch >= 3 ? c : 0u;
+    float v = 0.f;                                                  // the padding is zero BEFORE the normalisation
+    if (fy >= 0 && fy < g.h && fx >= 0 && fx < g.w) v = (float)g.base[(fy * g.w + fx) * g.bpp + sc * g.sb];
+    if (nm.on) v = __fdiv_rn(v - nm.mean[c], nm.stddev);
+    o[i] = v;
+  }
+}
+
+// KITTI's 16-bit RGB flow map: one thread per output pixel reads the pixel's six bytes once (byte loads: a packed frame's rows
+// start at any address) and writes the flow pair with one 8-byte store.  (u16 - 32768) / 64 and float(u16) are exact in fp32.
+__global__ __launch_bounds__(256) void png_to_flow_gt_kernel(const unsigned char* __restrict__ dec, long dec_bytes,
+                                                             const long* __restrict__ table, int Hs, int Ws,
+                                                             float2* __restrict__ flow, float* __restrict__ mask) {
+  PngWindow g;
+  if (!png_window_of(table + (long)blockIdx.y * PNG_DESC, dec, dec_bytes, g)) return;
+  if (g.bpp != 6 || g.sb != 2) return;
+  const unsigned n = (unsigned)Hs * (unsigned)Ws;                   // < 2^31 / 3 (the host checks)
+  float2* of = flow + (long)blockIdx.y * n;
+  float* om = mask + (long)blockIdx.y * n;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const unsigned y = i / (unsigned)Ws, x = i - y * (unsigned)Ws;
+    const long fy = (long)y + g.oy, fx = (long)x + g.ox;
+    float2 f = make_float2(0.f, 0.f);
+    float m = 0.f;
+    if (fy >= 0 && fy < g.h && fx >= 0 && fx < g.w) {
+      const unsigned char* p = g.base + (fy * g.w + fx) * 6;
+      unsigned char b[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) b[k] = p[k];
+      f.x = ((float)(int)((b[0] << 8) | b[1]) - 32768.f) * 0.015625f;
+      f.y = ((float)(int)((b[2] << 8) | b[3]) - 32768.f) * 0.015625f;
+      m = (float)(int)((b[4] << 8) | b[5]);
+    }
+    of[i] = f;
+    om[i] = m;
+  }
+}
+
 }  // namespace
 
 UNFLOW_API int unflow_png_unfilter_rows(void) { return PNG_R; }
@@ -228,5 +300,31 @@ UNFLOW_API int unflow_png_to_batch(const unsigned char* decoded, long decoded_by
   }
   const dim3 grid(min(stream_grid((long)H * W * 3), 256), n);
   png_to_batch_kernel<<<grid, 256, 0, as_stream(stream)>>>(decoded, decoded_bytes, table, H, W, nm, out);
+  return launch_status();
+}
+
+UNFLOW_API int unflow_png_to_window(const unsigned char* decoded, long decoded_bytes, const long* table, int n, int Hs, int Ws,
+                                    const float* mean3, float stddev, float* out, unflow_stream_t stream) {
+  if (!decoded || !table || !out) return UNFLOW_ERR_NULL;
+  if (n <= 0 || n > 65535 || Hs <= 0 || Ws <= 0 || decoded_bytes <= 0 || (long)Hs * Ws * 3 > 0x7fffffffL) return UNFLOW_ERR_SHAPE;
+  if (mean3 && !(stddev != 0.f)) return UNFLOW_ERR_SHAPE;
+  Norm nm{};
+  if (mean3) {
+    nm.mean[0] = mean3[0]; nm.mean[1] = mean3[1]; nm.mean[2] = mean3[2];
+    nm.stddev = stddev;
+    nm.on = 1;
+  }
+  const dim3 grid(min(stream_grid((long)Hs * Ws * 3), 256), n);
+  png_to_window_kernel<<<grid, 256, 0, as_stream(stream)>>>(decoded, decoded_bytes, table, Hs, Ws, nm, out);
+  return launch_status();
+}
+
+UNFLOW_API int unflow_png_to_flow_gt(const unsigned char* decoded, long decoded_bytes, const long* table, int n, int Hs, int Ws,
+                                     float* flow, float* mask, unflow_stream_t stream) {
+  if (!decoded || !table || !flow || !mask) return UNFLOW_ERR_NULL;
+  if (n <= 0 || n > 65535 || Hs <= 0 || Ws <= 0 || decoded_bytes <= 0 || (long)Hs * Ws * 3 > 0x7fffffffL) return UNFLOW_ERR_SHAPE;
+  const dim3 grid(min(stream_grid((long)Hs * Ws), 256), n);
+  png_to_flow_gt_kernel<<<grid, 256, 0, as_stream(stream)>>>(decoded, decoded_bytes, table, Hs, Ws,
+                                                             reinterpret_cast<float2*>(flow), mask);
   return launch_status();
 }

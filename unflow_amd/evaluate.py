@@ -1,7 +1,7 @@
 """python -m unflow_amd.evaluate: score a trained experiment on KITTI and write benchmark files — the non-GUI part of the
 reference's src/eval_gui.py, on core/inference.FlowEstimator (batched, graph-replayed, forward only).
 
-    python -m unflow_amd.evaluate --ex NAME [--variant train_2012] [--num 10] [--occlusion]
+    python -m unflow_amd.evaluate --ex NAME [--variant train_2012] [--num 10] [--occlusion] [--host_decode]
                                   [--output_benchmark [--output_png] [--output_backward]]
 
 The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives the network spec ([train] and
@@ -36,6 +36,8 @@ def parser():
     ap.add_argument('--occlusion', action='store_true',
                     help='forward-backward occlusion: scores on train_* variants, %%06d_10_occ.png with --output_benchmark')
     ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
+    ap.add_argument('--host_decode', action='store_true',
+                    help="decode the PNG files with the host's decoder (slow) instead of the library's PNG kernels")
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
     ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
     ap.add_argument('--dims', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
@@ -102,7 +104,8 @@ def main(argv=None):
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch_size, net_size=tuple(a.dims),
                                         bidirectional=a.output_backward or a.occlusion)
     kinput = KITTIInput(_KITTIData(dirs.get('data', '')), batch_size=a.batch_size, normalize=False, dims=tuple(a.dims))
-    batches = lambda: getattr(kinput, 'input_' + a.variant)()            # noqa: E731
+    dev = None if a.host_decode else est.dev          # the PNG files decoded by the library's kernels (core/png_device.py)
+    batches = lambda: getattr(kinput, 'input_' + a.variant)(device=dev)            # noqa: E731
     num = None if a.num < 0 else a.num
     print("-- evaluating %s (step %s) on kitti %s" % (a.ex, est.global_step, a.variant))
     if a.variant.startswith('train'):

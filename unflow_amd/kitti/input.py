@@ -36,13 +36,27 @@ class KITTIInput(Input):
         assert len(out[0]) == len(out[1])
         return out
 
-    def _input_train(self, image_dir, flow_dir, hold_out_inv=None):
+    def _input_train(self, image_dir, flow_dir, hold_out_inv=None, device=None, workers=8, prefetch=2):
         """kitti/input.py:75-82: batches of [im1, im2, input_shape, flow_occ, mask_occ, flow_noc, mask_noc] (numpy,
         NHWC), one epoch, a smaller final batch allowed.  The images come from Input.input_test's pair list (same
-        hold-out shuffle), the ground truth from _flow_files, position by position as the reference's queues pair them."""
+        hold-out shuffle), the ground truth from _flow_files, position by position as the reference's queues pair them.
+        device: None = decoded on the host; a GPU device = the same batches, bit for bit, as device tensors (input_shape stays a
+        host array) from the library's PNG kernels (core/png_device.py::DeviceEvalBatches)."""
+        if device is not None:
+            from ..core.png_device import DeviceEvalBatches
+            pairs, occ, noc = self._eval_files(image_dir, flow_dir, hold_out_inv)
+            return DeviceEvalBatches(pairs, self.batch_size, self.dims, self.normalize, self.mean, self.stddev, gt_lists=(occ, noc),
+                                     device=device, workers=workers, prefetch=prefetch)
+        return self._input_train_host(image_dir, flow_dir, hold_out_inv)
+
+    def _eval_files(self, image_dir, flow_dir, hold_out_inv):
         pairs = self.test_pairs(image_dir, hold_out_inv)
         occ, noc = self._flow_files(flow_dir, hold_out_inv)
         assert len(pairs) == len(occ), (len(pairs), len(occ))
+        return pairs, occ, noc
+
+    def _input_train_host(self, image_dir, flow_dir, hold_out_inv):
+        pairs, occ, noc = self._eval_files(image_dir, flow_dir, hold_out_inv)    # a generator: listed at the first next(), as ever
         for b0 in range(0, len(pairs), self.batch_size):
             cols = [[] for _ in range(7)]
             for (fn1, fn2), f_occ, f_noc in zip(pairs[b0:b0 + self.batch_size], occ[b0:], noc[b0:]):
@@ -54,17 +68,19 @@ class KITTIInput(Input):
                     c.append(v)
             yield tuple(np.stack(c) for c in cols)
 
-    def input_train_2015(self, hold_out_inv=None):
-        return self._input_train('data_scene_flow/training/image_2', 'data_scene_flow/training', hold_out_inv)
+    def input_train_2015(self, hold_out_inv=None, device=None, workers=8, prefetch=2):
+        return self._input_train('data_scene_flow/training/image_2', 'data_scene_flow/training', hold_out_inv, device, workers,
+                                 prefetch)
 
-    def input_test_2015(self, hold_out_inv=None):
-        return self.input_test('data_scene_flow/testing/image_2', hold_out_inv)
+    def input_test_2015(self, hold_out_inv=None, device=None, workers=8, prefetch=2):
+        return self.input_test('data_scene_flow/testing/image_2', hold_out_inv, device, workers, prefetch)
 
-    def input_train_2012(self, hold_out_inv=None):
-        return self._input_train('data_stereo_flow/training/colored_0', 'data_stereo_flow/training', hold_out_inv)
+    def input_train_2012(self, hold_out_inv=None, device=None, workers=8, prefetch=2):
+        return self._input_train('data_stereo_flow/training/colored_0', 'data_stereo_flow/training', hold_out_inv, device, workers,
+                                 prefetch)
 
-    def input_test_2012(self, hold_out_inv=None):
-        return self.input_test('data_stereo_flow/testing/colored_0', hold_out_inv)
+    def input_test_2012(self, hold_out_inv=None, device=None, workers=8, prefetch=2):
+        return self.input_test('data_stereo_flow/testing/colored_0', hold_out_inv, device, workers, prefetch)
 
     def train_gt_files(self, hold_out):
         """The example list of input_train_gt (kitti/input.py:86-124): per dataset (2015 image_2 + flow_occ, 2012 colored_0 +
@@ -87,7 +103,17 @@ class KITTIInput(Input):
         random.shuffle(filenames)
         return filenames
 
-    def input_train_gt(self, hold_out, seed=0, shift=0):
+    def input_train_gt(self, hold_out, seed=0, shift=0, device=None, workers=8, prefetch=2):
+        """The supervised fine-tuning input: _input_train_gt_host's batches, decoded on the host (device None) or — the same
+        batches, bit for bit, as device tensors — by the library's PNG kernels with `workers` inflate threads and `prefetch`
+        batches in flight (core/png_device.py::DeviceGTBatches)."""
+        if device is not None:
+            from ..core.png_device import DeviceGTBatches
+            return DeviceGTBatches(self.train_gt_files(hold_out), self.batch_size, self.dims, self.normalize, self.mean,
+                                   self.stddev, seed=seed, shift=shift, device=device, workers=workers, prefetch=prefetch)
+        return self._input_train_gt_host(hold_out, seed, shift)
+
+    def _input_train_gt_host(self, hold_out, seed=0, shift=0):
         """input_train_gt (kitti/input.py:86-146): an endless iterator of (im1, im2, flow_gt, mask_gt) numpy batches
         [B,h,w,3] x 2, [B,h,w,2], [B,h,w,1] over train_gt_files(hold_out), walked in order and cyclically like the
         reference's string_input_producer(shuffle=False); random_crop takes ONE window of self.dims for both frames and the

@@ -1,9 +1,10 @@
 """python -m unflow_amd.sequence: the flow along a clip of frames with a trained experiment — every frame uploaded and encoded
 once (core/inference.FlowEstimator(..., sequence=True)).
 
-    python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W]
+    python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
 
-The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  The
+The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
+inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
 experiment's config and latest checkpoint are found as python -m unflow_amd.evaluate finds them.  Files go to <--out>/NAME/:
 %06d_10.png (KITTI 16-bit flow) or, with --flo, %06d_10.flo."""
 import argparse
@@ -23,6 +24,45 @@ def read_frame(path):
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
         raise ValueError("%s: not an 8-bit RGB PNG (%s %s)" % (path, a.dtype, a.shape))
     return np.ascontiguousarray(a)
+
+
+def _inflate_frame(path):
+    """Worker: one 8-bit RGB PNG file -> its inflated scanlines (png_scanlines); read_frame's messages for anything else."""
+    import numpy as np
+    from .core.png_device import _CHANNELS, _check_variant, _walk_chunks, png_scanlines
+    try:
+        with open(path, 'rb') as f:
+            data = f.read()
+        w, h, depth, ctype, _, _, interlace = _walk_chunks(data)[0]
+        _check_variant(depth, ctype, interlace)
+    except Exception as err:
+        raise ValueError("%s: not a readable PNG (%s)" % (path, err))
+    if depth != 8 or ctype != 2:                  # from the IHDR: a wrong file is refused before it is inflated
+        raise ValueError("%s: not an 8-bit RGB PNG (%s %s)" % (path, np.dtype('uint%d' % depth), (h, w, _CHANNELS[ctype])))
+    try:
+        return png_scanlines(data)
+    except Exception as err:
+        raise ValueError("%s: not a readable PNG (%s)" % (path, err))
+
+
+def device_frames(files, batch, device=None, workers=8):
+    """The frames of a clip as uint8 [h, w, 3] DEVICE tensors, equal to read_frame's arrays: a thread pool inflates the files,
+    unflow_png_unfilter decodes `batch` frames — one replay's — per launch on the current stream, and the next replay's files
+    inflate meanwhile.  A broken or non-8-bit-RGB file raises read_frame's ValueError when its group is reached."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .core.png_device import MAX_WORKERS, decode_scanlines_device
+    groups = [files[i:i + batch] for i in range(0, len(files), batch)]
+    with ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS)), thread_name_prefix="png-inflate") as pool:
+        ahead = [pool.submit(_inflate_frame, p) for p in groups[0]] if groups else []
+        for k in range(len(groups)):
+            cur, ahead = ahead, ([pool.submit(_inflate_frame, p) for p in groups[k + 1]] if k + 1 < len(groups) else [])
+            try:
+                scans = [f.result() for f in cur]
+            except BaseException:
+                for f in ahead:
+                    f.cancel()
+                raise
+            yield from decode_scanlines_device(scans, device)
 
 
 def frame_files(folder):
@@ -50,6 +90,7 @@ def parser():
     ap.add_argument('--net_size', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
                     help='network input size (multiples of 64)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
+    ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     return ap
 
 
@@ -94,7 +135,8 @@ def main(argv=None):
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
     try:
-        paths = est.export_sequence((read_frame(p) for p in a.files), out_dir, fmt='flo' if a.flo else 'png')
+        frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
+        paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png')
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))

@@ -34,6 +34,8 @@ def parser():
     ap.add_argument('--num_vis', type=int, default=100, help='examples on the contact sheets (eval_gui.py --num_vis)')
     ap.add_argument('--sheet', action='store_true', help='also write page_%%03d.png contact sheets, four examples per page')
     ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
+    ap.add_argument('--host_decode', action='store_true',
+                    help="decode the PNG files with the host's decoder (slow) instead of the library's PNG kernels")
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
     ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
     ap.add_argument('--dims', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
@@ -124,7 +126,8 @@ def main(argv=None):
     os.makedirs(out_dir)
     shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
     print("-- visualising %s (step %s) on kitti %s" % (a.ex, est.global_step, a.variant))
-    examples = est.pictures(getattr(kinput, 'input_' + a.variant)(), num=None if a.num < 0 else a.num)
+    batches = getattr(kinput, 'input_' + a.variant)(device=None if a.host_decode else est.dev)
+    examples = est.pictures(batches, num=None if a.num < 0 else a.num)
     paths = write_pictures(examples, out_dir, sheet=a.sheet, num_vis=a.num_vis)
     print("wrote %d files to %s" % (len(paths), out_dir))
     return 0
