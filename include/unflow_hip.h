@@ -721,6 +721,31 @@ int unflow_png_to_window(const unsigned char* decoded, long decoded_bytes, const
 int unflow_png_to_flow_gt(const unsigned char* decoded, long decoded_bytes, const long* desc, int n, int Hs, int Ws, float* flow,
                           float* mask, unflow_stream_t stream);
 
+/* .flo ground truth (csrc/flo_decode.hip): Middlebury / FlyingChairs / Sintel flow files on a window of the same table.  A
+ * .flo row has src = the byte offset in `raw` of the file's first float (behind its 12-byte header: h * w pairs of
+ * little-endian fp32), bpp = 8 and sample_bytes = 4; dst is unused, and such a row never goes through unflow_png_unfilter.
+ * oy, ox are signed as above.  An entry whose src is not a multiple of 4, whose 8 * h * w bytes do not fit raw_bytes, or
+ * whose bpp / sample_bytes differ is skipped and its output left untouched; the caller validates on the host.  `raw` itself
+ * must be 4-byte aligned.  Plain vector loads and stores; nothing is accumulated.
+ *
+ * unflow_flo_to_flow_gt — the Middlebury / Chairs rule: flow [n][Hs][Ws][2] holds the file's floats bit for bit (the 1e10
+ * "unknown" marker, infinities and NaN payloads are kept), mask [n][Hs][Ws] = (u < 1e9 && v < 1e9) ? 1 : 0 as fp32
+ * comparisons (NaN gives 0).  A padded pixel has flow +0 and mask 0. */
+int unflow_flo_to_flow_gt(const unsigned char* raw, long raw_bytes, const long* desc, int n, int Hs, int Ws, float* flow,
+                          float* mask, unflow_stream_t stream);
+
+/* unflow_sintel_gt — Sintel's composition of a .flo file with its `invalid` and `occlusions` PNGs, fused.  desc holds 3 n rows,
+ * column-major: rows [0, n) the .flo files (in `raw`), [n, 2n) the invalid PNGs and [2n, 3n) the occlusion PNGs, both in
+ * `decoded` as unflow_png_unfilter leaves them (8 / 16-bit grey, grey + alpha, RGB or RGBA; the sample read is channel 0, a
+ * 16-bit sample's high byte).  With inv = sample != 0 and occ = sample != 0 (0 or 1, 0 in the padding):
+ *   flow [2][n][Hs][Ws][2]: map 0 (occluded) = the file's floats, map 1 (non-occluded) = flow * (1 - occ), an fp32 product
+ *                           (-0 under an occluded negative component);
+ *   mask [2][n][Hs][Ws]:    map 0 = 1 - inv, map 1 = (1 - inv) * (1 - occ).
+ * The padding is applied before the composition: a padded pixel has flow 0 and both masks 1.  An example with any of its
+ * three rows invalid is skipped whole. */
+int unflow_sintel_gt(const unsigned char* raw, long raw_bytes, const unsigned char* decoded, long decoded_bytes, const long* desc,
+                     int n, int Hs, int Ws, float* flow, float* mask, unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,12 @@ temporary directory — one with every row Paeth, one with a mix of the five fil
                 handed to the pool -> last staged; the sum of the workers' own times), upload, unflow_png_unfilter,
                 unflow_png_to_window and unflow_png_to_flow_gt.
 
+--dataset sintel measures the .flo input instead: a Sintel tree of two scenes of five frames (436 x 1024: 8-bit RGB
+frames in both passes, a mix of the five filters per row; .flo flow files; 8-bit grey invalid and occlusion maps), and
+SintelInput.input_train_clean at dims 512 x 1024, batch 4 — batches per second of the host iterator (over --host-examples examples,
+at least one batch) and of the device iterator (over --examples behind --warmup batches, the device drained at the end), with the
+device iterator's stage times (the .flo bodies count under inflate: they are read, not inflated).  One JSON line, no threshold.
+
 The host figures of (a) run in this process without a GPU.  Every GPU measurement is a child process of its own under its own time
 limit; after a child that failed or ran out of time nothing more is started on the GPU.  The host-fed evaluate reads batches of
 one example, so that its clock covers exactly the examples it counts."""
@@ -96,6 +102,104 @@ def write_trees(root):
 class Data:
     def __init__(self, root):
         self.current_dir = root
+
+
+# ------------------------------------------------------------------------------------------------------------- sintel
+SINTEL_FRAME = (436, 1024)
+SINTEL_DIMS = (512, 1024)
+SINTEL_SCENES = (5, 5)     # frames per scene: 8 pairs
+
+
+def encode_grey(arr, filters):
+    """uint8 [h, w] -> 8-bit greyscale PNG, row y filtered by filters[y]."""
+    def chunk(t, body):
+        return struct.pack('>I', len(body)) + t + body + struct.pack('>I', zlib.crc32(t + body) & 0xffffffff)
+    h, w = arr.shape
+    stream = filter_rows(arr, 1, filters).tobytes()
+    return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 0, 0, 0, 0)) +
+            chunk(b'IDAT', zlib.compress(stream, 6)) + chunk(b'IEND', b''))
+
+
+def write_sintel_tree(root):
+    import numpy as np
+    from unflow_amd.core.input import write_flo
+    rs = np.random.RandomState(0)
+    h, w = SINTEL_FRAME
+    yy, xx = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+
+    def put(path, data):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, 'wb') as f:
+            f.write(data)
+    tr = os.path.join(root, 'sintel', 'training')
+    for s, n in enumerate(SINTEL_SCENES):
+        scene = 'scene_%d' % s
+        for i in range(n):
+            name = 'frame_%04d' % (i + 1)
+            for p, noise in (('clean', 3), ('final', 8)):
+                smooth = 128 + 90 * np.sin(xx / 41.0 + i + s) * np.cos(yy / 29.0 + 0.5 * i)
+                frame = np.clip(smooth[:, :, None] + np.array([0, 8, -8]) + rs.normal(0, noise, size=(h, w, 3)), 0, 255)
+                put(os.path.join(tr, p, scene, name + '.png'), encode(frame.astype(np.uint8), rs.randint(0, 5, size=h)))
+            blobs = (np.sin(xx / 53.0 + i) * np.cos(yy / 31.0 + s) > 0.8)
+            put(os.path.join(tr, 'invalid', scene, name + '.png'),
+                encode_grey((blobs & (xx < 64)).astype(np.uint8) * 255, rs.randint(0, 5, size=h)))
+            if i == n - 1:
+                continue
+            flow = np.stack([3.0 + 2.0 * np.sin(xx / 97.0 + i), -1.0 + 1.5 * np.cos(yy / 53.0)], axis=2).astype(np.float32)
+            os.makedirs(os.path.join(tr, 'flow', scene), exist_ok=True)
+            write_flo(os.path.join(tr, 'flow', scene, name + '.flo'), flow)
+            put(os.path.join(tr, 'occlusions', scene, name + '.png'), encode_grey(blobs.astype(np.uint8) * 255, rs.randint(0, 5, size=h)))
+    return root
+
+
+def sintel_input(tree):
+    from unflow_amd.sintel.input import SintelInput
+    return SintelInput(Data(tree), B, SINTEL_DIMS, normalize=False)
+
+
+def child_sintel_reader(tree, a):
+    import torch
+    from unflow_amd.core.png_device import DeviceEvalBatches
+    sin = sintel_input(tree)
+    pairs, gt = sin.train_files('sintel/training/clean')
+    examples = a.examples + a.warmup * B
+    rep = -(-examples // len(pairs))
+    cut = lambda x: (x * rep)[:examples]          # noqa: E731
+    it = DeviceEvalBatches(cut(pairs), B, SINTEL_DIMS, False, sin.mean, sin.stddev, gt_lists=[cut(g) for g in gt], gt_kind='sintel',
+                           device=torch.device('cuda:0'), workers=a.workers, prefetch=a.prefetch, timing=True)
+    for _ in range(a.warmup):
+        next(it)
+    torch.cuda.synchronize()
+    it.stage_times.clear()
+    t0, n = time.perf_counter(), 0
+    for _batch in it:
+        n += 1
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    st = stages(it)
+    st['sintel_gt_ms'] = st.pop('to_flow_gt_ms')
+    print(json.dumps(dict(batches=n, batches_per_s=round(n / dt, 3), ms_per_batch=round(1e3 * dt / n, 3), stages=st)))
+
+
+def main_sintel(a):
+    res = dict(metric='sintel_input_host_vs_device', frame=list(SINTEL_FRAME) + [3], dims=list(SINTEL_DIMS), B=B,
+               pairs=sum(n - 1 for n in SINTEL_SCENES), files_per_example=5, workers=min(a.workers, 16), prefetch=a.prefetch,
+               warmup=a.warmup)
+    with tempfile.TemporaryDirectory(prefix='eval_input_bench_') as root:
+        tree = write_sintel_tree(root)
+        print("eval_input_bench: sintel host reader", file=sys.stderr, flush=True)
+        n = max(1, -(-a.host_examples // B))
+        t0 = time.perf_counter()
+        for _, _batch in zip(range(n), sintel_input(tree).input_train_clean()):
+            pass
+        dt = time.perf_counter() - t0
+        res['host'] = dict(batches=n, batches_per_s=round(n / dt, 5), s_per_batch=round(dt / n, 3))
+        r, err = run_child(['--child', 'sintel_reader', '--dir', tree, '--examples', str(a.examples), '--warmup', str(a.warmup),
+                            '--workers', str(a.workers), '--prefetch', str(a.prefetch)], a.limit)
+        res['device'] = r if err is None else err
+        if err is None:
+            res['device_over_host'] = round(r['batches_per_s'] / res['host']['batches_per_s'], 1)
+    print(json.dumps(res))
 
 
 def kitti_input(tree, dims, normalize):
@@ -253,7 +357,7 @@ def run_child(args, limit):
     return json.loads(lines[-1]), None
 
 
-CHILDREN = ('reader', 'evaluate_device', 'evaluate_host', 'ceiling', 'fed', 'host_fed')
+CHILDREN = ('reader', 'evaluate_device', 'evaluate_host', 'ceiling', 'fed', 'host_fed')       # of --dataset kitti
 
 
 def main():
@@ -265,9 +369,14 @@ def main():
     ap.add_argument('--workers', type=int, default=16)
     ap.add_argument('--prefetch', type=int, default=2)
     ap.add_argument('--limit', type=int, default=240, help='time limit of each GPU child, seconds (the host-fed children get their measured decode time on top)')
-    ap.add_argument('--child', choices=CHILDREN, help=argparse.SUPPRESS)
+    ap.add_argument('--dataset', choices=('kitti', 'sintel'), default='kitti', help='sintel: the .flo input alone (see above)')
+    ap.add_argument('--child', choices=CHILDREN + ('sintel_reader',), help=argparse.SUPPRESS)
     ap.add_argument('--dir', help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.child == 'sintel_reader':
+        return child_sintel_reader(a.dir, a)
+    if a.dataset == 'sintel' and not a.child:
+        return main_sintel(a)
     if a.child == 'reader':
         return child_reader(a.dir, a)
     if a.child in ('evaluate_device', 'evaluate_host'):

@@ -48,6 +48,8 @@ def lib():
         _lib.unflow_png_unfilter_rows.restype = ctypes.c_int
         _lib.unflow_png_to_window.restype = ctypes.c_int
         _lib.unflow_png_to_flow_gt.restype = ctypes.c_int
+        _lib.unflow_flo_to_flow_gt.restype = ctypes.c_int
+        _lib.unflow_sintel_gt.restype = ctypes.c_int
         _apply_env_options(_lib)
     return _lib
 

@@ -14,9 +14,16 @@ order, same crop draws, bit-identical batches) with the next batches in flight o
 DeviceGTBatches is the twin of KITTIInput.input_train_gt (supervised fine-tuning) and DeviceEvalBatches of the evaluation
 readers (KITTIInput.input_train_2012 / 2015, input_test_*): the same pipeline over a list of files per batch, each with a
 role (frame or ground truth) and an origin.
+.flo ground truth (Sintel, FlyingChairs, Middlebury) rides the same ring: a .flo body needs no inflate, so a worker reads it
+straight into the pinned staging slot and csrc/flo_decode.hip cuts the window and derives the masks —
+
+  * unflow_flo_to_flow_gt the Middlebury / Chairs rule: the file's floats and mask = both components < 1e9;
+  * unflow_sintel_gt      Sintel's composition of a .flo file with its `invalid` and `occlusions` PNGs -> two maps.
+
 There is no host fallback: without the library's kernels these raise."""
 import collections
 import ctypes
+import os
 import queue
 import struct
 import threading
@@ -29,9 +36,12 @@ import torch
 
 from .. import _lib
 from .._lib import check, ptr
+from .input import FLO_TAG
 
 PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
 _CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
+FLO_HEADER_BYTES = 12    # tag, width, height
+FLO_ALIGN = 16           # a .flo body's offset in the staging buffer (the kernels need 4; 16 keeps whole-pair and wider loads open)
 MAX_WORKERS = 16         # a command's CPU budget on a GPU box; never sized from os.cpu_count()
 
 
@@ -91,6 +101,22 @@ def png_header(path):
     w, h, depth, ctype, _, _, interlace = hdr
     _check_variant(depth, ctype, interlace)
     return h, w, depth, ctype
+
+
+def flo_header(path):
+    """(h, w) of a .flo file: the tag 202021.25, a positive width and height, and a file of exactly 12 + 8 * w * h bytes;
+    anything else raises ValueError naming the file."""
+    with open(path, 'rb') as f:
+        head = f.read(12)
+        size = os.fstat(f.fileno()).st_size
+    if len(head) < 12 or struct.unpack('<f', head[:4])[0] != FLO_TAG:
+        raise ValueError("%s: not a .flo file (no 'PIEH' tag)" % path)
+    w, h = struct.unpack('<ii', head[4:])
+    if w <= 0 or h <= 0:
+        raise ValueError("%s: a .flo file of %d x %d" % (path, h, w))
+    if size != FLO_HEADER_BYTES + 8 * w * h:
+        raise ValueError("%s: a %d x %d .flo file has %d bytes, this one %d" % (path, h, w, FLO_HEADER_BYTES + 8 * w * h, size))
+    return h, w
 
 
 def _bpp(depth, ctype):
@@ -171,6 +197,16 @@ def _to_flow_gt(dec_dev, n_dec, table_dev, n, H, W, flow, mask, stream):
                                            _stream_ptr(stream)), "png_to_flow_gt")
 
 
+def _flo_to_flow_gt(raw_dev, n_raw, table_dev, n, H, W, flow, mask, stream):
+    check(_lib.lib().unflow_flo_to_flow_gt(ptr(raw_dev), _lib.cl(n_raw), ptr(table_dev), n, H, W, ptr(flow), ptr(mask),
+                                           _stream_ptr(stream)), "flo_to_flow_gt")
+
+
+def _sintel_gt(raw_dev, n_raw, dec_dev, n_dec, table_dev, n, H, W, flow, mask, stream):
+    check(_lib.lib().unflow_sintel_gt(ptr(raw_dev), _lib.cl(n_raw), ptr(dec_dev), _lib.cl(n_dec), ptr(table_dev), n, H, W,
+                                      ptr(flow), ptr(mask), _stream_ptr(stream)), "sintel_gt")
+
+
 class PairPlanner:
     """The host-only half of DevicePairBatches: which files form the next batch and where they are cropped.  Walks the pair list
     as RawPairBatches does (in order, cyclically, `batch_size` examples per batch) and makes the same
@@ -221,7 +257,26 @@ def _inflate_into(path, meta, dst):
     return time.perf_counter() - t0
 
 
-FRAME, GT = 'frame', 'gt'        # a file's role: through unflow_png_to_batch / _to_window, or through unflow_png_to_flow_gt
+def _read_flo_into(path, meta, dst):
+    """Worker: the body of a .flo file -> `dst`, a numpy view of the pinned staging slot (no intermediate copy, nothing to
+    inflate).  Returns the seconds it took."""
+    t0 = time.perf_counter()
+    with open(path, 'rb') as f:
+        head = f.read(FLO_HEADER_BYTES)
+        ok = len(head) == FLO_HEADER_BYTES and struct.unpack('<fii', head) == (FLO_TAG, meta[1], meta[0])
+        if not ok or f.readinto(memoryview(dst)) != dst.size or f.read(1):
+            raise ValueError("%s changed on disk while it was being read" % path)
+    return time.perf_counter() - t0
+
+
+# A file's role: FRAME through unflow_png_to_batch / _to_window, GT (a KITTI flow PNG) through unflow_png_to_flow_gt, FLO (a .flo
+# body, never unfiltered) through unflow_flo_to_flow_gt or, with its two MASK PNGs (Sintel's invalid and occlusions), through
+# unflow_sintel_gt.  A batch's table holds its files in TABLE_ORDER, so the PNG rows are one run (one unfilter launch) and
+# the rows of unflow_sintel_gt another.
+FRAME, GT, FLO, MASK = 'frame', 'gt', 'flo', 'mask'
+TABLE_ORDER = (FLO, MASK, FRAME, GT)
+GT_KINDS = {'kitti': None, 'flo': (FLO,), 'sintel': (FLO, MASK, MASK)}       # roles of the ground-truth lists (kitti: GT each)
+NO_GT = 'none'           # what gt_kind=None means without lists: a test split, frames only
 
 
 def window_origin(n, size):
@@ -278,17 +333,37 @@ class GTPlanner(PairPlanner):
 class EvalPlanner(PairPlanner):
     """The host-only half of DeviceEvalBatches: one pass over the pair list, `batch_size` examples per batch (a short last one),
     ground-truth files position by position as KITTIInput._input_train pairs them; every file gets the origin of
-    resize_image_with_crop_or_pad for its OWN size (window_origin)."""
+    resize_image_with_crop_or_pad for its OWN size (window_origin).
+    gt_kind: None — no lists: a test split, frames only (with lists, for the callers of 7.7: 'kitti'); 'kitti' — every list holds
+    KITTI flow PNGs, one map each; 'flo' — one list of .flo files, one map (Middlebury,
+    FlyingChairs); 'sintel' — three lists (.flo, invalid PNGs, occlusion PNGs), two maps.  A .flo file is checked by flo_header,
+    and a Sintel mask whose size differs from its .flo's raises ValueError naming it."""
 
-    def __init__(self, pairs, batch_size, dims, gt_lists=()):
+    def __init__(self, pairs, batch_size, dims, gt_lists=(), gt_kind=None):
         super().__init__(pairs, batch_size, dims, False, 0)
         self.gt_lists = [list(g) for g in gt_lists]
+        if gt_kind is None:
+            gt_kind = 'kitti' if self.gt_lists else NO_GT
+        elif gt_kind not in GT_KINDS:
+            raise ValueError("gt_kind must be None or one of %s, got %r" % (sorted(GT_KINDS), gt_kind))
+        self.gt_kind = gt_kind
+        self.gt_roles = GT_KINDS.get(gt_kind) or (GT,) * len(self.gt_lists)
+        if len(self.gt_lists) != len(self.gt_roles):
+            raise ValueError("gt_kind %r takes %d ground-truth lists, got %d" % (gt_kind, len(self.gt_roles), len(self.gt_lists)))
+        self.n_maps = {NO_GT: 0, 'kitti': len(self.gt_lists), 'flo': 1, 'sintel': 2}[gt_kind]
         for g in self.gt_lists:
             if len(g) != len(self.pairs):
                 raise ValueError("%d ground-truth files for %d pairs" % (len(g), len(self.pairs)))
 
+    def header(self, path, role=FRAME):
+        if role != FLO:
+            return super().header(path)
+        if path not in self._headers:
+            self._headers[path] = flo_header(path)
+        return self._headers[path]
+
     def _file(self, path, role):
-        m = self.header(path)
+        m = self.header(path, role)
         if role == GT:
             check_gt_header(path, m)
         return (path, m, role, window_origin(m[0], self.dims[0]), window_origin(m[1], self.dims[1]))
@@ -301,7 +376,11 @@ class EvalPlanner(PairPlanner):
         out = []
         for k in range(self.pos, min(self.pos + self.batch_size, len(self.pairs))):
             fn1, fn2 = self.pairs[k]
-            out.append([self._file(fn1, FRAME), self._file(fn2, FRAME)] + [self._file(g[k], GT) for g in self.gt_lists])
+            ex = [self._file(fn1, FRAME), self._file(fn2, FRAME)] + [self._file(g[k], r) for g, r in zip(self.gt_lists, self.gt_roles)]
+            for f in ex[3:] if self.gt_kind == 'sintel' else ():
+                if f[1][:2] != ex[2][1][:2]:
+                    raise ValueError("%s is %d x %d, its flow file %s %d x %d" % ((f[0],) + f[1][:2] + (ex[2][0],) + ex[2][1][:2]))
+            out.append(ex)
         self.pos += len(out)
         return out
 
@@ -310,20 +389,26 @@ class EvalPlanner(PairPlanner):
         """Column-major: all first frames, all second frames, then each ground-truth list."""
         return [ex[c] for c in range(len(examples[0])) for ex in examples]
 
+    @classmethod
+    def table_files(cls, examples):
+        """files() with the columns in TABLE_ORDER (stable): .flo files, Sintel's masks, the frames, KITTI maps."""
+        cols = sorted(range(len(examples[0])), key=lambda c: TABLE_ORDER.index(examples[0][c][2]))
+        return [ex[c] for c in cols for ex in examples]
+
 
 class _Slot:
     """Staging and output of one batch in flight.  Every buffer is allocated (and grown) on the CONSUMER's thread, see
     _DeviceBatches._schedule."""
 
-    def __init__(self, n_frames, n_gt, H, W, dev):
-        n = n_frames + n_gt
+    def __init__(self, n_rows, n_frames, n_maps, H, W, dev):
+        n = n_rows                                # table rows: the batch's files; n_maps ground-truth maps come out of them
         self.staging = None                       # pinned uint8: the batch's inflated streams, back to back
         self.table_host = torch.empty(n, _lib.PNG_DESC_FIELDS, dtype=torch.int64).pin_memory()
         self.table = torch.empty(n, _lib.PNG_DESC_FIELDS, dtype=torch.int64, device=dev)
         self.raw = self.dec = None                # device: inflated streams, decoded frames
         self.out = torch.empty(n_frames, H, W, 3, dtype=torch.float32, device=dev)
-        self.flow = torch.empty(n_gt, H, W, 2, dtype=torch.float32, device=dev) if n_gt else None
-        self.mask = torch.empty(n_gt, H, W, 1, dtype=torch.float32, device=dev) if n_gt else None
+        self.flow = torch.empty(n_maps, H, W, 2, dtype=torch.float32, device=dev) if n_maps else None
+        self.mask = torch.empty(n_maps, H, W, 1, dtype=torch.float32, device=dev) if n_maps else None
         self.uploaded = None                      # side-stream event: the pinned buffers have been read
 
     def reserve(self, n_raw, n_dec, dev):
@@ -339,19 +424,28 @@ class _Slot:
 
 
 class _Job:
-    """One batch: its slot, its files [(file, header, role, oy, ox)] (the frames first, then the ground-truth maps), the kernels'
-    table rows, each file's span in the staging buffer, the byte totals, the workers' futures and the event behind which the slot
-    may be rewritten.  `plan` is what the planner returned (the iterator builds its result from it)."""
+    """One batch: its slot, its files [(file, header, role, oy, ox)] in TABLE_ORDER (.flo files, Sintel's masks, the frames,
+    KITTI maps), the kernels' table rows, each file's span in the staging buffer, the byte totals, the workers' futures and the
+    event behind which the slot may be rewritten.  A .flo span starts at a multiple of FLO_ALIGN: the PNG streams around it have
+    arbitrary lengths, and the kernels read its floats in place.  `plan` is what the planner returned (the iterator builds
+    its result from it)."""
 
     def __init__(self, slot, files, plan=None):
         self.slot, self.files, self.plan = slot, files, plan
-        self.n_frames = sum(1 for f in files if f[2] == FRAME)
-        self.n_gt = len(files) - self.n_frames
-        assert all(f[2] == FRAME for f in files[:self.n_frames]) and all(f[2] == GT for f in files[self.n_frames:])
+        roles = [f[2] for f in files]
+        self.n_flo, self.n_mask, self.n_frames, self.n_gt = (roles.count(r) for r in TABLE_ORDER)
+        assert roles == sorted(roles, key=TABLE_ORDER.index) and self.n_mask in (0, 2 * self.n_flo)
         self.rows, self.spans, src, dst = [], [], 0, 0
-        for _, (h, w, depth, ctype), _, oy, ox in self.files:
-            n_in, n_out = h * (w * _bpp(depth, ctype) + 1), h * w * _bpp(depth, ctype)
-            self.rows.append(_table_row(src, dst, h, w, depth, ctype, oy, ox))
+        for _, meta, role, oy, ox in self.files:
+            if role == FLO:
+                h, w = meta
+                src = -(-src // FLO_ALIGN) * FLO_ALIGN
+                n_in, n_out = 8 * h * w, 0
+                self.rows.append((src, 0, h, w, 8, 4, oy, ox))
+            else:
+                h, w, depth, ctype = meta
+                n_in, n_out = h * (w * _bpp(depth, ctype) + 1), h * w * _bpp(depth, ctype)
+                self.rows.append(_table_row(src, dst, h, w, depth, ctype, oy, ox))
             self.spans.append((src, n_in))
             src, dst = src + n_in, dst + n_out
         self.n_raw, self.n_dec = src, dst
@@ -395,6 +489,7 @@ class _Pipeline:
     def _produce(self, job):
         slot, (H, W) = job.slot, self.dims
         n, nf = len(job.rows), job.n_frames
+        f0 = job.n_flo + job.n_mask                            # the first frame's row; the PNG rows start behind the .flo rows
         slot.table_host[:n].copy_(torch.tensor(job.rows, dtype=torch.int64))
         errors = [f.exception() for f in job.futures]         # waits for every worker: none is left writing into the slot
         job.times['inflate_s'] = time.perf_counter() - job.submitted          # submit -> last frame staged
@@ -409,13 +504,17 @@ class _Pipeline:
             slot.raw[:job.n_raw].copy_(slot.staging[:job.n_raw], non_blocking=True)
             slot.table[:n].copy_(slot.table_host[:n], non_blocking=True)
             marks[1].record(self.side)
-            _unfilter(slot.raw, job.n_raw, slot.dec, job.n_dec, slot.table, n, self.side)
+            _unfilter(slot.raw, job.n_raw, slot.dec, job.n_dec, slot.table[job.n_flo:], n - job.n_flo, self.side)
             marks[2].record(self.side)
             to_frames = _to_window if self.window else _to_batch
-            to_frames(slot.dec, job.n_dec, slot.table, nf, H, W, self.mean, self.stddev, slot.out, self.side)
+            to_frames(slot.dec, job.n_dec, slot.table[f0:], nf, H, W, self.mean, self.stddev, slot.out, self.side)
             marks[3].record(self.side)
             if job.n_gt:
-                _to_flow_gt(slot.dec, job.n_dec, slot.table[nf:], job.n_gt, H, W, slot.flow, slot.mask, self.side)
+                _to_flow_gt(slot.dec, job.n_dec, slot.table[f0 + nf:], job.n_gt, H, W, slot.flow, slot.mask, self.side)
+            elif job.n_mask:
+                _sintel_gt(slot.raw, job.n_raw, slot.dec, job.n_dec, slot.table, job.n_flo, H, W, slot.flow, slot.mask, self.side)
+            elif job.n_flo:
+                _flo_to_flow_gt(slot.raw, job.n_raw, slot.table, job.n_flo, H, W, slot.flow, slot.mask, self.side)
             marks[4].record(self.side)
         slot.uploaded, job.marks, job.ready = marks[1], marks, marks[4]
 
@@ -445,7 +544,7 @@ class _DeviceBatches:
     staging and hands the batch's files to the workers — everything that allocates or synchronises happens on the consumer's
     thread, between steps.  close() (and garbage collection) stops the threads.  Threads only: no other process opens the GPU."""
 
-    def __init__(self, n_frames, n_gt, dims, mean, stddev, device, workers, prefetch, timing, window):
+    def __init__(self, n_rows, n_frames, n_maps, dims, mean, stddev, device, workers, prefetch, timing, window):
         if prefetch < 1:
             raise ValueError("prefetch must be at least 1")
         self.device = _device(device)
@@ -459,7 +558,7 @@ class _DeviceBatches:
         self._timed = collections.deque()
         try:
             with torch.cuda.device(self.device):
-                slots = [_Slot(n_frames, n_gt, self.dims[0], self.dims[1], self.device) for _ in range(prefetch + 1)]
+                slots = [_Slot(n_rows, n_frames, n_maps, self.dims[0], self.dims[1], self.device) for _ in range(prefetch + 1)]
             # (slot, event on the current stream behind which the side stream may write it)
             self._free = collections.deque((s, self._mark()) for s in slots)
             for _ in range(prefetch):
@@ -498,7 +597,8 @@ class _DeviceBatches:
         # the workers start now, so the frames of every batch in flight share the pool; the producer thread takes the batches in order
         stage = slot.staging.numpy()
         job.submitted = time.perf_counter()
-        job.futures = [self._pipe.pool.submit(_inflate_into, f[0], f[1], stage[o:o + n]) for f, (o, n) in zip(job.files, job.spans)]
+        job.futures = [self._pipe.pool.submit(_read_flo_into if f[2] == FLO else _inflate_into, f[0], f[1], stage[o:o + n])
+                       for f, (o, n) in zip(job.files, job.spans)]
         self._inflight.append(job)
         self._pipe.jobs.put(job)
         return True
@@ -539,7 +639,7 @@ class _DeviceBatches:
             m = j.marks
             t = dict(j.times, upload_ms=m[0].elapsed_time(m[1]), unfilter_ms=m[1].elapsed_time(m[2]),
                      to_batch_ms=m[2].elapsed_time(m[3]))
-            if j.n_gt:
+            if j.n_gt or j.n_flo:
                 t['flow_gt_ms'] = m[3].elapsed_time(m[4])
             self.stage_times.append(t)
 
@@ -567,7 +667,7 @@ class DevicePairBatches(_DeviceBatches):
         self.planner = PairPlanner(pairs, batch_size, dims, needs_crop, seed)
         self.batch_size = batch_size
         mean, stddev = _norm(normalize, mean, stddev)
-        super().__init__(2 * batch_size, 0, dims, mean, stddev, device, workers, prefetch, timing, window=False)
+        super().__init__(2 * batch_size, 2 * batch_size, 0, dims, mean, stddev, device, workers, prefetch, timing, window=False)
 
     def _plan(self):
         examples = self.planner.next_batch()
@@ -591,7 +691,7 @@ class DeviceGTBatches(_DeviceBatches):
         self.planner = GTPlanner(files, batch_size, dims, seed, shift)
         self.batch_size = batch_size
         mean, stddev = _norm(normalize, mean, stddev)
-        super().__init__(2 * batch_size, batch_size, dims, mean, stddev, device, workers, prefetch, timing, window=True)
+        super().__init__(3 * batch_size, 2 * batch_size, batch_size, dims, mean, stddev, device, workers, prefetch, timing, window=True)
 
     def _plan(self):
         examples = self.planner.next_batch()
@@ -606,24 +706,27 @@ class DeviceEvalBatches(_DeviceBatches):
     """The device twin of KITTIInput._input_train (gt_lists = the flow_occ and flow_noc files) and Input.input_test (no ground
     truth): one pass, a short last batch, the host iterator's tuples — im1, im2 [n,Hs,Ws,3] on the device, input_shape [n,3]
     int32 on the HOST (from im1's IHDR) and per ground-truth list flow [n,Hs,Ws,2], mask [n,Hs,Ws,1] — every tensor equal to the
-    host's bit for bit (crop or zero padding per file as resize_image_with_crop_or_pad, normalisation after the padding)."""
+    host's bit for bit (crop or zero padding per file as resize_image_with_crop_or_pad, normalisation after the padding).
+    gt_kind (EvalPlanner): None with no lists is a test split (3-tuples), 'flo' is the twin of ChairsInput.input_test /
+    MiddleburyInput.input_train (gt_lists = the .flo files; 5-tuples), 'sintel' of SintelInput.input_train_* (gt_lists = the .flo, invalid and occlusion files; 7-tuples: flow_occ,
+    mask_occ, flow_noc, mask_noc)."""
 
     def __init__(self, pairs, batch_size, dims, normalize, mean, stddev, gt_lists=(), device=None, workers=8, prefetch=2,
-                 timing=False):
-        self.planner = EvalPlanner(pairs, batch_size, dims, gt_lists)
+                 timing=False, gt_kind=None):
+        self.planner = EvalPlanner(pairs, batch_size, dims, gt_lists, gt_kind)
         self.batch_size = batch_size
         mean, stddev = _norm(normalize, mean, stddev)
-        super().__init__(2 * batch_size, len(self.planner.gt_lists) * batch_size, dims, mean, stddev, device, workers, prefetch,
-                         timing, window=True)
+        super().__init__((2 + len(self.planner.gt_lists)) * batch_size, 2 * batch_size, self.planner.n_maps * batch_size, dims, mean,
+                         stddev, device, workers, prefetch, timing, window=True)
 
     def _plan(self):
         examples = self.planner.next_batch()
-        return None if examples is None else (self.planner.files(examples), examples)
+        return None if examples is None else (self.planner.table_files(examples), examples)
 
     def _result(self, job):
         n, s = len(job.plan), job.slot
         shapes = np.asarray([(ex[0][1][0], ex[0][1][1], 3) for ex in job.plan], dtype=np.int32)
         out = [s.out[:n], s.out[n:2 * n], shapes]
-        for g in range(len(self.planner.gt_lists)):
+        for g in range(self.planner.n_maps):
             out += [s.flow[g * n:(g + 1) * n], s.mask[g * n:(g + 1) * n]]
         return tuple(out)

@@ -11,7 +11,7 @@ The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives
 --output_backward branch means to write).  --occlusion runs both directions and adds the forward-backward occlusion mask
 (losses.occlusion): this project's occlusion precision / recall / F1 against KITTI's occluded pixels on train_* variants,
 and %06d_10_occ.png (8-bit, 255 = occluded) with --output_benchmark.  The pictures (colour wheel, error map, overlay) are
-python -m unflow_amd.visualize's; other datasets are not supported."""
+python -m unflow_amd.visualize's; Sintel, FlyingChairs and Middlebury are python -m unflow_amd.evaluate_flo's."""
 import argparse
 import os
 import shutil
@@ -25,7 +25,7 @@ UNSUPPORTED = {'output_visual': "--output_visual is not supported here: python -
 def parser():
     ap = argparse.ArgumentParser(prog='python -m unflow_amd.evaluate', description=__doc__.split('\n')[0])
     ap.add_argument('--ex', required=True, help='experiment name')
-    ap.add_argument('--dataset', default='kitti', help="only 'kitti' is supported")
+    ap.add_argument('--dataset', default='kitti', help="only 'kitti' (sintel / chairs / mdb: python -m unflow_amd.evaluate_flo)")
     ap.add_argument('--variant', default='train_2012', choices=VARIANTS)
     ap.add_argument('--num', type=int, default=10, help='examples to evaluate; -1: all (eval_gui.py --num)')
     ap.add_argument('--output_benchmark', action='store_true', help='write the benchmark flow files')
@@ -50,8 +50,8 @@ def parse_args(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     if a.dataset != 'kitti':
-        ap.error("--dataset %s is not supported (only kitti; sintel / chairs / mdb inputs are not part of this project)"
-                 % a.dataset)
+        ap.error("--dataset %s is not supported here (only kitti; python -m unflow_amd.evaluate_flo scores and draws sintel / "
+                 "chairs / mdb)" % a.dataset)
     for k, msg in UNSUPPORTED.items():
         if getattr(a, k):
             ap.error(msg)

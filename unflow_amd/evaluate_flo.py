@@ -1,0 +1,157 @@
+"""python -m unflow_amd.evaluate_flo: score a trained experiment on Sintel, FlyingChairs or Middlebury, write benchmark files and
+pictures — the rest of the reference's src/eval_gui.py (:303-322), beside python -m unflow_amd.evaluate (KITTI).
+
+    python -m unflow_amd.evaluate_flo --dataset {sintel,chairs,mdb} --ex NAME [--variant ...] [--num 10] [--batch_size 4]
+                                      [--occlusion] [--output_benchmark [--output_png] [--output_backward]]
+                                      [--visual [--sheet]] [--host_decode] [--dims H W]
+
+Variants: sintel train_clean (default), train_final, test_clean, test_final; chairs test; mdb train (default), test.  The
+network input size defaults to eval_gui.py's: 512 x 1024, 384 x 512, 512 x 640.  The experiment, its config ([train] and
+[train_<dataset>]) and its checkpoint are found as python -m unflow_amd.evaluate finds them.  The frames, the .flo ground truth
+and Sintel's masks are decoded on the device (core/png_device.py) unless --host_decode.  On variants with ground truth the
+scores are printed: AEE/<map> and outliers/<map> — occluded and non-occluded on Sintel, all on the one-map datasets — and, on
+Sintel with --occlusion, this project's occlusion precision / recall / F1 of the forward-backward mask against Sintel's
+occlusion maps.  --output_benchmark and --visual write through FlowEstimator.export to <--out>/NAME/: %06d_10.flo (or .png),
+with --output_backward %06d_01, with --occlusion %06d_10_occ.png, with --visual the pictures of python -m unflow_amd.visualize
+(--sheet: its contact sheets, too)."""
+import argparse
+import os
+import shutil
+import sys
+
+from .evaluate import experiment_paths
+
+DATASETS = {      # variants (the first is the default), eval_gui.py's dims
+    'sintel': (('train_clean', 'train_final', 'test_clean', 'test_final'), (512, 1024)),
+    'chairs': (('test',), (384, 512)),
+    'mdb': (('train', 'test'), (512, 640)),
+}
+WITH_GT = {('sintel', 'train_clean'), ('sintel', 'train_final'), ('chairs', 'test'), ('mdb', 'train')}
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m unflow_amd.evaluate_flo', description=__doc__.split('\n')[0])
+    ap.add_argument('--ex', required=True, help='experiment name')
+    ap.add_argument('--dataset', required=True, choices=sorted(DATASETS), help='kitti: python -m unflow_amd.evaluate')
+    ap.add_argument('--variant', default=None, help='the split, see above (default: the first of the dataset)')
+    ap.add_argument('--num', type=int, default=10, help='examples to evaluate; -1: all (eval_gui.py --num)')
+    ap.add_argument('--num_vis', type=int, default=100, help='examples on the contact sheets (eval_gui.py --num_vis)')
+    ap.add_argument('--output_benchmark', action='store_true', help='write the flow files')
+    ap.add_argument('--output_png', action='store_true', help='KITTI 16-bit PNG files (default: .flo)')
+    ap.add_argument('--output_backward', action='store_true', help='with --output_benchmark: also the backward flow (%%06d_01)')
+    ap.add_argument('--occlusion', action='store_true',
+                    help='forward-backward occlusion: scores on Sintel train_*, %%06d_10_occ.png with --output_benchmark')
+    ap.add_argument('--visual', action='store_true', help='write the pictures (overlay, flow colours, errors) beside the flow files')
+    ap.add_argument('--sheet', action='store_true', help='with --visual: also page_%%03d.png contact sheets, four examples per page')
+    ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
+    ap.add_argument('--host_decode', action='store_true',
+                    help="read the files with the host's decoders (slow) instead of the library's kernels")
+    ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
+    ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
+    ap.add_argument('--dims', type=int, nargs=2, default=None, metavar=('H', 'W'), help="network input size (default: eval_gui.py's)")
+    return ap
+
+
+def parse_args(argv=None):
+    """Parsed flags with the dataset's defaults filled in (variant, dims; num = None for all); refuses what this tool does not
+    do with a clear message (SystemExit, status 2)."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    variants, dims = DATASETS[a.dataset]
+    if a.variant is None:
+        a.variant = variants[0]
+    if a.variant not in variants:
+        ap.error("--variant %s: --dataset %s has %s" % (a.variant, a.dataset, ', '.join(variants)))
+    a.dims = tuple(a.dims) if a.dims else dims
+    a.num = None if a.num < 0 else a.num
+    a.has_gt = (a.dataset, a.variant) in WITH_GT
+    if a.output_backward and not a.output_benchmark:
+        ap.error("--output_backward requires --output_benchmark")
+    if a.sheet and not a.visual:
+        ap.error("--sheet requires --visual")
+    if a.batch_size <= 0:
+        ap.error("--batch_size must be positive")
+    if a.num_vis < 0:
+        ap.error("--num_vis must not be negative")
+    return a
+
+
+class _Data:
+    """What the inputs need of the reference's Data classes: the data root (dirs.data)."""
+
+    def __init__(self, root):
+        self.current_dir = root
+
+    def get_raw_dirs(self):
+        return []
+
+
+def dataset_input(dataset, root, batch_size, dims):
+    if dataset == 'sintel':
+        from .sintel.input import SintelInput as cls
+    elif dataset == 'chairs':
+        from .chairs.input import ChairsInput as cls
+    else:
+        from .middlebury.input import MiddleburyInput as cls
+    return cls(_Data(root), batch_size=batch_size, normalize=False, dims=tuple(dims))
+
+
+def write_sheets(out_dir, n_examples, has_gt, num_vis):
+    """The contact sheets of python -m unflow_amd.visualize --sheet over the first num_vis examples, put together from the
+    picture files export(visual=True) has just written to out_dir (read back: no further pass over the input and the network);
+    returns the written paths."""
+    from .core.inference import VISUAL_IMAGES, visual_files
+    from .core.input import decode_png, write_png_rgb8
+    from .visualize import EXAMPLES_PER_PAGE, SHEET_COLUMNS, contact_sheet, sheet_name
+    rows = []
+    for n in range(min(n_examples, num_vis)):
+        files = {VISUAL_IMAGES[k]: os.path.join(out_dir, name) for k, name in visual_files(n, has_gt)}
+        row = []
+        for column in SHEET_COLUMNS[has_gt]:
+            with open(files[column], 'rb') as f:
+                row.append(decode_png(f.read()))
+        rows.append(row)
+    paths = []
+    for page, r0 in enumerate(range(0, len(rows), EXAMPLES_PER_PAGE)):
+        paths.append(os.path.join(out_dir, sheet_name(page)))
+        write_png_rgb8(paths[-1], contact_sheet(rows[r0:r0 + EXAMPLES_PER_PAGE]))
+    return paths
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from .core.util import config_dict, convert_input_strings
+    from .core.inference import OCC_NAMES, FlowEstimator
+    cfg_path, ckpt_dir = experiment_paths(a.ex, a.config)
+    config = config_dict(cfg_path)
+    params = dict(config.get('train', {}))
+    dirs = config_dict(a.config).get('dirs', {})
+    convert_input_strings(params, dirs)
+    params.update(config.get('train_' + a.dataset, {}))
+    est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch_size, net_size=a.dims,
+                                        bidirectional=a.output_backward or a.occlusion, visual=a.visual)
+    dinput = dataset_input(a.dataset, dirs.get('data', ''), a.batch_size, a.dims)
+    dev = None if a.host_decode else est.dev
+    batches = lambda: getattr(dinput, 'input_' + a.variant)(device=dev)            # noqa: E731
+    print("-- evaluating %s (step %s) on %s %s" % (a.ex, est.global_step, a.dataset, a.variant))
+    if a.has_gt:
+        res = est.evaluate(batches(), num=a.num)
+        for k in res['names'] + [k for k in OCC_NAMES if a.occlusion and k in res]:
+            print("%-24s %.4f" % (k, res[k]))
+        print("examples: %d" % res['num_examples'])
+    if a.output_benchmark or a.visual:
+        out_dir = os.path.join(a.out, a.ex)
+        if os.path.isdir(out_dir):
+            shutil.rmtree(out_dir)
+        os.makedirs(out_dir)
+        shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
+        paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=a.num, backward=a.output_backward,
+                           occlusion=a.occlusion, visual=a.visual)
+        if a.sheet:
+            paths += write_sheets(out_dir, sum(p.endswith('_img.png') for p in paths), a.has_gt, a.num_vis)
+        print("wrote %d files to %s" % (len(paths), out_dir))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -11,7 +11,7 @@ occluded) and %06d_gt.png (the ground truth's colour wheel).  eval_gui.py --outp
 into _flow.png and the flow colours into _err.png and never writes the error map; the names' evident meaning is followed.
 --sheet: the pages of its window (e2eflow/gui.py: four examples each) as contact sheets page_%03d.png over the first --num_vis
 examples: one row per example, one column per image slot of eval_gui.py:160-204, smaller frames padded with black.  There is
-no window on screen, and only --dataset kitti."""
+no window on screen, and only --dataset kitti (the other datasets: python -m unflow_amd.evaluate_flo --visual)."""
 import argparse
 import os
 import sys
@@ -28,7 +28,7 @@ SHEET_COLUMNS = {True: ('overlay', 'warp_error', 'flow', 'gt', 'error'), False: 
 def parser():
     ap = argparse.ArgumentParser(prog='python -m unflow_amd.visualize', description=__doc__.split('\n')[0])
     ap.add_argument('--ex', required=True, help='experiment name')
-    ap.add_argument('--dataset', default='kitti', help="only 'kitti' is supported")
+    ap.add_argument('--dataset', default='kitti', help="only 'kitti' (sintel / chairs / mdb: python -m unflow_amd.evaluate_flo)")
     ap.add_argument('--variant', default='train_2012', choices=VARIANTS)
     ap.add_argument('--num', type=int, default=10, help='examples to process; -1: all (eval_gui.py --num)')
     ap.add_argument('--num_vis', type=int, default=100, help='examples on the contact sheets (eval_gui.py --num_vis)')
@@ -48,8 +48,8 @@ def parse_args(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     if a.dataset != 'kitti':
-        ap.error("--dataset %s is not supported (only kitti; sintel / chairs / mdb inputs are not part of this project)"
-                 % a.dataset)
+        ap.error("--dataset %s is not supported here (only kitti; python -m unflow_amd.evaluate_flo scores and draws sintel / "
+                 "chairs / mdb)" % a.dataset)
     if a.batch_size <= 0:
         ap.error("--batch_size must be positive")
     if a.num_vis < 0:
