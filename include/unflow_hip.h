@@ -360,6 +360,28 @@ int unflow_photometric_augment(const float* im, int ld_in, float* out, int ld_ou
                                const float* brightness, const float* colour3, const float* gamma, const float* noise,
                                int n_par, const float* mean3, int N, int H, int W, unflow_stream_t stream);
 
+/* Geometric + photometric augmentation of the supervised step with its ground truth, one launch (csrc/augment_flow.hip).
+ * mats: DEVICE [B][3][6] fp32, per sample the affine PIXEL maps M1, M2, M2^-1 (rows [a b c; d e f]: x' = (a x + b y) + c),
+ * where A(theta; H, W) is unflow_stn_affine_fwd's map written on pixel coordinates, M1 = A(theta_global) and
+ * M2 = A(theta_global) A(theta_local).  For output pixel p of sample b, s1 = M1 p and s2 = M2 p:
+ *   im01 [2B,H,W,3]       rows b / b + B = im1 at s1 / im2 at s2 with unflow_stn_affine_fwd's tap rule (floor, indices clipped
+ *                         before the weights, its add order) on the taps v / 255 (im1, im2: [B,H,W,3] in [0,255]);
+ *   x0 [2B,H,W,ld_out]    unflow_photometric_augment's expression on those values (sample row n uses draw n % n_par; mean3:
+ *                         HOST [3] in [0,255] or NULL), channels 3..ld_out-1 zero: bit-identical to that entry run on im01;
+ *   flow_out [B,H,W,2], mask_out [B,H,W]  from flow_gt [B,H,W,2] and mask_gt [B,H,W] (NULL = ones):
+ *     mode 0 (bilinear): f = convex bilinear of the four flow taps around s1 (a + (b - a) * alpha per row, then across the
+ *                        rows), valid = the four taps lie inside the map and all their masks are > 0.5;
+ *     mode 1 (nearest):  f = the tap at r = floor(s1 + 0.5), valid = r inside and mask(r) > 0.5 (sparse maps);
+ *     q = M2^-1 (s1 + f); flow_out = q - p and mask_out = 1 where valid, else +0 and 0 by selection — a non-finite or marker
+ *     value under an invalid tap never reaches an output.
+ * The sources are gathered while the targets are written: flow_gt / mask_gt / im1 / im2 must not be the output buffers
+ * (UNFLOW_ERR_UNSUPPORTED, as for mode outside {0, 1}); n_par <= 0, H or W <= 0, ld_out < 3: UNFLOW_ERR_SHAPE. */
+int unflow_supervised_geo_augment(const float* im1, const float* im2, const float* flow_gt, const float* mask_gt,
+                                  const float* mats, const float* contrast, const float* brightness, const float* colour3,
+                                  const float* gamma, const float* noise, int n_par, const float* mean3, float* im01, float* x0,
+                                  int ld_out, float* flow_out, float* mask_out, int mode, int B, int H, int W,
+                                  unflow_stream_t stream);
+
 /* Input tensor of a FlowNetS stage (flownet.py:46-59), channels-last with stride ld_out (pad channels untouched):
  * [first, second] (6 ch) when prev_flow2 == NULL, else [first, second, flow, warp(second, flow), |warp - first|]
  * (14 ch) with flow = resize_bilinear(prev_flow2 [N,h,w,2]) * flow_scale (= 4 * FLOW_SCALE).  Forward only: the

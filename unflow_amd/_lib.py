@@ -50,6 +50,7 @@ def lib():
         _lib.unflow_png_to_flow_gt.restype = ctypes.c_int
         _lib.unflow_flo_to_flow_gt.restype = ctypes.c_int
         _lib.unflow_sintel_gt.restype = ctypes.c_int
+        _lib.unflow_supervised_geo_augment.restype = ctypes.c_int
         _apply_env_options(_lib)
     return _lib
 

@@ -139,8 +139,104 @@ def draw_training_augmentation(num_batch, generator=None):
     return aug
 
 
-def draw_supervised_augmentation(num_batch, generator=None):
+# Range keys of the geometric part of draw_supervised_augmentation (draw_affine's keywords; 'local_' + key: the local transform
+# of the second frame).  Trainer reads them from params as 'augment_' + key.
+GEOMETRIC_RANGE_KEYS = ('max_translation_x', 'max_translation_y', 'max_rotation', 'min_scale', 'max_scale', 'horizontal_flipping',
+                        'local_max_translation_x', 'local_max_translation_y', 'local_max_rotation', 'local_min_scale',
+                        'local_max_scale')
+
+
+def draw_supervised_augmentation(num_batch, generator=None, geometric=False, **ranges):
     """The draws of the supervised step (supervised.py:21-25): photometric only, the same ranges as the photometric part of
-    draw_training_augmentation; one draw per image pair, applied to both frames."""
-    return draw_photometric(num_batch, noise_stddev=0.04, min_contrast=-0.3, max_contrast=0.3, brightness_stddev=0.02,
-                            min_colour=0.9, max_colour=1.1, min_gamma=0.7, max_gamma=1.5, generator=generator)
+    draw_training_augmentation; one draw per image pair, applied to both frames.
+    geometric=True (this project's addition): the dict also carries theta_global and theta_local of draw_affine, by
+    default with the unsupervised step's ranges (unsupervised.py:39-50: global = flip and scale 0.9 .. 1.1, local = scale
+    0.9 .. 1.1); `ranges` overrides them (GEOMETRIC_RANGE_KEYS).  The photometric draws come FIRST, so a seed gives the same
+    photometric draws with and without `geometric`."""
+    unknown = sorted(set(ranges) - set(GEOMETRIC_RANGE_KEYS))
+    if unknown or (ranges and not geometric):
+        raise TypeError("draw_supervised_augmentation: %s" % ("unknown range keys %s" % unknown if unknown else
+                                                              "range keys need geometric=True"))
+    aug = draw_photometric(num_batch, noise_stddev=0.04, min_contrast=-0.3, max_contrast=0.3, brightness_stddev=0.02,
+                           min_colour=0.9, max_colour=1.1, min_gamma=0.7, max_gamma=1.5, generator=generator)
+    if geometric:
+        glob = dict(horizontal_flipping=True, min_scale=0.9, max_scale=1.1)
+        loc = dict(min_scale=0.9, max_scale=1.1)
+        for k, v in ranges.items():
+            if k.startswith('local_'):
+                loc[k[len('local_'):]] = v
+            else:
+                glob[k] = v
+        aug['theta_global'] = draw_affine(num_batch, generator=generator, **glob)
+        aug['theta_local'] = draw_affine(num_batch, generator=generator, **loc)
+    return aug
+
+
+def identity_photometric(num_batch):
+    """Photometric draws that change nothing: contrast 0, brightness 0, colour 1, gamma 1, noise 0."""
+    z = torch.zeros(num_batch)
+    return dict(contrast=z.clone(), brightness=z.clone(), colour=torch.ones(num_batch, 3), gamma=torch.ones(num_batch), noise=z)
+
+
+def pixel_identity_theta(H, W):
+    """The theta whose PIXEL map is the identity: [(W-1)/W, 0, -1/W, 0, (H-1)/H, -1/H] (not theta = I: the transformer's
+    normalised grid spans [-1, 1] over W - 1 steps but is scaled back by W / 2).  [1,2,3] float64."""
+    return torch.tensor([[[(W - 1) / W, 0.0, -1.0 / W], [0.0, (H - 1) / H, -1.0 / H]]], dtype=torch.float64)
+
+
+def affine_pixel_matrix(theta, H, W):
+    """A(theta; H, W): the map of transformer() from output pixel (px, py) to the source coordinate, as [B,3,3] float64 on
+    (px, py, 1):  x = (W/2) (t0 (2 px / (W-1) - 1) + t1 (2 py / (H-1) - 1) + t2 + 1), y likewise with H/2 and t3..t5."""
+    if H < 2 or W < 2:
+        raise ValueError("affine_pixel_matrix: the transformer's grid needs H, W >= 2, got %d x %d" % (H, W))
+    t = torch.as_tensor(theta).detach().to('cpu', torch.float64).reshape(-1, 6)
+    A = torch.zeros(t.shape[0], 3, 3, dtype=torch.float64)
+    A[:, 0, 0] = W * t[:, 0] / (W - 1)
+    A[:, 0, 1] = W * t[:, 1] / (H - 1)
+    A[:, 0, 2] = (W / 2.0) * (-t[:, 0] - t[:, 1] + t[:, 2] + 1.0)
+    A[:, 1, 0] = H * t[:, 3] / (W - 1)
+    A[:, 1, 1] = H * t[:, 4] / (H - 1)
+    A[:, 1, 2] = (H / 2.0) * (-t[:, 3] - t[:, 4] + t[:, 5] + 1.0)
+    A[:, 2, 2] = 1.0
+    return A
+
+
+def affine_pixel_maps(theta_global, theta_local, H, W, dtype=torch.float32):
+    """The three pixel maps of unflow_supervised_geo_augment per sample, formed in fp64 and rounded once: [B,3,6] =
+    (M1 = G, M2 = G L, M2^-1) with G = A(theta_global), L = A(theta_local) — the unsupervised step shows im1(G p) and
+    im2(G (L p)) (engine.set_input's chain) — each as the two rows [a b c; d e f] of the affine 3 x 3."""
+    G, L = affine_pixel_matrix(theta_global, H, W), affine_pixel_matrix(theta_local, H, W)
+    if G.shape[0] != L.shape[0]:
+        raise ValueError("affine_pixel_maps: %d global and %d local thetas" % (G.shape[0], L.shape[0]))
+    M2 = G @ L
+    M2i = torch.linalg.inv(M2)
+    return torch.stack([G[:, :2], M2[:, :2], M2i[:, :2]], 1).reshape(-1, 3, 6).to(dtype).contiguous()
+
+
+GT_SAMPLING = {'bilinear': 0, 'nearest': 1}
+
+
+def supervised_geo_augment(im1, im2, flow_gt, mask_gt, mats, draws, im01, x0, flow_out, mask_out, gt_sampling='bilinear',
+                           mean=None):
+    """unflow_supervised_geo_augment (csrc/augment_flow.hip): im1, im2 [B,H,W,3] in [0,255], flow_gt [B,H,W,2], mask_gt
+    [B,H,W,1] or None, mats = affine_pixel_maps(...) -> im01 [2B,H,W,3], x0 [2B,H,W,>=3 stride], flow_out [B,H,W,2],
+    mask_out [B,H,W,1], all written in one launch.  draws: photometric draws (identity_photometric for none)."""
+    if gt_sampling not in GT_SAMPLING:
+        raise ValueError("gt_sampling must be one of %s, got %r" % (sorted(GT_SAMPLING), gt_sampling))
+    B, H, W, _ = im1.shape
+    dev = im1.device
+    for t, shape in ((im1, (B, H, W, 3)), (im2, (B, H, W, 3)), (flow_gt, (B, H, W, 2)), (im01, (2 * B, H, W, 3)),
+                     (flow_out, (B, H, W, 2)), (mask_out, (B, H, W, 1))) + (() if mask_gt is None else ((mask_gt, (B, H, W, 1)),)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, (tuple(t.shape), shape)
+    assert x0.is_cuda and x0.dtype == torch.float32 and x0.stride(3) == 1 and tuple(x0.shape[:3]) == (2 * B, H, W)
+    ld = x0.stride(2)
+    assert x0.stride(1) == W * ld and x0.stride(0) == H * W * ld
+    mats = torch.as_tensor(mats).to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(mats.shape) != (B, 3, 6):
+        raise ValueError("supervised_geo_augment: mats must be [%d,3,6], got %s" % (B, tuple(mats.shape)))
+    g = {k: draws[k].to(device=dev, dtype=torch.float32).contiguous() for k in ('contrast', 'brightness', 'colour', 'gamma', 'noise')}
+    mean_host = None if mean is None else (_lib.ctypes.c_float * 3)(*[float(v) for v in mean])
+    check(_lib.lib().unflow_supervised_geo_augment(
+        ptr(im1), ptr(im2), ptr(flow_gt), ptr(mask_gt), ptr(mats), ptr(g['contrast']), ptr(g['brightness']), ptr(g['colour']),
+        ptr(g['gamma']), ptr(g['noise']), g['contrast'].numel(), mean_host, ptr(im01), ptr(x0), ld, ptr(flow_out), ptr(mask_out),
+        GT_SAMPLING[gt_sampling], B, H, W, stream()), "supervised_geo_augment")

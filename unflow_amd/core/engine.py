@@ -980,7 +980,9 @@ class FlowNetEngine:
         what unsupervised.py:37-68 builds: geometrically augmented images for the losses, photometrically augmented
         mean-free ones for the network, and a per-sample border mask (product of the two warped masks).
         Supervised engine: target = (flow_gt [B,H,W,2], mask_gt [B,H,W,1] or None = ones) is copied into the engine's own
-        buffers; augment is None or photometric draws only (core.augment.draw_supervised_augmentation, supervised.py:21-25)."""
+        buffers; augment is None or photometric draws only (core.augment.draw_supervised_augmentation, supervised.py:21-25) —
+        or, with theta_global / theta_local in the dict, the geometric augmentation of _set_input_geometric, which writes the
+        TRANSFORMED target into those buffers."""
         B, N, H, W = self.B, self.N, self.H, self.W
         lib = _lib.lib()
         st = self.stream()
@@ -1049,6 +1051,8 @@ class FlowNetEngine:
         flow_gt = torch.as_tensor(flow_gt).to(device=self.dev, dtype=torch.float32).contiguous()
         if tuple(flow_gt.shape) != (B, H, W, 2):
             raise ValueError("set_input: flow_gt must be [%d,%d,%d,2], got %s" % (B, H, W, tuple(flow_gt.shape)))
+        if augment is not None and 'theta_global' in augment:
+            return self._set_input_geometric(im1, im2, flow_gt, mask_gt, augment)
         check(lib.unflow_copy(ptr(self.flow_gt), ptr(flow_gt), _lib.csz(flow_gt.numel() * 4), st), "copy")
         if mask_gt is None:
             self.mask_gt.fill_(1.0)
@@ -1068,6 +1072,32 @@ class FlowNetEngine:
         check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(self.im01), self.mean_host,
                                             None, st), "prepare_image_pair")
         A.photometric(self.im01, augment, out=self.x0, mean=CHANNEL_MEAN)
+        self._input_planes()
+
+    def _set_input_geometric(self, im1, im2, flow_gt, mask_gt, augment):
+        """Geometric (+ photometric) augmentation of the supervised step: ONE launch of
+        unflow_supervised_geo_augment resamples both frames (im01), builds the network input (x0) and writes the transformed
+        ground truth straight into the engine's flow_gt / mask_gt; the caller's tensors are read in place.  augment carries
+        theta_global and theta_local (core.augment.draw_supervised_augmentation(geometric=True)); photometric draws are
+        optional (identity without them).  params['gt_sampling']: 'bilinear' (dense maps, default) or 'nearest' (sparse KITTI
+        maps)."""
+        from . import augment as A
+        B, H, W = self.B, self.H, self.W
+        if mask_gt is not None:
+            mask_gt = torch.as_tensor(mask_gt).to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(mask_gt.shape) != (B, H, W, 1):
+                raise ValueError("set_input: mask_gt must be [%d,%d,%d,1], got %s" % (B, H, W, tuple(mask_gt.shape)))
+            if mask_gt.data_ptr() == self.mask_gt.data_ptr():
+                mask_gt = mask_gt.clone()         # the kernel gathers: it cannot read the buffer it writes
+        if flow_gt.data_ptr() == self.flow_gt.data_ptr():
+            flow_gt = flow_gt.clone()
+        tg, tl = augment['theta_global'], augment['theta_local']
+        if tg.reshape(-1, 6).shape[0] != B or tl.reshape(-1, 6).shape[0] != B:
+            raise ValueError("set_input: theta_global / theta_local must hold %d transforms" % B)
+        mats = A.affine_pixel_maps(tg, tl, H, W)
+        draws = augment if 'contrast' in augment else A.identity_photometric(B)
+        A.supervised_geo_augment(im1, im2, flow_gt, mask_gt, mats, draws, self.im01, self.x0, self.flow_gt, self.mask_gt,
+                                 gt_sampling=self.params.get('gt_sampling') or 'bilinear', mean=CHANNEL_MEAN)
         self._input_planes()
 
     def _set_input_inference(self, im1, im2, augment, target):

@@ -299,17 +299,41 @@ def check_window_inside(path, meta, oy, ox, dims):
         raise ValueError("%s is %d x %d: the %d x %d window at (%d, %d) leaves it" % (path, meta[0], meta[1], h, w, oy, ox))
 
 
-class GTPlanner(PairPlanner):
-    """The host-only half of DeviceGTBatches: walks KITTIInput.train_gt_files' (im1, im2, gt) list as input_train_gt does — from
-    `shift`, in order, cyclically — and draws oy, then ox, per example from np.random.RandomState(seed) with limits from im1's
-    header.  The window must lie inside all three files and the ground truth must be 16-bit RGB."""
+TRAIN_GT_KINDS = ('kitti', 'flo', 'sintel')
 
-    def __init__(self, files, batch_size, dims, seed, shift=0):
+
+class GTPlanner(PairPlanner):
+    """The host-only half of DeviceGTBatches: walks an example list as the input_train_gt iterators do — from `shift`, in order,
+    cyclically — and draws oy, then ox, per example from np.random.RandomState(seed) with limits from im1's header.  The window
+    must lie inside every file of the example.
+    gt_kind 'kitti' (default): KITTIInput.train_gt_files' (im1, im2, gt) list, the ground truth a 16-bit RGB PNG.
+    gt_kind 'flo': (im1, im2, .flo) — ChairsInput.input_train_gt; 'sintel': (im1, im2, .flo, invalid PNG, occlusions PNG) —
+    SintelInput.input_train_gt; a .flo file is checked by flo_header, a Sintel mask must have its .flo's size."""
+
+    def __init__(self, files, batch_size, dims, seed, shift=0, gt_kind='kitti'):
         super().__init__(files, batch_size, dims, True, seed)
         self.pos = int(shift)
+        if gt_kind not in TRAIN_GT_KINDS:
+            raise ValueError("gt_kind must be one of %s, got %r" % (TRAIN_GT_KINDS, gt_kind))
+        self.gt_kind = gt_kind
+        self.gt_roles = GT_KINDS[gt_kind] or (GT,)
+        self.n_maps = 2 if gt_kind == 'sintel' else 1
+        for ex in self.pairs:
+            if len(ex) != 2 + len(self.gt_roles):
+                raise ValueError("gt_kind %r takes examples of %d files, got %d" % (gt_kind, 2 + len(self.gt_roles), len(ex)))
+
+    def header(self, path, role=FRAME):
+        if role != FLO:
+            return super().header(path)
+        if path not in self._headers:
+            self._headers[path] = flo_header(path)
+        return self._headers[path]
 
     def next_batch(self):
-        """[(im1, im2, gt, header 1, header 2, header gt, oy, ox), ...] of the next batch."""
+        """gt_kind 'kitti': [(im1, im2, gt, header 1, header 2, header gt, oy, ox), ...] of the next batch; the .flo kinds:
+        [[file of im1, of im2, of every ground-truth file], ...] — (path, header, role, oy, ox) each, as EvalPlanner's."""
+        if self.gt_kind != 'kitti':
+            return self._next_batch_flo()
         h, w = self.dims
         out = []
         for _ in range(self.batch_size):
@@ -325,7 +349,28 @@ class GTPlanner(PairPlanner):
             out.append((fn1, fn2, fgt, m1, m2, mg, oy, ox))
         return out
 
+    def _next_batch_flo(self):
+        h, w = self.dims
+        out = []
+        for _ in range(self.batch_size):
+            ex = self.pairs[self.pos % len(self.pairs)]
+            self.pos += 1
+            roles = (FRAME, FRAME) + tuple(self.gt_roles)
+            metas = [self.header(fn, r) for fn, r in zip(ex, roles)]
+            check_window_inside(ex[0], metas[0], 0, 0, self.dims)
+            oy = int(self.rng.randint(0, metas[0][0] - h + 1))
+            ox = int(self.rng.randint(0, metas[0][1] - w + 1))
+            for fn, m in zip(ex[1:], metas[1:]):
+                check_window_inside(fn, m, oy, ox, self.dims)
+            for fn, m in zip(ex[3:], metas[3:]):
+                if tuple(m[:2]) != tuple(metas[2][:2]):
+                    raise ValueError("%s is %d x %d, its flow file %s %d x %d" % ((fn,) + tuple(m[:2]) + (ex[2],) + tuple(metas[2][:2])))
+            out.append([(fn, m, r, oy, ox) for fn, m, r in zip(ex, metas, roles)])
+        return out
+
     def files(self, examples):
+        if self.gt_kind != 'kitti':
+            return EvalPlanner.table_files(examples)
         return [(e[0], e[3], FRAME, e[6], e[7]) for e in examples] + [(e[1], e[4], FRAME, e[6], e[7]) for e in examples] + \
                [(e[2], e[5], GT, e[6], e[7]) for e in examples]
 
@@ -681,25 +726,30 @@ class DevicePairBatches(_DeviceBatches):
 
 
 class DeviceGTBatches(_DeviceBatches):
-    """The device twin of KITTIInput.input_train_gt: an endless iterator of (im1, im2, flow_gt, mask_gt), float32 DEVICE tensors
+    """The device twin of the input_train_gt iterators (KITTIInput, and with gt_kind 'flo' / 'sintel' ChairsInput / SintelInput):
+    an endless iterator of (im1, im2, flow_gt, mask_gt), float32 DEVICE tensors
     [B,h,w,3] x 2, [B,h,w,2], [B,h,w,1], bit-identical to the host iterator for the same file list, seed and shift (GTPlanner).
-    A window that leaves one of an example's three files, or a ground-truth file that is not 16-bit RGB, raises ValueError
-    naming the file (from the constructor or from next(), whichever plans the batch)."""
+    A window that leaves one of an example's files, or a KITTI ground-truth file that is not 16-bit RGB, raises ValueError
+    naming the file (from the constructor or from next(), whichever plans the batch).  gt_map (gt_kind 'sintel'): 0 = the
+    occluded map (flow, 1 - invalid), 1 = the non-occluded one (unflow_sintel_gt composes both)."""
 
     def __init__(self, files, batch_size, dims, normalize, mean, stddev, seed=0, shift=0, device=None, workers=8, prefetch=2,
-                 timing=False):
-        self.planner = GTPlanner(files, batch_size, dims, seed, shift)
-        self.batch_size = batch_size
+                 timing=False, gt_kind='kitti', gt_map=0):
+        self.planner = GTPlanner(files, batch_size, dims, seed, shift, gt_kind)
+        if not 0 <= int(gt_map) < self.planner.n_maps:
+            raise ValueError("gt_map %r: gt_kind %r has %d map(s)" % (gt_map, gt_kind, self.planner.n_maps))
+        self.batch_size, self.gt_map = batch_size, int(gt_map)
         mean, stddev = _norm(normalize, mean, stddev)
-        super().__init__(3 * batch_size, 2 * batch_size, batch_size, dims, mean, stddev, device, workers, prefetch, timing, window=True)
+        super().__init__((2 + len(self.planner.gt_roles)) * batch_size, 2 * batch_size, self.planner.n_maps * batch_size, dims, mean,
+                         stddev, device, workers, prefetch, timing, window=True)
 
     def _plan(self):
         examples = self.planner.next_batch()
         return self.planner.files(examples), examples
 
     def _result(self, job):
-        B, s = self.batch_size, job.slot
-        return s.out[:B], s.out[B:], s.flow, s.mask
+        B, s, g = self.batch_size, job.slot, self.gt_map
+        return s.out[:B], s.out[B:], s.flow[g * B:(g + 1) * B], s.mask[g * B:(g + 1) * B]
 
 
 class DeviceEvalBatches(_DeviceBatches):

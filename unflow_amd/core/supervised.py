@@ -10,7 +10,7 @@ _engines = {}
 def get_supervised_engine(batch, height, width, params=None, device=None):
     """One-direction engine per (shape, device, flownet / full_res / train_all), cached like flownet.get_engine."""
     params = params or {}
-    ep = {k: params[k] for k in ('flownet', 'full_res', 'train_all') if params.get(k) is not None}
+    ep = {k: params[k] for k in ('flownet', 'full_res', 'train_all', 'gt_sampling') if params.get(k) is not None}
     key = (batch, height, width, None if device is None else str(torch.device(device)), tuple(sorted(ep.items())))
     if key not in _engines:
         _engines[key] = FlowNetEngine(batch, height, width, params=dict(ep, flownet=ep.get('flownet', 'S')), device=device,
@@ -23,7 +23,9 @@ def supervised_loss(batch, params, normalization=None, augment=True, return_flow
     """batch = (im1, im2, flow_gt, mask_gt), NHWC float32, images in [0,255], flow_gt [B,H,W,2], mask_gt [B,H,W,1].
     `normalization` is accepted for signature compatibility; the channel means are the reference's (core/input.py:45).
     augment: True draws random_photometric with the reference's ranges (supervised.py:21-25; host RNG `generator`), a dict
-    replays given draws (core.augment.draw_supervised_augmentation), False/None disables it.  With backward=True the
+    replays given draws (core.augment.draw_supervised_augmentation; with theta_global / theta_local in it — geometric=True —
+    the engine also resamples both frames and the ground truth, params['gt_sampling'] = 'bilinear' or 'nearest'), False/None
+    disables it.  With backward=True the
     parameter gradients are left in engine.G.  return_flow: also the final forward flow [B,H,W,2]."""
     if normalization is not None:
         mean = [float(v) for v in normalization[0]]

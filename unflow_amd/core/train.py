@@ -213,7 +213,10 @@ class Trainer:
     supervised=True: the supervised fine-tuning trainer (run.py:175-190, Trainer(supervised=True)): the one-direction engine,
     train_batch_fn yields (im1, im2, flow_gt, mask_gt) batches (kitti.input.KITTIInput.input_train_gt) and the step augments
     photometrically only (supervised.py:21-25).  eval keeps the bidirectional engine of the unsupervised loss, as the
-    reference does (train.py:277)."""
+    reference does (train.py:277).  params['augment_geometric'] (default False; this project's addition) adds
+    the geometric augmentation of image pair and ground truth: the draws of draw_supervised_augmentation(geometric=True) with
+    the ranges of the optional keys 'augment_' + core.augment.GEOMETRIC_RANGE_KEYS, the ground truth resampled as
+    params['gt_sampling'] says ('bilinear', default; 'nearest' for sparse maps)."""
 
     ENGINE_KEYS = ('flownet', 'train_all', 'full_res', 'pyramid_loss', 'border_mask', 'mask_occlusion')
 
@@ -222,11 +225,21 @@ class Trainer:
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
         self.supervised = bool(supervised)
+        if params.get('augment_geometric') and not self.supervised:
+            raise ValueError("augment_geometric is a key of the supervised trainer (the unsupervised step always augments "
+                             "geometrically)")
+        if params.get('gt_sampling') not in (None, 'bilinear', 'nearest'):
+            raise ValueError("gt_sampling must be 'bilinear' or 'nearest', got %r" % (params['gt_sampling'],))
         eng_params = {k: v for k, v in params.items() if k.endswith('_weight') or k in self.ENGINE_KEYS}
         self.engine = FlowNetEngine(batch_size, height, width, params=eng_params or None, device=device, seed=seed,
                                     supervised=self.supervised)
         self.runner = StepRunner(self.engine, self.world, use_graph=use_graph)
         self.augment = augment
+        self.augment_geometric = bool(params.get('augment_geometric', False))
+        from .augment import GEOMETRIC_RANGE_KEYS
+        self.geometric_ranges = {k: params['augment_' + k] for k in GEOMETRIC_RANGE_KEYS if params.get('augment_' + k) is not None}
+        if params.get('gt_sampling') is not None:
+            self.engine.params['gt_sampling'] = params['gt_sampling']
         self.generator = torch.Generator().manual_seed(1000003 * (seed + 1) + self.rank)   # per-rank augmentation draws
         self.iteration = 0
 
@@ -408,8 +421,11 @@ class Trainer:
         aug = self.augment if augment is None else augment
         if aug is True:
             from .augment import draw_training_augmentation, draw_supervised_augmentation
-            draw = draw_supervised_augmentation if getattr(self, 'supervised', False) else draw_training_augmentation
-            aug = draw(self.engine.B, self.generator)
+            if getattr(self, 'supervised', False) and getattr(self, 'augment_geometric', False):
+                aug = draw_supervised_augmentation(self.engine.B, self.generator, geometric=True, **self.geometric_ranges)
+            else:
+                draw = draw_supervised_augmentation if getattr(self, 'supervised', False) else draw_training_augmentation
+                aug = draw(self.engine.B, self.generator)
         loss = self.runner.step(im1, im2, lr, augment=aug or None, target=target)
         self.iteration += 1
         return loss

@@ -73,6 +73,51 @@ class FloInput(Input):
             yield tuple(np.stack(c) for c in cols)
 
 
+    # ---- supervised training input (this project's addition): the twin of KITTIInput.input_train_gt
+    def _window_gt(self, files, oy, ox):
+        """One example's ground truth on the (dims) window at (oy, ox): (flow [h,w,2], mask [h,w,1]) of a .flo file."""
+        from ..core.png_device import check_window_inside
+        h, w = self.dims
+        flow, mask = read_flo(files[0])
+        check_window_inside(files[0], flow.shape, oy, ox, self.dims)
+        return flow.numpy()[oy:oy + h, ox:ox + w], mask.numpy()[oy:oy + h, ox:ox + w]
+
+    def _train_gt(self, examples, gt_kind, gt_map, seed, shift, device, workers, prefetch):
+        """examples: [(im1, im2, ground-truth files ...)].  Host generator, or the same batches from DeviceGTBatches."""
+        if device is not None:
+            from ..core.png_device import DeviceGTBatches
+            return DeviceGTBatches(examples, self.batch_size, self.dims, self.normalize, self.mean, self.stddev, seed=seed,
+                                   shift=shift, device=device, workers=workers, prefetch=prefetch, gt_kind=gt_kind, gt_map=gt_map)
+        return self._train_gt_host(examples, gt_map, seed, shift)
+
+    def _train_gt_host(self, examples, gt_map, seed, shift):
+        """An endless iterator of (im1, im2, flow_gt, mask_gt) numpy batches [B,h,w,3] x 2, [B,h,w,2], [B,h,w,1]: the examples
+        in order and cyclically from `shift`, per example ONE random window of self.dims for both frames and the ground truth
+        — oy, then ox, from np.random.RandomState(seed), limits from im1 (KITTIInput._input_train_gt_host's draws).  A window
+        that leaves one of the example's files raises ValueError naming it."""
+        from ..core.png_device import check_window_inside
+        h, w = self.dims
+        rng = np.random.RandomState(seed)
+        pos = shift
+        while True:
+            cols = [[] for _ in range(4)]
+            for _ in range(self.batch_size):
+                ex = examples[pos % len(examples)]
+                pos += 1
+                a, b = read_png_image(ex[0]), read_png_image(ex[1])
+                check_window_inside(ex[0], a.shape, 0, 0, self.dims)
+                oy = int(rng.randint(0, a.shape[0] - h + 1))
+                ox = int(rng.randint(0, a.shape[1] - w + 1))
+                check_window_inside(ex[1], b.shape, oy, ox, self.dims)
+                flow, mask = self._window_gt(ex[2:], oy, ox)[2 * gt_map:2 * gt_map + 2]
+                a, b = a[oy:oy + h, ox:ox + w], b[oy:oy + h, ox:ox + w]
+                if self.normalize:
+                    a, b = self._normalize_image(a), self._normalize_image(b)
+                for c, v in zip(cols, (a, b, flow, mask)):
+                    c.append(v)
+            yield tuple(np.stack(c).astype(np.float32) for c in cols)
+
+
 class MiddleburyInput(FloInput):
     def train_files(self):
         """(pairs of middlebury/other-data, [the .flo files of middlebury/other-gt-flow]).  The reference zips the two position

@@ -9,7 +9,8 @@ the padding away again).  invalid and occ are BINARY here — 1 where channel 0 
 non-zero: the reference feeds the raw 0 / 255 grey values into 1 - invalid, which makes mask_occ = -254; the evident meaning of a
 binary mask is followed.  The .flo size comes from the file's header, not the reference's hard-coded 436 x 1024.
 Host numpy batches, or — with a device — the same batches as device tensors, composed by unflow_sintel_gt
-(middlebury/input.py::FloInput, core/png_device.py).  The dataset downloader (sintel/data.py) is out of scope."""
+(middlebury/input.py::FloInput, core/png_device.py).  input_train_gt (this project's addition, DESIGN 7.9) is the supervised
+training input: random crops with one of the two composed maps.  The dataset downloader (sintel/data.py) is out of scope."""
 import numpy as np
 
 from ..core.input import read_flo, read_png_image
@@ -48,6 +49,36 @@ class SintelInput(FloInput):
         flow, invalid, occ = self._preprocess_map(flow), self._preprocess_map(invalid), self._preprocess_map(occ)
         mask_occ = 1 - invalid
         return flow, mask_occ, flow * (1 - occ), mask_occ * (1 - occ)
+
+    def _window_gt(self, files, oy, ox):
+        """_read_gt's composition on the (dims) window at (oy, ox) instead of the central crop / padding: (flow_occ, mask_occ,
+        flow_noc, mask_noc).  The window must lie inside all three maps (ValueError naming the file)."""
+        from ..core.png_device import check_window_inside
+        f_flow, f_invalid, f_occ = files
+        h, w = self.dims
+        flow = read_flo(f_flow)[0].numpy()
+        invalid, occ = read_binary(f_invalid), read_binary(f_occ)
+        check_window_inside(f_flow, flow.shape, oy, ox, self.dims)
+        for f, m in ((f_invalid, invalid), (f_occ, occ)):
+            if m.shape[:2] != flow.shape[:2]:
+                raise ValueError("%s is %d x %d, its flow file %s %d x %d" % ((f,) + m.shape[:2] + (f_flow,) + flow.shape[:2]))
+        flow, invalid, occ = (a[oy:oy + h, ox:ox + w] for a in (flow, invalid, occ))
+        mask_occ = 1 - invalid
+        return flow, mask_occ, flow * (1 - occ), mask_occ * (1 - occ)
+
+    def input_train_gt(self, variant='clean', gt='occ', seed=0, shift=0, device=None, workers=8, prefetch=2):
+        """The supervised training input (this project's addition; the reference has none for Sintel): an endless iterator of
+        (im1, im2, flow_gt, mask_gt) over the pairs of sintel/training/<variant> with the composed ground truth of _read_gt —
+        gt 'occ': (flow, 1 - invalid), 'noc': (flow * (1 - occ), (1 - invalid) * (1 - occ)) — one random window of self.dims
+        per example, as KITTIInput.input_train_gt draws it (FloInput._train_gt_host).  device: the same batches, bit for
+        bit, as device tensors (core/png_device.py::DeviceGTBatches, composed by unflow_sintel_gt)."""
+        if variant not in ('clean', 'final'):
+            raise ValueError("variant must be 'clean' or 'final', got %r" % (variant,))
+        if gt not in ('occ', 'noc'):
+            raise ValueError("gt must be 'occ' or 'noc', got %r" % (gt,))
+        pairs, lists = self.train_files('sintel/training/' + variant)
+        examples = [tuple(p) + tuple(g[k] for g in lists) for k, p in enumerate(pairs)]
+        return self._train_gt(examples, 'sintel', ('occ', 'noc').index(gt), seed, shift, device, workers, prefetch)
 
     def _input_train(self, image_dir, device, workers, prefetch):
         """_input_train (:107-114): batches of (im1, im2, input_shape, flow_occ, mask_occ, flow_noc, mask_noc)."""
