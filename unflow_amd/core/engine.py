@@ -1380,6 +1380,107 @@ class FlowNetEngine:
         lib.unflow_forward_warp_workspace_bytes.restype = _lib.ctypes.c_size_t
         lv['fwws'] = torch.empty(int(lib.unflow_forward_warp_workspace_bytes(N, h, w, 1)) // 4 + 64, dtype=torch.float32, device=self.dev)
 
+    def _terms_scratch(self, lv):
+        """loss_terms()'s own buffers of a level (allocated on first use, outside any capture): what forward_loss keeps in
+        lv['gray1'], lv['maskN'] ... lives here a second time, so that reading the terms never writes a buffer of the step."""
+        if 'terms' not in lv:
+            N, h, w = self.N, lv['h'], lv['w']
+            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)
+            lib = _lib.lib()
+            lib.unflow_forward_warp_workspace_bytes.restype = _lib.ctypes.c_size_t
+            lv['terms'] = dict(gray1=z(N, h, w), gray2w=z(N, h, w), dist=z(N, h, w), maskN=z(N, h, w), fwarped=z(N, h, w, 2),
+                               fscaled=z(N, h, w, 2), fwmap=z(N, h, w), imw=z(N, h, w, 3), gdiff=z(N, h, w, 6),
+                               fwws=torch.empty(int(lib.unflow_forward_warp_workspace_bytes(N, h, w, 1)) // 4 + 64,
+                                                dtype=torch.float32, device=self.dev))
+        return lv['terms']
+
+    def loss_terms(self):
+        """The terms of the loss that forward_loss (alone, or inside a training step) has just summed, one value each
+        (unsupervised.py:136-141,152-156, the reference's 'loss<k>/<term>' and 'loss/<term>' summaries):
+
+            {'levels': [{term: value} per pyramid level, enabled terms only],
+             'combined': {term: sum over the levels of layer_weight * value, 0.0 for a term that is off; all of LOSSES},
+             'regularization': float}
+
+        so that sum(weight * combined) + regularization is the total of forward_loss.  READS the flow of every level
+        (act['flow<n>'], which backward_net and the optimizer leave alone), the image pyramid lv['im'] that forward_loss built
+        from im01, and the per-level border masks lv['mask'] of set_input; and P for the regularisation term — after an
+        optimizer step those are the updated weights, a relative difference of the order of the learning rate from the term
+        inside that step's loss.  WRITES only its own scratch (_terms_scratch) and accumulators: no buffer of the step, no
+        gradient, not loss_acc.  Every term goes through its per-term entry point with weight 1 and no gradient output, into
+        an accumulator of its own; unflow_mask_terms is called once per weight.  Launched on the current stream, one host
+        synchronisation at the end; not part of StepRunner.step."""
+        self._no_training("loss_terms")
+        if self.supervised:
+            raise ValueError("loss_terms: the supervised loss has one term, the value forward_loss returns")
+        lib = _lib.lib()
+        st = self.stream()
+        N, B = self.N, self.B
+        P = self.params
+        wt = lambda k: float(P.get(k + '_weight') or 0.0)
+        on = [k for k in LOSSES if wt(k)]
+        occl = {'': 0, None: 0, 'fb': 1, 'disocc': 2}[P.get('mask_occlusion', '')]
+        use_border = bool(P.get('border_mask'))
+        levels = self.lv if P.get('pyramid_loss') else self.lv[:1]
+        need_fbwarp = bool(wt('fb')) or occl == 1
+        need_fwarp = bool(wt('sym')) or occl == 2
+        need_mask_terms = need_fbwarp or need_fwarp or bool(wt('occ')) or not use_border
+        null = ptr(None)
+        with torch.cuda.device(self.dev):
+            acc = getattr(self, '_terms_acc', None)
+            if acc is None:
+                acc = self._terms_acc = torch.zeros(len(self.lv) + 1, len(LOSSES), dtype=torch.float32, device=self.dev)
+            check(lib.unflow_zero(ptr(acc), _lib.csz(acc.numel() * 4), st), "zero")
+            for i, lv in enumerate(levels):
+                h, w, fs, flow = lv['h'], lv['w'], lv['fs'], lv['flow']
+                n1 = B * h * w
+                T = self._terms_scratch(lv)
+                slot = lambda k: ptr(acc[i, LOSSES.index(k)])
+                if wt('smooth_2nd'):
+                    check(lib.unflow_second_order_fwd_bwd(ptr(flow), cf(fs), slot('smooth_2nd'), null, 0, cf(1.0), cf(n1 * 4),
+                                                          N, h, w, st), "second_order")
+                if wt('smooth_1st'):
+                    check(lib.unflow_smooth_1st_fwd_bwd(ptr(flow), cf(fs), slot('smooth_1st'), null, 0, cf(1.0), cf(n1 * 2),
+                                                        N, h, w, st), "smooth_1st")
+                mask, n_mask = lv['mask'], lv['n_mask']
+                if need_mask_terms:
+                    warped = fwm = None
+                    if need_fbwarp:
+                        warped = T['fwarped']
+                        check(lib.unflow_image_warp_fwd(ptr(flow), 2, ptr(flow), cf(fs), ptr(warped), null, B, N, h, w, 2, st),
+                              "image_warp(flow)")
+                    if need_fwarp:
+                        check(lib.unflow_scale(ptr(flow), cf(fs), ptr(T['fscaled']), cl(flow.numel()), st), "scale")
+                        fwm = T['fwmap']
+                        check(lib.unflow_forward_warp_fwd(ptr(T['fscaled']), ptr(fwm), N, h, w, 1, ptr(T['fwws']),
+                                                          _lib.csz(T['fwws'].numel() * 4), st), "forward_warp")
+                    # the mask of the data terms once (no weight), then one launch per enabled term, one weight at a time
+                    for k in [None] + [k for k in ('fb', 'occ', 'sym') if wt(k)]:
+                        check(lib.unflow_mask_terms(ptr(flow), ptr(warped), ptr(fwm), ptr(lv['mask'] if use_border else None),
+                                                    lv['n_mask'], cf(fs), occl, ptr(T['maskN']) if k is None else null,
+                                                    null if k is None else slot(k), null, null, 0, cf(k == 'fb'), cf(k == 'occ'),
+                                                    cf(k == 'sym'), B, B, N, h, w, st), "mask_terms")
+                    mask, n_mask = T['maskN'], N
+                if wt('ternary'):
+                    check(lib.unflow_gray_pair(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(T['gray1']), ptr(T['gray2w']), B, N, h, w,
+                                               st), "gray_pair")
+                    check(lib.unflow_ternary_fwd(ptr(T['gray1']), ptr(T['gray2w']), ptr(mask), n_mask, ptr(T['dist']),
+                                                 slot('ternary'), cf(1.0), cf(n1), lv['pd'], N, h, w, st), "ternary")
+                if wt('photo'):
+                    check(lib.unflow_photometric_fwd_bwd(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(mask), n_mask, slot('photo'),
+                                                         null, 0, cf(1.0), cf(n1 * 3), B, N, h, w, st), "photometric")
+                if wt('grad'):
+                    check(lib.unflow_image_warp_fwd(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(T['imw']), null, B, N, h, w, 3, st),
+                          "image_warp(im)")
+                    check(lib.unflow_gradient_loss_fwd(ptr(lv['im']), 3, ptr(T['imw']), ptr(mask), n_mask, ptr(T['gdiff']),
+                                                       slot('grad'), cf(1.0), cf(n1 * 6), N, h, w, st), "gradient_loss")
+            check(lib.unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(acc[len(self.lv), 0]), st), "l2_loss")
+            host = acc.cpu().double().numpy()
+        out_levels = [{k: float(host[i, LOSSES.index(k)]) for k in on} for i in range(len(levels))]
+        combined = {k: float(sum(lv['lw'] * host[i, LOSSES.index(k)] for i, lv in enumerate(levels))) if k in on else 0.0
+                    for k in LOSSES}
+        return {'levels': out_levels, 'combined': combined, 'regularization': float(host[len(self.lv), 0])}
+
     # ------------------------------------------------------------------ backward
     def backward_net(self, part=None):
         """Gradients of the trained (last) network; earlier stages are behind stop_gradient (flownet.py:51-54).

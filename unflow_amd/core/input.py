@@ -460,8 +460,10 @@ class Input:
         import random
         skip = skip if isinstance(skip, list) else [skip]
         pairs = []
+        # a data object may list a raw directory itself (unflow_amd/data.py::KITTIData.list_frames leaves the benchmark frames out)
+        list_frames = getattr(self.data, 'list_frames', None) or (lambda folder: sorted(os.listdir(folder)))
         for folder in self.data.get_raw_dirs():
-            listing = sorted(os.listdir(folder))
+            listing = list_frames(folder)
             for i, j in self._pair_indices(len(listing), sequence, skip):
                 if sequence and self.skipped_frames:
                     # datasets with dropped frames: keep a pair only when the frame numbers are consecutive (input.py:153-158)

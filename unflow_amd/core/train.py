@@ -1,8 +1,9 @@
 """Mirror of the hot-path parts of src/e2eflow/core/train.py: the training op (get_train_and_loss_ops :147-185:
 AdamOptimizer + towers + average_gradients :388-422), the learning-rate schedule (:225-244) and the loop body
 (:247-251), Trainer.run / train with checkpoint save and resume (:116-145, :186-262; TF checkpoint-V2 bundles written and
-read by core/tf_checkpoint.py), and Trainer.eval (:265-385: batch-1 evaluation against KITTI-format ground truth; the TF
-summaries and the plot process around it are out of scope).
+read by core/tf_checkpoint.py), and Trainer.eval (:265-385: batch-1 evaluation against KITTI-format ground truth).  The
+summaries are written by the caller (python -m unflow_amd.run, core/summary.py) through the on_display hook of train / run and
+from eval's result; the plot process is out of scope, SURVEY §2.
 
 One process per GPU.  A training step is
 
@@ -98,6 +99,16 @@ def network_files(params, spec, ckpt_dir, strict=False):
             raise ValueError("network(s) %s of spec %r are neither in a checkpoint of %s nor in params['finetune']: nothing "
                              "to restore them from" % (missing, spec, ckpt_dir))
     return files, ckpt
+
+
+def term_tags(terms):
+    """engine.loss_terms() under the reference's summary tags (unsupervised.py:141,152-156): 'loss/<term>' = the layer-weighted
+    sum of every term of LOSSES (0 for one that is off), 'loss<k>/<term>' = level k's value, k counted from 2 (the finest level
+    of the default pyramid is flow2)."""
+    out = {'loss/' + k: v for k, v in terms['combined'].items()}
+    for i, level in enumerate(terms['levels']):
+        out.update({'loss%d/%s' % (i + 2, k): v for k, v in level.items()})
+    return out
 
 
 class StepRunner:
@@ -295,7 +306,7 @@ class Trainer:
         return ckpt
 
     # ---------------------------------------------------------------------------------------------- train.py:265-385
-    def eval(self, eval_batch_fn, ckpt_dir, num=1, resized=(384, 1280)):
+    def eval(self, eval_batch_fn, ckpt_dir, num=1, resized=(384, 1280), terms=False):
         """Trainer.eval (train.py:265-385) without the TF summaries / plot process: every batch-1 example of eval_batch_fn()
         — (im1, im2, input_shape, flow_occ, mask_occ, flow_noc, mask_noc), kitti/input.py:75-82 — is brought from the
         input pipeline's crop / pad back to its own size and stretched onto the 384 x 1280 network input (resize_input),
@@ -303,7 +314,10 @@ class Trainer:
         ckpt_dir (restore_networks), the final flow is resized to the frame with per-axis rescaling (resize_output_flow) and
         compared with both ground-truth maps.  Returns what the reference writes to its 'eval_avg' summaries: the averages
         over the examples of AEE/<name>, outliers/<name> (name = occluded, non-occluded) and the loss; plus global_step
-        and the example count.  `per_example` (list of the per-example values) is kept for tests."""
+        and the example count.  `per_example` (list of the per-example values) is kept for tests.  terms=True adds the loss
+        terms of engine.loss_terms() under the reference's summary tags (train.py:314-328: 'loss/<term>' for all of LOSSES,
+        'loss<k>/<term>' per level and enabled term): averaged over the examples in the result, per example in
+        `per_example_terms`."""
         from . import tf_checkpoint as T
         from .flow_util import flow_error_avg, outlier_pct
         from .input import resize_input, resize_output_crop, resize_output_flow
@@ -320,7 +334,7 @@ class Trainer:
         self.restore(ckpt_dir, engine=eng)
         names = ['AEE/occluded', 'outliers/occluded', 'AEE/non-occluded', 'outliers/non-occluded', 'loss']
         sums = [0.0] * len(names)
-        per_example = []
+        per_example, per_example_terms = [], []
         for batch in eval_batch_fn():
             im1, im2, input_shape = (torch.as_tensor(t) for t in batch[:3])
             truths = [torch.as_tensor(t).float().to(dev) for t in batch[3:]]
@@ -338,6 +352,8 @@ class Trainer:
                 vals += [float(flow_error_avg(gt, flow, mask)), float(outlier_pct(gt, flow, mask))]
             vals.append(float(loss))
             per_example.append(vals)
+            if terms:
+                per_example_terms.append(term_tags(eng.loss_terms()))
             sums = [s0 + v for s0, v in zip(sums, vals)]
         n_ex = len(per_example)
         assert n_ex > 0, "eval_batch_fn() yielded no examples"
@@ -345,16 +361,19 @@ class Trainer:
         print("-- eval: i = {}".format(global_step))
         out = {k: s0 / n_ex for k, s0 in zip(names, sums)}
         out.update(global_step=global_step, num_examples=n_ex, per_example=per_example, names=names)
+        if terms:
+            out.update({k: sum(t[k] for t in per_example_terms) / n_ex for k in per_example_terms[0]})
+            out.update(per_example_terms=per_example_terms, term_names=list(per_example_terms[0]))
         return out
 
-    def run(self, min_iter, max_iter, train_batch_fn, ckpt_dir, eval_fn=None):
+    def run(self, min_iter, max_iter, train_batch_fn, ckpt_dir, eval_fn=None, on_display=None):
         """Trainer.run (train.py:116-145): train (at most) from min_iter + 1 to max_iter in chunks of params['save_interval']
         steps, a checkpoint after every chunk.  A checkpoint found in ckpt_dir must carry a global_step within [min_iter, max_iter];
         training then continues from global_step + 1.  train_batch_fn(iter_offset) returns an iterator of (im1, im2) batches
         already shifted by iter_offset steps (the reference builds its input queue with shift = batch_size * iter_offset) — of
         (im1, im2, flow_gt, mask_gt) batches for a supervised trainer;
-        eval_fn(i), if given, runs after each chunk (self.eval(1) of the reference).  Returns the list of (iteration, loss) at the
-        display interval."""
+        eval_fn(i), if given, runs after each chunk (self.eval(1) of the reference); on_display is handed to train().  Returns
+        the list of (iteration, loss) at the display interval."""
         save_interval = self.params['save_interval']
         global_step = self.checkpoint_step(ckpt_dir)
         if global_step is not None:
@@ -373,14 +392,17 @@ class Trainer:
             # Saver's scope and their Adam slots continue from the checkpoint just written (or start from params['finetune'] /
             # their initialisation), frozen networks come from finetune again and every other optimizer slot restarts at zero
             self.restore(ckpt_dir)
-            log += self.train(i, i + save_interval - 1, i - (min_iter + 1), train_batch_fn, ckpt_dir)
+            log += self.train(i, i + save_interval - 1, i - (min_iter + 1), train_batch_fn, ckpt_dir, on_display=on_display)
             if eval_fn is not None:
                 eval_fn(i + save_interval - 1)
         return log
 
-    def train(self, start_iter, max_iter, iter_offset, train_batch_fn, ckpt_dir):
+    def train(self, start_iter, max_iter, iter_offset, train_batch_fn, ckpt_dir, on_display=None):
         """Trainer.train (train.py:186-262): steps start_iter .. max_iter with the learning rate of decay_iters = local_i +
-        iter_offset (learning_rate_at), the loss printed at i == 1 and every display_interval, one checkpoint at the end."""
+        iter_offset (learning_rate_at), the loss printed at i == 1 and every display_interval, one checkpoint at the end.
+        on_display(i, loss, trainer), if given, is called at those display steps after the print — the host has synchronised
+        on the loss there, and the engine still holds the step's buffers (engine.loss_terms(); the step's learning rate is
+        self.last_lr)."""
         batches = iter(train_batch_fn(iter_offset))
         display = self.params.get('display_interval', 100)
         # every train() call of the reference builds a fresh graph and runs global_variables_initializer before the restore
@@ -402,6 +424,8 @@ class Trainer:
                 self._check_faults()                    # the host has just synchronised on the loss: read the fault counters
                 log.append((i, loss))
                 print("-- train: i = {}, loss = {}".format(i, loss))
+                if on_display is not None:
+                    on_display(i, loss, self)
         self._check_faults()                            # never checkpoint a run whose kernels reported a fault
         self.save(ckpt_dir, max_iter)
         return log
@@ -417,7 +441,7 @@ class Trainer:
         """sess.run([train_op, loss_]) (train.py:247-251): returns the loss tensor (device, no sync).  `augment`: None = the
         trainer's setting (random draws per step), False = off, or a dict of draws to replay.  target: (flow_gt, mask_gt)
         of a supervised trainer."""
-        lr = learning_rate_at(self.params, self.iteration)
+        lr = self.last_lr = learning_rate_at(self.params, self.iteration)
         aug = self.augment if augment is None else augment
         if aug is True:
             from .augment import draw_training_augmentation, draw_supervised_augmentation

@@ -80,14 +80,7 @@ def experiment_paths(name, config_path):
     return cfg, exp_dir
 
 
-class _KITTIData:
-    """What KITTIInput needs of the reference's KITTIData: the data root (dirs.data)."""
-
-    def __init__(self, root):
-        self.current_dir = root
-
-    def get_raw_dirs(self):
-        return []
+from .data import Data as _KITTIData      # the data root alone (dirs.data)       # noqa: E402
 
 
 def main(argv=None):

@@ -76,14 +76,7 @@ def parse_args(argv=None):
     return a
 
 
-class _Data:
-    """What the inputs need of the reference's Data classes: the data root (dirs.data)."""
-
-    def __init__(self, root):
-        self.current_dir = root
-
-    def get_raw_dirs(self):
-        return []
+from .data import Data as _Data      # the data root alone (dirs.data)       # noqa: E402
 
 
 def dataset_input(dataset, root, batch_size, dims):

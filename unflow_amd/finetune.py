@@ -13,8 +13,8 @@ resumes from the latest checkpoint found there, like the reference; the final ch
   chairs  ChairsInput.input_train_gt(): flying_chairs/image with the .flo files of flying_chairs/train_flow
 --geometric turns params['augment_geometric'] on: image pair and ground truth are transformed together (on kitti with
 gt_sampling = 'nearest', the sparse maps; a [train_*_ft] gt_sampling key wins).  The batches are decoded on the device
-(core/png_device.py) unless --host_decode.  Out of scope: the unsupervised datasets of run.py, summaries, evaluation during
-training (python -m unflow_amd.evaluate / evaluate_flo score a checkpoint)."""
+(core/png_device.py) unless --host_decode.  The unsupervised datasets of run.py, summaries and evaluation during training are
+python -m unflow_amd.run's (its kitti_ft branch takes this module's batches)."""
 import argparse
 import sys
 
@@ -63,14 +63,7 @@ def parse_args(argv=None):
     return a
 
 
-class _Data:
-    """What the inputs need of the reference's Data classes: the data root (dirs.data)."""
-
-    def __init__(self, root):
-        self.current_dir = root
-
-    def get_raw_dirs(self):
-        return []
+from .data import Data as _Data      # the data root alone (dirs.data)       # noqa: E402
 
 
 def finetune_params(config, dataset, geometric):
