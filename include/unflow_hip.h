@@ -768,6 +768,50 @@ int unflow_flo_to_flow_gt(const unsigned char* raw, long raw_bytes, const long* 
 int unflow_sintel_gt(const unsigned char* raw, long raw_bytes, const unsigned char* decoded, long decoded_bytes, const long* desc,
                      int n, int Hs, int Ws, float* flow, float* mask, unflow_stream_t stream);
 
+/* ===================================================================== */
+/* PNG encode on the device (csrc/png_encode.hip, core/png_device.py)      */
+/* ===================================================================== */
+
+/* A surface says where the raw bytes of a run of images come from, so no staging copy is made: `images` images, image_stride
+ * ELEMENTS apart, each an (H, W) allocation of `channels` interleaved samples per pixel with rows row_stride elements apart
+ * (row_stride >= W * channels, image_stride >= (H - 1) * row_stride + W * channels).  The image a table entry names sits at
+ * the origin of its allocation and may be smaller than (H, W).  kind is the sample:
+ *   UNFLOW_PNG_U8     uint8 elements, written as they are (the pictures: 3 channels; bytes per pixel = channels);
+ *   UNFLOW_PNG_U8X255 uint8 elements times 255 mod 256 (the occlusion masks: 0 / 1 -> 0 / 255, 1 channel);
+ *   UNFLOW_PNG_U16BE  16-bit elements (int16 or uint16 bit patterns; base 2-byte aligned), written high byte first, PNG's
+ *                     16-bit samples (out_u16: 3 channels, 6 bytes per pixel). */
+#define UNFLOW_PNG_U8 0
+#define UNFLOW_PNG_U8X255 1
+#define UNFLOW_PNG_U16BE 2
+typedef struct {
+  const void* base;
+  long image_stride;
+  long row_stride;
+  int images, H, W;
+  int channels; /* 1 .. 4 */
+  int kind;
+} unflow_png_surface;
+#define UNFLOW_PNG_SURFACES_MAX 16
+#define UNFLOW_PNG_FILTER_FIELDS 8
+#define UNFLOW_PNG_FILTER_MAX_ROW_BYTES 32512 /* w * bytes per pixel of one row: two rows of it live in LDS */
+
+/* PNG row filtering of n images in one launch, one workgroup per (image, row): for every entry of the DEVICE table
+ * desc[n][UNFLOW_PNG_FILTER_FIELDS] of int64 = {surface, image, h, w, dst, 0, 0, 0} — image `image` of the HOST array
+ * surfaces[surface], its top-left (h, w) pixels — the finished scanlines, h rows of 1 + w * bpp bytes with the filter byte first,
+ * are written to out[dst ...] (a DEVICE byte buffer of out_bytes).  max_h >= every h and max_row_bytes >= every w * bpp
+ * (<= UNFLOW_PNG_FILTER_MAX_ROW_BYTES, else UNFLOW_ERR_UNSUPPORTED).  An entry that does not fit its surface, max_row_bytes
+ * or the output buffer is skipped and its bytes left untouched (rows at and beyond max_h are not written); the caller
+ * validates the table, and that the ranges do not overlap, on the host (core/png_device.py).  Nothing outside the entries'
+ * ranges is written.
+ *
+ * The filter rule, exact integer work: for a row, the five filtered rows of the PNG specification are formed — 0 None, 1 Sub,
+ * 2 Up, 3 Average on the 9-bit sum, 4 Paeth with ties in the order left, up, upper left; a missing neighbour (left of the
+ * first pixel, above the first row) is 0.  The cost of a candidate is the sum over its bytes b of (b < 128 ? b : 256 - b); the
+ * filter of least cost is chosen, the lowest filter number on a tie.  So an all-zero row gets 0, and a first row where Sub
+ * wins gets 1, never 4 (Paeth predicts `left` there).  No float arithmetic and no atomics: bit-reproducible. */
+int unflow_png_filter(const unflow_png_surface* surfaces, int n_surfaces, const long* desc, int n, int max_h, int max_row_bytes,
+                      unsigned char* out, long out_bytes, unflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

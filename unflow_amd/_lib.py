@@ -51,6 +51,7 @@ def lib():
         _lib.unflow_flo_to_flow_gt.restype = ctypes.c_int
         _lib.unflow_sintel_gt.restype = ctypes.c_int
         _lib.unflow_supervised_geo_augment.restype = ctypes.c_int
+        _lib.unflow_png_filter.restype = ctypes.c_int
         _apply_env_options(_lib)
     return _lib
 
@@ -137,6 +138,19 @@ PNG_DESC_FIELDS = 8      # int64 per image of the PNG entries' table (include/un
 def png_unfilter_rows():
     """unflow_png_unfilter_rows: rows of an image that unflow_png_unfilter decodes together (host only)."""
     return int(lib().unflow_png_unfilter_rows())
+
+
+PNG_FILTER_FIELDS = 8    # int64 per entry of unflow_png_filter's table: surface, image, h, w, dst, 0, 0, 0
+PNG_SURFACES_MAX = 16
+PNG_FILTER_MAX_ROW_BYTES = 32512
+PNG_U8, PNG_U8X255, PNG_U16BE = 0, 1, 2
+
+
+class PngSurface(ctypes.Structure):
+    """unflow_png_surface of include/unflow_hip.h (one source of unflow_png_filter)."""
+    _fields_ = [('base', ctypes.c_void_p), ('image_stride', ctypes.c_long), ('row_stride', ctypes.c_long),
+                ('images', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int), ('channels', ctypes.c_int),
+                ('kind', ctypes.c_int)]
 
 
 class CarryBuf(ctypes.Structure):

@@ -177,6 +177,14 @@ class _Slot:
         self.vis = pin(len(VISUAL_IMAGES), B, Hm, Wm, 3, dtype=torch.uint8) if est.visual else None
         self.event = None
         self.pending = None
+        self.scan = self.scan_table = self.spans = None      # files through the device encode path (FlowEstimator._encoder)
+
+    def scan_buffers(self, enc):
+        """The pinned scanline buffer and table of this slot, sized like the estimator's device ones."""
+        if self.scan is None:
+            self.scan = torch.zeros(enc.scan.numel(), dtype=torch.uint8, pin_memory=True)
+            self.scan_table = torch.zeros(tuple(enc.table.shape), dtype=torch.int64, pin_memory=True)
+        return self.scan, self.scan_table
 
     def gt(self, est):
         if self.gt_flow is None:
@@ -188,6 +196,28 @@ class _Slot:
     def wait(self):
         if self.event is not None:
             self.event.synchronize()
+
+
+class _Encoder:
+    """The device half of FlowEstimator's file output (csrc/png_encode.hip): the surfaces unflow_png_filter reads — the
+    estimator's own output buffers, no staging copy — a device table and the device scanline buffer, sized for every file one
+    replay can ask for."""
+
+    def __init__(self, est):
+        from .png_device import PngSurface
+        B, Hm, Wm = est.B, est.Hmax, est.Wmax
+        named = [('u16', est.out_u16, B, 3, _lib.PNG_U16BE)]
+        if est.bidirectional:
+            named += [('u16_bw', est.out_u16_bw, B, 3, _lib.PNG_U16BE), ('occ', est.occ[0], B, 1, _lib.PNG_U8X255)]
+        if est.visual:
+            named += [('vis', est.vis, len(VISUAL_IMAGES) * B, 3, _lib.PNG_U8)]
+        self.index = {name: k for k, (name, *_) in enumerate(named)}
+        self.surfaces = [PngSurface(t, images, Hm, Wm, ch, kind) for _, t, images, ch, kind in named]
+        n_files = sum(s.images for s in self.surfaces)
+        n_bytes = sum(s.images * Hm * (1 + Wm * s.bpp) for s in self.surfaces)
+        with torch.cuda.device(est.dev):
+            self.table = torch.zeros(n_files, _lib.PNG_FILTER_FIELDS, dtype=torch.int64, device=est.dev)
+            self.scan = torch.zeros(n_bytes, dtype=torch.uint8, device=est.dev)
 
 
 class FlowEstimator:
@@ -256,6 +286,7 @@ class FlowEstimator:
         self._carry = 0               # sequence: the row that holds the clip's last frame (0: none yet)
         self._clip = None             # sequence: (h, w, dtype is uint8) of the clip's frames
         self._seq_k = 0               # sequence: replays submitted (the pinned slot alternates)
+        self._enc = None              # _Encoder, built by the first export through the device encode path
 
     # ------------------------------------------------------------------------------------------ parameters
     @classmethod
@@ -348,6 +379,27 @@ class FlowEstimator:
             self.graph = g
         self.graph.replay()
 
+    def _filter(self, slot, entries):
+        """The files of one replay through the device encode path: entries [(surface name, image, h, w), ...] -> one
+        unflow_png_filter launch on the current stream, right behind the replay and OUTSIDE the captured graph (the set of
+        wanted files varies per call), and the copy of the scanlines into the slot's pinned buffer.  slot.spans: per entry
+        (offset, bytes, h, w, depth, colour type) in that buffer."""
+        from .png_device import filter_scanlines, plan_scanlines
+        if not entries:
+            slot.spans = []
+            return
+        if self._enc is None:
+            self._enc = _Encoder(self)
+        enc = self._enc
+        scan, table = slot.scan_buffers(enc)
+        rows, spans, total, max_h, max_row = plan_scanlines(enc.surfaces, [(enc.index[s], im, h, w) for s, im, h, w in entries])
+        slot.spans = spans
+        n = len(entries)
+        table.numpy()[:n] = rows
+        enc.table[:n].copy_(table[:n], non_blocking=True)
+        filter_scanlines(enc.surfaces, enc.table, n, max_h, max_row, enc.scan, torch.cuda.current_stream(self.dev))
+        scan[:total].copy_(enc.scan[:total], non_blocking=True)
+
     # ------------------------------------------------------------------------------------------ staging
     def _slot(self, k):
         if self.slots is None:
@@ -425,9 +477,10 @@ class FlowEstimator:
                 put(self.gt_mask[m, :n], batch[4 + 2 * m][:n].reshape(n, hs, ws))
         return shapes
 
-    def _submit(self, k, examples, staged=None, nmaps=0, want=('flow',), device_batch=None):
+    def _submit(self, k, examples, staged=None, nmaps=0, want=('flow',), device_batch=None, files=None):
         """Stage batch k into its slot, copy it in, run, and queue the copies back; returns the slot.  device_batch: (batch,
-        n) — the first n examples of a batch of device tensors instead of `examples`."""
+        n) — the first n examples of a batch of device tensors instead of `examples`.  files: a function (shapes, nmaps) ->
+        _filter's entries — the scanlines of those files come back in slot.scan instead of the raw outputs."""
         slot = self._slot(k)
         slot.wait()                               # the last replay that read this slot's buffers (and its copies back) is done
         if device_batch is not None:
@@ -462,19 +515,21 @@ class FlowEstimator:
             if 'vis' in want:                     # the error image and the gt colours exist only with ground truth
                 nv = len(VISUAL_IMAGES) if nmaps else len(FlowVisual._fields)
                 slot.vis[:nv].copy_(self.vis[:nv], non_blocking=True)
+            if files is not None:
+                self._filter(slot, files(shapes, nmaps))
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
         slot.pending = (shapes, nmaps)
         return slot
 
-    def _pipeline(self, batches, staged=None, nmaps_of=lambda b: 0, want=('flow',)):
+    def _pipeline(self, batches, staged=None, nmaps_of=lambda b: 0, want=('flow',), files=None):
         """Yields (slot, shapes, nmaps, examples) per batch, in order; batch k + 1 is staged and queued before batch k is
         handed to the caller, so host packing overlaps the device."""
         prev = None
         for k, exs in enumerate(batches):
             nm = nmaps_of(exs)
-            slot = self._submit(k, exs, staged, nm, want)
+            slot = self._submit(k, exs, staged, nm, want, files=files)
             if prev is not None:
                 yield self._collect(*prev)
             prev = (slot, exs)
@@ -553,17 +608,31 @@ class FlowEstimator:
             out += [FlowVisual(*(v[k, i, :h, :w].copy() for k in range(3))) for i, (h, w) in enumerate(shapes)]
         return out
 
-    def pictures(self, batch_iter, num=None):
+    def pictures(self, batch_iter, num=None, scanlines=False):
         """The pictures of what KITTIInput.input_{train,test}_{2012,2015}() yields, one dict per example in iteration order:
         VISUAL_IMAGES' names -> uint8 [h, w, 3]; 'error' and 'gt' only when the input carries ground truth (two maps:
-        flow_error_image(flow, flow_occ, mask_occ, mask_noc) and flow_to_color(flow_occ, mask_occ); one map: mask_noc = ones)."""
+        flow_error_image(flow, flow_occ, mask_occ, mask_noc) and flow_to_color(flow_occ, mask_occ); one map: mask_noc = ones).
+        scanlines: every dict also has 'scanlines': image name -> (h, w, depth, colour type, bytes), the picture's finished PNG
+        scanlines from the device encode path (unflow_png_filter), what png_device.DeviceFileWriter.submit takes."""
         self._pair_mode('pictures')
         if not self.visual:
             raise RuntimeError("pictures: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
-        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, ('vis',), lambda exs: (len(exs[0]) - 3) // 2):
+        B, files = self.B, None
+        if scanlines:
+            def files(shapes, nmaps):
+                return [('vis', k * B + i, h, w) for i, (h, w) in enumerate(shapes) for k in range(len(VISUAL_IMAGES) if nmaps else 3)]
+        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, ('vis',), lambda exs: (len(exs[0]) - 3) // 2, files):
             v = slot.vis.numpy()
+            spans = iter(slot.spans or ())
             for i, (h, w) in enumerate(shapes):
-                yield {name: v[k, i, :h, :w].copy() for k, name in enumerate(VISUAL_IMAGES) if k < 3 or nmaps}
+                ex = {name: v[k, i, :h, :w].copy() for k, name in enumerate(VISUAL_IMAGES) if k < 3 or nmaps}
+                if scanlines:
+                    sc, buf = {}, slot.scan.numpy()
+                    for name in ex:
+                        off, nb, _, _, depth, ctype = next(spans)
+                        sc[name] = (h, w, depth, ctype, buf[off:off + nb].tobytes())
+                    ex['scanlines'] = sc
+                yield ex
 
     def evaluate(self, batch_iter, num=None):
         """Scores on what KITTIInput.input_train_{2012,2015}() yields — (im1, im2, input_shape, flow_occ, mask_occ, flow_noc,
@@ -612,7 +681,7 @@ class FlowEstimator:
                 raise ValueError("evaluate / export: the input's frames changed size (%s, then %s)" % (self._dims, dims))
             yield ex
 
-    def _pipeline_staged(self, it, want, nmaps_of):
+    def _pipeline_staged(self, it, want, nmaps_of, files=None):
         """_pipeline over examples of the KITTIInput layout."""
         self._dims = None
         gen = self._staged_examples(it)
@@ -620,14 +689,14 @@ class FlowEstimator:
         if first is None:
             return
         batches = chunks(itertools.chain([first], gen), self.B)
-        yield from self._pipeline(batches, staged=tuple(self._dims), nmaps_of=nmaps_of, want=want)
+        yield from self._pipeline(batches, staged=tuple(self._dims), nmaps_of=nmaps_of, want=want, files=files)
 
     def _on_device(self, batch):
         t = batch[0]
         return isinstance(t, torch.Tensor) and t.is_cuda and \
             t.device == torch.device('cuda', torch.cuda.current_device() if self.dev.index is None else self.dev.index)
 
-    def _pipeline_device(self, batches, num, want, nmaps_of):
+    def _pipeline_device(self, batches, num, want, nmaps_of, files=None):
         """_pipeline over batches of device tensors (DeviceEvalBatches): each is consumed as it comes, never re-chunked —
         its tensors are valid only until the iterator's next next(), and batch k is staged (copies enqueued on the current
         stream) before batch k + 1 is asked for."""
@@ -649,7 +718,7 @@ class FlowEstimator:
                 self._dims = dims
             elif dims != tuple(self._dims):
                 raise ValueError("evaluate / export: the input's frames changed size (%s, then %s)" % (self._dims, dims))
-            slot = self._submit(k, None, dims, nmaps_of([batch]), want, device_batch=(batch, n))
+            slot = self._submit(k, None, dims, nmaps_of([batch]), want, device_batch=(batch, n), files=files)
             done += n
             if prev is not None:
                 yield self._collect(*prev)
@@ -657,7 +726,7 @@ class FlowEstimator:
         if prev is not None:
             yield self._collect(*prev)
 
-    def _staged_input(self, batch_iter, num, want, nmaps_of):
+    def _staged_input(self, batch_iter, num, want, nmaps_of, files=None):
         """The batches of evaluate / export / pictures: host arrays go example by example through _pipeline_staged; batches of
         tensors on this estimator's device through _pipeline_device."""
         batch_iter = iter(batch_iter)
@@ -666,14 +735,15 @@ class FlowEstimator:
             return
         batches = itertools.chain([first], batch_iter)
         if self._on_device(first):
-            yield from self._pipeline_device(batches, num, want, nmaps_of)
+            yield from self._pipeline_device(batches, num, want, nmaps_of, files)
             return
         it = example_stream(batches)
         if num is not None:
             it = (ex for i, ex in zip(range(int(num)), it))
-        yield from self._pipeline_staged(it, want, nmaps_of)
+        yield from self._pipeline_staged(it, want, nmaps_of, files)
 
-    def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False, visual=False):
+    def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False, visual=False, workers=0,
+               level=6):
         """The benchmark files of eval_gui.py --output_benchmark (:247-263): for the k-th example in iteration order,
         out_dir/%06d_10.png (KITTI 16-bit RGB, --output_png) or out_dir/%06d_10.flo.  Input: what
         KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths (per example: _10, _01, _10_occ, then
@@ -684,7 +754,12 @@ class FlowEstimator:
         %06d_img.png (overlay), %06d_flow.png (flow colours), %06d_diff.png (brightness error) and, when the input carries
         ground truth (two maps or one), %06d_err.png (the KITTI error image) and %06d_gt.png (the ground truth's colours).
         eval_gui.py:248-254 writes the brightness error into _flow.png and the flow colours into _err.png and never writes the
-        error image; the names' evident meaning is followed here."""
+        error image; the names' evident meaning is followed here.
+        workers = 0 (the default): the host writers of core/input.py, one file after another on this thread (filter 0 on every
+        row).  workers >= 1: the device encode path — unflow_png_filter chooses and applies a filter per row right
+        behind each replay, the scanlines come back instead of the raw outputs, and a pool of `workers` threads
+        (png_device.DeviceFileWriter) deflates at `level` and writes; .flo files go through the same pool.  The same paths in
+        the same order, files that decode to the same pixels (.flo: the same bytes), all written when the call returns."""
         from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         self._pair_mode('export')
         if fmt not in ('png', 'flo'):
@@ -705,6 +780,8 @@ class FlowEstimator:
         n = 0
         # the ground truth is staged only for the pictures that show it
         nmaps_of = (lambda exs: (len(exs[0]) - 3) // 2) if visual else (lambda exs: 0)
+        if workers:
+            return self._export_pool(batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level)
         for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, nmaps_of):
             for i, (h, w) in enumerate(shapes):
                 flows = [('10', slot.u16, slot.flow)] + ([('01', slot.u16_bw, slot.flow_bw)] if backward else [])
@@ -727,6 +804,47 @@ class FlowEstimator:
                         paths.append(path)
                 n += 1
         return paths
+
+    def _export_pool(self, batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level):
+        """export through the device encode path: the file list of export's loop, each PNG as an entry of the replay's
+        unflow_png_filter launch and a job of the writer pool."""
+        from .png_device import DeviceFileWriter, flo_file_bytes
+        B = self.B
+        tags = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
+
+        def files(shapes, nmaps):
+            ents = []
+            for i, (h, w) in enumerate(shapes):
+                if fmt == 'png':
+                    ents += [(u16, i, h, w) for _, u16, _ in tags]
+                if occlusion:
+                    ents.append(('occ', i, h, w))
+                if visual:
+                    ents += [('vis', k * B + i, h, w) for k, _ in visual_files(0, nmaps > 0)]
+            return ents
+        want = tuple(flow for _, _, flow in tags) if fmt == 'flo' else ()
+        n = 0
+        with DeviceFileWriter(workers, level) as pool:
+            for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, nmaps_of, files):
+                spans, scan = iter(slot.spans), slot.scan.numpy()
+
+                def png(name):
+                    off, nb, h, w, depth, ctype = next(spans)
+                    pool.submit(os.path.join(out_dir, name), 'png', (h, w, depth, ctype, scan[off:off + nb].tobytes()))
+                for i, (h, w) in enumerate(shapes):
+                    for tag, _, flow in tags:
+                        if fmt == 'png':
+                            png('%06d_%s.png' % (n, tag))
+                        else:
+                            pool.submit(os.path.join(out_dir, '%06d_%s.flo' % (n, tag)), 'flo',
+                                        flo_file_bytes(getattr(slot, flow).numpy()[i, :h, :w]))
+                    if occlusion:
+                        png('%06d_10_occ.png' % n)
+                    if visual:
+                        for _, name in visual_files(n, nmaps > 0):
+                            png(name)
+                    n += 1
+        return list(pool.paths)
 
     # ------------------------------------------------------------------------------------------ sequence mode
     def reset(self):
@@ -761,9 +879,9 @@ class FlowEstimator:
             out.append(a)
         return out
 
-    def _submit_sequence(self, frames, want=('flow',)):
+    def _submit_sequence(self, frames, want=('flow',), encode=False):
         """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns (slot, valid
-        pair slots)."""
+        pair slots).  encode: the valid pairs' flow PNGs go through the device encode path (_filter) into slot.scan."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
@@ -794,6 +912,8 @@ class FlowEstimator:
                 slot.flow.copy_(self.out_flow, non_blocking=True)
             if 'u16' in want:
                 slot.u16.copy_(self.out_u16, non_blocking=True)
+            if encode:
+                self._filter(slot, [('u16', i, h, w) for i in valid])
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -811,14 +931,14 @@ class FlowEstimator:
         fl = slot.flow.numpy()
         return [fl[i, :h, :w].copy() for i in valid]
 
-    def _pipeline_sequence(self, frames, want):
+    def _pipeline_sequence(self, frames, want, encode=False):
         """reset, then pipelined pushes of B frames: yields (slot, valid pair slots) per replay; replay k + 1 is staged and
         queued before replay k is handed out."""
         self.reset()
         prev, total = None, 0
         for chunk in chunks(frames, self.B):
             total += len(chunk)
-            cur = self._submit_sequence(chunk, want)
+            cur = self._submit_sequence(chunk, want, encode)
             if prev is not None:
                 prev[0].wait()
                 yield prev
@@ -839,14 +959,30 @@ class FlowEstimator:
             out += [fl[i, :h, :w].copy() for i in valid]
         return out
 
-    def export_sequence(self, frames, out_dir, fmt='png'):
+    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
-        -> frame n + 1), with export's writers.  Returns the written paths."""
+        -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
+        writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one)."""
         from .input import write_flo, write_kitti_flow_png
         self._sequence_mode('export_sequence')
         if fmt not in ('png', 'flo'):
             raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
         os.makedirs(out_dir, exist_ok=True)
+        if workers:
+            from .png_device import DeviceFileWriter, flo_file_bytes
+            n = 0
+            with DeviceFileWriter(workers, level) as pool:
+                for slot, valid in self._pipeline_sequence(frames, ('flow',) if fmt == 'flo' else (), encode=fmt == 'png'):
+                    h, w, _ = self._clip
+                    for j, i in enumerate(valid):
+                        path = os.path.join(out_dir, '%06d_10.%s' % (n, fmt))
+                        if fmt == 'png':
+                            off, nb, _, _, depth, ctype = slot.spans[j]
+                            pool.submit(path, 'png', (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
+                        else:
+                            pool.submit(path, 'flo', flo_file_bytes(slot.flow.numpy()[i, :h, :w]))
+                        n += 1
+            return list(pool.paths)
         paths = []
         for slot, valid in self._pipeline_sequence(frames, ('u16',) if fmt == 'png' else ('flow',)):
             h, w, _ = self._clip

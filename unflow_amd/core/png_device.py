@@ -20,6 +20,10 @@ straight into the pinned staging slot and csrc/flo_decode.hip cuts the window an
   * unflow_flo_to_flow_gt the Middlebury / Chairs rule: the file's floats and mask = both components < 1e9;
   * unflow_sintel_gt      Sintel's composition of a .flo file with its `invalid` and `occlusions` PNGs -> two maps.
 
+The output side mirrors it (the end of this file): unflow_png_filter (csrc/png_encode.hip) chooses and applies the
+PNG row filters on the device, DeviceFileWriter deflates and writes on a thread pool; encode_png_device is decode_png_device's
+counterpart.
+
 There is no host fallback: without the library's kernels these raise."""
 import collections
 import ctypes
@@ -780,3 +784,233 @@ class DeviceEvalBatches(_DeviceBatches):
         for g in range(self.planner.n_maps):
             out += [s.flow[g * n:(g + 1) * n], s.mask[g * n:(g + 1) * n]]
         return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------------------ PNG encode
+# The output side of the same split (csrc/png_encode.hip): the GPU chooses and applies the row filters
+# (unflow_png_filter: finished scanlines, filter byte included, for a list of images in one launch), the host deflates them, on a
+# pool — zlib.compress and zlib.crc32 release the GIL — and writes the files.
+_CTYPE_OF_CHANNELS = {1: 0, 2: 4, 3: 2, 4: 6}
+PNG_LEVELS = range(0, 10)
+
+
+def check_level(level):
+    if isinstance(level, bool) or int(level) != level or int(level) not in PNG_LEVELS:
+        raise ValueError("a deflate level is an integer in [0, 9], got %r" % (level,))
+    return int(level)
+
+
+def _chunk(typ, body):
+    return struct.pack('>I', len(body)) + typ + body + struct.pack('>I', zlib.crc32(body, zlib.crc32(typ)) & 0xffffffff)
+
+
+def assemble_png(h, w, depth, ctype, scanlines, level=6, compress=zlib.compress):
+    """Finished scanlines (h rows of 1 + w * bpp bytes, the filter byte first) -> PNG file bytes: IHDR, one IDAT, IEND.  Host
+    only; `scanlines` is anything with the buffer protocol."""
+    _check_variant(depth, ctype, 0)
+    scan = memoryview(scanlines).cast('B')
+    if len(scan) != h * (1 + w * _bpp(depth, ctype)):
+        raise ValueError("%d bytes of scanlines for a %d x %d image of %d bytes per pixel" % (len(scan), h, w, _bpp(depth, ctype)))
+    return b''.join((PNG_SIGNATURE, _chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, depth, ctype, 0, 0, 0)),
+                     _chunk(b'IDAT', compress(scan, level)), _chunk(b'IEND', b'')))
+
+
+class PngSurface:
+    """Where unflow_png_filter reads images from (unflow_png_surface of include/unflow_hip.h): `images` allocations of (H, W)
+    pixels of `channels` samples in the device tensor `tensor`, strides in elements; kind = _lib.PNG_U8 / PNG_U8X255 / PNG_U16BE."""
+
+    def __init__(self, tensor, images, H, W, channels, kind, image_stride=None, row_stride=None):
+        self.tensor, self.images, self.H, self.W, self.channels, self.kind = tensor, int(images), int(H), int(W), int(channels), kind
+        self.row_stride = self.W * self.channels if row_stride is None else int(row_stride)
+        self.image_stride = self.H * self.row_stride if image_stride is None else int(image_stride)
+        self.depth = 16 if kind == _lib.PNG_U16BE else 8
+        self.bpp = self.channels * self.depth // 8
+        self.ctype = _CTYPE_OF_CHANNELS[self.channels]
+        want = 2 if kind == _lib.PNG_U16BE else 1
+        if tensor.element_size() != want or not tensor.is_cuda:
+            raise ValueError("a PNG surface of kind %d takes a device tensor of %d-byte elements" % (kind, want))
+        last = (self.images - 1) * self.image_stride + (self.H - 1) * self.row_stride + self.W * self.channels
+        if self.row_stride < self.W * self.channels or last > tensor.numel() or not tensor.is_contiguous() or \
+                self.image_stride < (self.H - 1) * self.row_stride + self.W * self.channels:
+            raise ValueError("a PNG surface of %d x (%d, %d, %d) with strides (%d, %d) leaves its tensor of %d elements"
+                             % (self.images, self.H, self.W, self.channels, self.image_stride, self.row_stride, tensor.numel()))
+
+    def c(self):
+        return _lib.PngSurface(self.tensor.data_ptr(), self.image_stride, self.row_stride, self.images, self.H, self.W,
+                               self.channels, self.kind)
+
+
+def plan_scanlines(surfaces, entries, first=0):
+    """Host packing of unflow_png_filter's table.  entries: [(surface index, image, h, w), ...] -> (rows int64 [n][8], spans
+    [(offset, bytes, h, w, depth, ctype)], end offset, max h, max row bytes): image k's scanlines lie at [offset, offset +
+    bytes) of the output buffer, back to back from `first`.  Everything the kernel would skip raises ValueError here."""
+    rows = np.zeros((len(entries), _lib.PNG_FILTER_FIELDS), dtype=np.int64)
+    spans, off, max_h, max_row = [], int(first), 1, 1
+    for k, (si, image, h, w) in enumerate(entries):
+        if not 0 <= si < len(surfaces):
+            raise ValueError("entry %d names surface %d of %d" % (k, si, len(surfaces)))
+        s = surfaces[si]
+        if not (0 <= image < s.images and 1 <= h <= s.H and 1 <= w <= s.W):
+            raise ValueError("entry %d: image %d of %d x %d leaves its surface (%d images of %d x %d)"
+                             % (k, image, h, w, s.images, s.H, s.W))
+        if w * s.bpp > _lib.PNG_FILTER_MAX_ROW_BYTES:
+            raise ValueError("entry %d: a row of %d bytes (the filter kernel takes %d)" % (k, w * s.bpp, _lib.PNG_FILTER_MAX_ROW_BYTES))
+        n = h * (1 + w * s.bpp)
+        rows[k, :5] = (si, image, h, w, off)
+        spans.append((off, n, h, w, s.depth, s.ctype))
+        off, max_h, max_row = off + n, max(max_h, h), max(max_row, w * s.bpp)
+    return rows, spans, off, max_h, max_row
+
+
+def filter_scanlines(surfaces, table_dev, n, max_h, max_row, out_dev, stream):
+    """One unflow_png_filter launch on `stream`: the n entries of the device table -> scanlines in out_dev."""
+    if len(surfaces) > _lib.PNG_SURFACES_MAX:
+        raise ValueError("%d surfaces in one launch (at most %d)" % (len(surfaces), _lib.PNG_SURFACES_MAX))
+    arr = (_lib.PngSurface * len(surfaces))(*[s.c() for s in surfaces])
+    check(_lib.lib().unflow_png_filter(arr, len(surfaces), ptr(table_dev), int(n), int(max_h), int(max_row), ptr(out_dev),
+                                       _lib.cl(out_dev.numel()), _stream_ptr(stream)), "png_filter")
+
+
+def _surface_of(t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("encode_png_device takes device tensors")
+    if t.ndim == 2 and t.dtype == torch.uint8:
+        ch, kind = 1, _lib.PNG_U8
+    elif t.ndim == 3 and t.shape[2] == 3 and t.dtype == torch.uint8:
+        ch, kind = 3, _lib.PNG_U8
+    elif t.ndim == 3 and t.shape[2] == 3 and t.dtype in (torch.int16, torch.uint16):
+        ch, kind = 3, _lib.PNG_U16BE
+    else:
+        raise ValueError("encode_png_device: uint8 [h,w], uint8 [h,w,3] or uint16 / int16 [h,w,3], got %s %s" % (t.dtype, tuple(t.shape)))
+    if t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("encode_png_device: an empty image %s" % (tuple(t.shape),))
+    t = t.contiguous()
+    return PngSurface(t, 1, t.shape[0], t.shape[1], ch, kind)
+
+
+def scanlines_device(images):
+    """[device tensor, ...] -> (uint8 device tensor of all scanlines, spans as plan_scanlines'): the filter half of
+    encode_png_device.  One launch serves up to 16 images (the kernel's surface list); a longer list takes one launch per 16."""
+    surfaces = [_surface_of(t) for t in images]
+    if not surfaces:
+        return None, []
+    dev = surfaces[0].tensor.device
+    rows, spans, total, _, _ = plan_scanlines(surfaces, [(k, 0, s.H, s.W) for k, s in enumerate(surfaces)])
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        step = _lib.PNG_SURFACES_MAX
+        for k0 in range(0, len(surfaces), step):
+            part = surfaces[k0:k0 + step]
+            r = rows[k0:k0 + step].copy()
+            r[:, 0] -= k0
+            table = torch.from_numpy(r).to(dev)
+            filter_scanlines(part, table, len(part), max(s.H for s in part), max(s.W * s.bpp for s in part), out, stream)
+    return out, spans
+
+
+def encode_png_device(images, level=6):
+    """[device tensor uint8 [h,w] / uint8 [h,w,3] / uint16 or int16 [h,w,3], ...] -> [PNG file bytes, ...]: the counterpart of
+    decode_png_device — decode_png(encode_png_device([x])[0]) and decode_png_device(...) return x exactly (int16 as its uint16
+    bit pattern).  The row filters are chosen and applied on the device (unflow_png_filter: least sum of absolute differences
+    per row); the host deflates at `level` and assembles IHDR, one IDAT and IEND."""
+    level = check_level(level)
+    out, spans = scanlines_device(images)
+    if out is None:
+        return []
+    host = out.cpu().numpy()
+    return [assemble_png(h, w, depth, ctype, host[off:off + n], level) for off, n, h, w, depth, ctype in spans]
+
+
+def flo_file_bytes(flow):
+    """float32 [h,w,2] -> the bytes of a .flo file (write_flo's)."""
+    flow = np.ascontiguousarray(flow, dtype='<f4')
+    h, w, _ = flow.shape
+    return struct.pack('<f', FLO_TAG) + struct.pack('<ii', w, h) + flow.tobytes()
+
+
+class DeviceFileWriter:
+    """The ordered writer pool of the device encode path: submit(path, kind, payload) queues one file and returns at once;
+    a worker deflates, forms the chunk CRCs and writes it.
+
+        kind 'png': payload = (h, w, depth, ctype, scanlines) — host bytes that are already filtered (assemble_png);
+        kind 'flo': payload = the file's bytes (flo_file_bytes), written as they are through the same pool.
+
+    workers is capped by MAX_WORKERS (never sized from os.cpu_count()).  At most `bound` = 2 * workers files are pending
+    (submitted and not yet written): a producer that gets ahead blocks in submit, so the memory behind the payloads stays
+    bounded.  A payload must stay unchanged until its file is written; the estimator hands over copies.  close() / leaving the
+    `with` block waits for every file and raises RuntimeError naming the path of the first (in submission order) file whose
+    worker failed, chained to the worker's exception.  Workers receive host bytes only and never touch the GPU — neither a
+    launch nor a sync nor a copy — so they may run while another thread captures a graph.  `paths` lists the submitted paths in
+    order; `written` and `file_bytes` count what the workers finished."""
+
+    KINDS = ('png', 'flo')
+
+    def __init__(self, workers=8, level=6, compress=zlib.compress):
+        self.workers = max(1, min(int(workers), MAX_WORKERS))
+        self.level = check_level(level)
+        self.bound = 2 * self.workers
+        self.compress = compress
+        self.paths = []
+        self.written = self.file_bytes = self.pending = self.max_pending = 0
+        self._lock = threading.Lock()
+        self._room = threading.BoundedSemaphore(self.bound)
+        self._error = None                           # (submission number, path, exception) of the earliest failure
+        self._pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="png-deflate")
+        self._closed = False
+
+    def submit(self, path, kind, payload):
+        if self._closed:
+            raise RuntimeError("DeviceFileWriter is closed")
+        if kind not in self.KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (self.KINDS, kind))
+        self._room.acquire()                         # blocks while `bound` files are pending
+        with self._lock:
+            seq = len(self.paths)
+            self.paths.append(path)
+            self.pending += 1
+            self.max_pending = max(self.max_pending, self.pending)
+        self._pool.submit(self._work, seq, path, kind, payload)
+
+    def _work(self, seq, path, kind, payload):
+        n = 0
+        try:
+            if kind == 'png':
+                h, w, depth, ctype, scan = payload
+                data = assemble_png(h, w, depth, ctype, scan, self.level, self.compress)
+            else:
+                data = payload
+            with open(path, 'wb') as f:
+                f.write(data)
+            n = len(data)
+        except BaseException as e:
+            with self._lock:
+                if self._error is None or seq < self._error[0]:
+                    self._error = (seq, path, e)
+        finally:
+            with self._lock:
+                self.pending -= 1
+                if n:
+                    self.written += 1
+                    self.file_bytes += n
+            self._room.release()
+
+    def close(self):
+        """Wait for every submitted file; raise the first failure."""
+        if not self._closed:
+            self._closed = True
+            self._pool.shutdown(wait=True)
+        err, self._error = self._error, None
+        if err is not None:
+            raise RuntimeError("writing %s failed: %s: %s" % (err[1], type(err[2]).__name__, err[2])) from err[2]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:                                        # the caller's exception wins; still leave no thread behind
+            self._closed = True
+            self._pool.shutdown(wait=True)
+        return False

@@ -11,7 +11,9 @@ The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives
 --output_backward branch means to write).  --occlusion runs both directions and adds the forward-backward occlusion mask
 (losses.occlusion): this project's occlusion precision / recall / F1 against KITTI's occluded pixels on train_* variants,
 and %06d_10_occ.png (8-bit, 255 = occluded) with --output_benchmark.  The pictures (colour wheel, error map, overlay) are
-python -m unflow_amd.visualize's; Sintel, FlyingChairs and Middlebury are python -m unflow_amd.evaluate_flo's."""
+python -m unflow_amd.visualize's; Sintel, FlyingChairs and Middlebury are python -m unflow_amd.evaluate_flo's.
+--workers N (N >= 1) writes the files through the device encode path: PNG row filters on the GPU, N threads that
+deflate at --level L (6) and write; the default and --host_encode: the host's writers, one file after another."""
 import argparse
 import os
 import shutil
@@ -38,6 +40,7 @@ def parser():
     ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
     ap.add_argument('--host_decode', action='store_true',
                     help="decode the PNG files with the host's decoder (slow) instead of the library's PNG kernels")
+    add_encode_flags(ap)
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
     ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
     ap.add_argument('--dims', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
@@ -45,10 +48,30 @@ def parser():
     return ap
 
 
+def add_encode_flags(ap):
+    """The output flags the file-writing commands share (evaluate, evaluate_flo, visualize, sequence)."""
+    ap.add_argument('--workers', type=int, default=0, metavar='N',
+                    help='N >= 1: write the output files through the device encode path, the PNG filter kernel and N threads '
+                         'that deflate and write (at most 16; 8 is a good value); 0, the default: the host writers')
+    ap.add_argument('--level', type=int, default=6, metavar='L', help='deflate level of the PNG files, 0 .. 9')
+    ap.add_argument('--host_encode', action='store_true',
+                    help="write the files one after another with the host's PNG writers (filter 0), whatever --workers says")
+
+
+def check_encode_flags(ap, a):
+    """Refuses a bad --workers / --level (status 2); a.encode_workers: FlowEstimator.export's workers (0 with --host_encode)."""
+    if a.workers < 0:
+        ap.error("--workers must not be negative (0: the host's writers)")
+    if not 0 <= a.level <= 9:
+        ap.error("--level must be in 0 .. 9, got %d" % a.level)
+    a.encode_workers = 0 if a.host_encode else a.workers
+
+
 def parse_args(argv=None):
     """Parsed flags; refuses what this tool does not do with a clear message (SystemExit, status 2)."""
     ap = parser()
     a = ap.parse_args(argv)
+    check_encode_flags(ap, a)
     if a.dataset != 'kitti':
         ap.error("--dataset %s is not supported here (only kitti; python -m unflow_amd.evaluate_flo scores and draws sintel / "
                  "chairs / mdb)" % a.dataset)
@@ -114,7 +137,7 @@ def main(argv=None):
         os.makedirs(out_dir)
         shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
         paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=num, backward=a.output_backward,
-                           occlusion=a.occlusion)
+                           occlusion=a.occlusion, workers=a.encode_workers, level=a.level)
         print("wrote %d files to %s" % (len(paths), out_dir))
     return 0
 

@@ -19,7 +19,7 @@ import os
 import shutil
 import sys
 
-from .evaluate import experiment_paths
+from .evaluate import add_encode_flags, check_encode_flags, experiment_paths
 
 DATASETS = {      # variants (the first is the default), eval_gui.py's dims
     'sintel': (('train_clean', 'train_final', 'test_clean', 'test_final'), (512, 1024)),
@@ -46,6 +46,7 @@ def parser():
     ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
     ap.add_argument('--host_decode', action='store_true',
                     help="read the files with the host's decoders (slow) instead of the library's kernels")
+    add_encode_flags(ap)
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
     ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
     ap.add_argument('--dims', type=int, nargs=2, default=None, metavar=('H', 'W'), help="network input size (default: eval_gui.py's)")
@@ -57,6 +58,7 @@ def parse_args(argv=None):
     do with a clear message (SystemExit, status 2)."""
     ap = parser()
     a = ap.parse_args(argv)
+    check_encode_flags(ap, a)
     variants, dims = DATASETS[a.dataset]
     if a.variant is None:
         a.variant = variants[0]
@@ -139,7 +141,7 @@ def main(argv=None):
         os.makedirs(out_dir)
         shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
         paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=a.num, backward=a.output_backward,
-                           occlusion=a.occlusion, visual=a.visual)
+                           occlusion=a.occlusion, visual=a.visual, workers=a.encode_workers, level=a.level)
         if a.sheet:
             paths += write_sheets(out_dir, sum(p.endswith('_img.png') for p in paths), a.has_gt, a.num_vis)
         print("wrote %d files to %s" % (len(paths), out_dir))

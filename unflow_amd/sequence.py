@@ -6,7 +6,8 @@ once (core/inference.FlowEstimator(..., sequence=True)).
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
 experiment's config and latest checkpoint are found as python -m unflow_amd.evaluate finds them.  Files go to <--out>/NAME/:
-%06d_10.png (KITTI 16-bit flow) or, with --flo, %06d_10.flo."""
+%06d_10.png (KITTI 16-bit flow) or, with --flo, %06d_10.flo — with --workers N (N >= 1) through the device encode path (DESIGN 7.11; --level L);
+the default and --host_encode: the host's writers."""
 import argparse
 import os
 import sys
@@ -91,6 +92,8 @@ def parser():
                     help='network input size (multiples of 64)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
+    from .evaluate import add_encode_flags
+    add_encode_flags(ap)
     return ap
 
 
@@ -98,6 +101,8 @@ def parse_args(argv=None):
     """Parsed flags plus a.files; a folder that holds no clip is an argparse error (SystemExit, status 2)."""
     ap = parser()
     a = ap.parse_args(argv)
+    from .evaluate import check_encode_flags
+    check_encode_flags(ap, a)
     if a.batch <= 0:
         ap.error("--batch must be positive")
     if a.net_size[0] % 64 or a.net_size[1] % 64 or min(a.net_size) <= 0:
@@ -136,7 +141,7 @@ def main(argv=None):
                                                            a.frames))
     try:
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
-        paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png')
+        paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))

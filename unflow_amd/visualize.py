@@ -18,7 +18,7 @@ import sys
 
 import numpy as np
 
-from .evaluate import VARIANTS, _KITTIData, experiment_paths
+from .evaluate import VARIANTS, _KITTIData, add_encode_flags, check_encode_flags, experiment_paths
 
 EXAMPLES_PER_PAGE = 4                                   # eval_gui.py NUM_EXAMPLES_PER_PAGE
 # the columns of a sheet: eval_gui.py's image slots on ground truth (:160-178, :190-194) and without (:199-204)
@@ -36,6 +36,7 @@ def parser():
     ap.add_argument('--batch_size', type=int, default=4, help='pairs per graph replay')
     ap.add_argument('--host_decode', action='store_true',
                     help="decode the PNG files with the host's decoder (slow) instead of the library's PNG kernels")
+    add_encode_flags(ap)
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: data, log, checkpoints)')
     ap.add_argument('--out', default='../out', help='output root: files go to <out>/<ex>/')
     ap.add_argument('--dims', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
@@ -47,6 +48,7 @@ def parse_args(argv=None):
     """Parsed flags; refuses what this tool does not do with a clear message (SystemExit, status 2)."""
     ap = parser()
     a = ap.parse_args(argv)
+    check_encode_flags(ap, a)
     if a.dataset != 'kitti':
         ap.error("--dataset %s is not supported here (only kitti; python -m unflow_amd.evaluate_flo scores and draws sintel / "
                  "chairs / mdb)" % a.dataset)
@@ -79,12 +81,18 @@ def sheet_name(page):
     return 'page_%03d.png' % page
 
 
-def write_pictures(examples, out_dir, sheet=False, num_vis=100):
+def write_pictures(examples, out_dir, sheet=False, num_vis=100, workers=0, level=6):
     """Writes the picture files of every example (dicts of FlowEstimator.pictures) and, with sheet, the contact sheets of the
-    first num_vis of them; returns the written paths."""
+    first num_vis of them; returns the written paths.  workers >= 1: the per-example pictures go through a writer pool
+    (png_device.DeviceFileWriter) from the examples' 'scanlines' (FlowEstimator.pictures(..., scanlines=True)); the contact sheets
+    are composed and written on the host either way."""
     from .core.inference import VISUAL_IMAGES, visual_files
     from .core.input import write_png_rgb8
     paths, page_rows, page = [], [], 0
+    pool = None
+    if workers:
+        from .core.png_device import DeviceFileWriter
+        pool = DeviceFileWriter(workers, level)
 
     def flush():
         nonlocal page_rows, page
@@ -93,16 +101,26 @@ def write_pictures(examples, out_dir, sheet=False, num_vis=100):
             write_png_rgb8(p, contact_sheet(page_rows))
             paths.append(p)
             page_rows, page = [], page + 1
-    for n, ex in enumerate(examples):
-        for k, name in visual_files(n, 'error' in ex):
-            p = os.path.join(out_dir, name)
-            write_png_rgb8(p, ex[VISUAL_IMAGES[k]])
-            paths.append(p)
-        if sheet and n < num_vis:
-            page_rows.append([ex[c] for c in SHEET_COLUMNS['error' in ex]])
-            if len(page_rows) == EXAMPLES_PER_PAGE:
-                flush()
-    flush()
+    try:
+        for n, ex in enumerate(examples):
+            for k, name in visual_files(n, 'error' in ex):
+                p = os.path.join(out_dir, name)
+                if pool is not None:
+                    pool.submit(p, 'png', ex['scanlines'][VISUAL_IMAGES[k]])
+                else:
+                    write_png_rgb8(p, ex[VISUAL_IMAGES[k]])
+                paths.append(p)
+            if sheet and n < num_vis:
+                page_rows.append([ex[c] for c in SHEET_COLUMNS['error' in ex]])
+                if len(page_rows) == EXAMPLES_PER_PAGE:
+                    flush()
+        flush()
+    except BaseException:
+        if pool is not None:
+            pool.__exit__(*sys.exc_info())
+        raise
+    if pool is not None:
+        pool.close()
     return paths
 
 
@@ -127,8 +145,8 @@ def main(argv=None):
     shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
     print("-- visualising %s (step %s) on kitti %s" % (a.ex, est.global_step, a.variant))
     batches = getattr(kinput, 'input_' + a.variant)(device=None if a.host_decode else est.dev)
-    examples = est.pictures(batches, num=None if a.num < 0 else a.num)
-    paths = write_pictures(examples, out_dir, sheet=a.sheet, num_vis=a.num_vis)
+    examples = est.pictures(batches, num=None if a.num < 0 else a.num, scanlines=a.encode_workers > 0)
+    paths = write_pictures(examples, out_dir, sheet=a.sheet, num_vis=a.num_vis, workers=a.encode_workers, level=a.level)
     print("wrote %d files to %s" % (len(paths), out_dir))
     return 0
 
