@@ -812,6 +812,68 @@ typedef struct {
 int unflow_png_filter(const unflow_png_surface* surfaces, int n_surfaces, const long* desc, int n, int max_h, int max_row_bytes,
                       unsigned char* out, long out_bytes, unflow_stream_t stream);
 
+/* A non-blocking HIP stream on the current device that belongs to no framework's stream pool (host only, no launch): the
+ * loader's side stream, see core/png_device.py::loader_stream.  The caller keeps it for the life of the process. */
+int unflow_stream_create(unflow_stream_t* stream);
+
+/* ---- deflate on the device (csrc/deflate.hip; tests/deflate_ref.py is the same rule in Python, equal byte for byte).
+ *
+ * The stream format, exact integer work.  A stream of `bytes` >= 1 bytes is cut into chunks of chunk_bytes (1 ..
+ * UNFLOW_DEFLATE_CHUNK_MAX = 65535, so one stored block always covers a chunk; the last chunk is what is left).  Chunks are coded
+ * independently — no match reaches before its chunk's first byte — each as ONE deflate block (RFC 1951), BFINAL set in the last
+ * chunk's.  A chunk's segment is formed in three codings and the one of fewest segment BYTES is emitted, the lowest number on a
+ * tie:
+ *   0  stored: the byte BFINAL, LEN, NLEN, the chunk: 5 + n bytes.  Byte-aligned by itself, so it carries no marker.
+ *   1  dynamic Huffman over the literals (and end-of-block) only.
+ *   2  dynamic Huffman over literals and distance-1 matches.  A run is a maximal stretch of L bytes that equal their
+ *      predecessor (the byte before the run is a literal).  L < 3: literals.  Otherwise L / 258 matches of length 258 from the
+ *      run's start, and for the remainder r = L % 258 one match of r if r >= 3, else r literals.  So nothing of a run is lost.
+ * A Huffman segment that is not the stream's last ends with the sync-flush marker — the three header bits of an empty stored
+ * block, zero bits to the byte boundary, 00 00 FF FF — so segments concatenate without bit shifting; the last ends with zero
+ * bits to the byte boundary.
+ *
+ * Code lengths, for the literal / length alphabet (286 symbols, limit 15) and the code-length alphabet (19 symbols, limit 7):
+ * the symbols of non-zero count are sorted by (count, symbol).  One such symbol gets length 1.  Otherwise Moffat and Katajainen's
+ * in-place minimum-redundancy construction on the sorted counts (a leaf is taken before an internal node of equal weight) gives
+ * the number of leaves per depth; depths above the limit count at the limit; the repair rule: while the Kraft sum exceeds 1, one
+ * leaf is taken from the limit's level and the deepest non-empty level below the limit hands one leaf to the next level as two
+ * (each round lowers the sum by exactly one unit of 2^-limit).  The levels are then dealt out from the deepest: the least
+ * (count, symbol) gets the longest code.  Codes are canonical (RFC 1951 3.2.2).
+ *
+ * The block header: HLIT = last used literal / length symbol - 256, HDIST = 0 — ONE distance code, of length 1, in both Huffman
+ * codings (its code is the bit 0; distance 1 has no extra bits) — HCLEN = the last non-zero entry of the RFC's permuted order,
+ * at least 4.  The HLIT + 257 + 1 code lengths are sent with the symbols 0 .. 15, 17 and 18 (never 16): a maximal run of z
+ * zero lengths is cut greedily into pieces t = min(z, 138) while z >= 3 — symbol 18 for t >= 11, else 17 — and the 0 .. 2 zeros
+ * left are sent as they are.  A Huffman segment therefore carries at most (17 + 57 + 287 * 7 + 15 + 7) / 8 + 5 = 268 bytes
+ * beyond its coded literals and matches.
+ *
+ * The zlib stream is 78 01, the segments, Adler-32 big-endian.  Adler-32 is formed from per-chunk partials a = sum of b[i],
+ * b = sum of (n - i) * b[i] (mod 65521), combined in chunk order: B += n * A + b, then A += a, from A = 1, B = 0.
+ *
+ * unflow_deflate: n streams in one launch pair, one workgroup per (stream, chunk).  DEVICE table desc[n][UNFLOW_DEFLATE_FIELDS]
+ * of int64 = {src, bytes, dst, cap, scratch, meta, 0, 0}: the stream in[src .. src + bytes) becomes the zlib stream at
+ * out[dst ...], which may take cap >= unflow_deflate_stream_bound(bytes, chunk_bytes) bytes; its size is written to sizes[k]
+ * (DEVICE, n int64).  Working memory per stream: chunks * unflow_deflate_slot_bytes(chunk_bytes) bytes of `scratch` from the
+ * offset `scratch` (a multiple of 16; the buffer itself 16-byte aligned) and `chunks` entries of `meta`
+ * (int[meta_chunks][UNFLOW_DEFLATE_META] = {segment bytes, Adler a, Adler b, coding}) from entry `meta`.  max_chunks >= every
+ * stream's chunk count (chunks beyond it are not coded).  An entry that leaves in, out, scratch or meta, or whose cap is below
+ * the bound, is skipped and nothing of it is written; the caller validates the table, and that the ranges do not overlap, on
+ * the host (core/png_device.py).  Nothing outside the entries' ranges is written; inside [dst, dst + cap) only the stream's
+ * own bytes are.  `in` may start at any alignment.  Integer arithmetic, LDS atomic OR / ADD only: bit-reproducible.
+ * chunk_bytes outside 1 .. 65535: UNFLOW_ERR_UNSUPPORTED. */
+#define UNFLOW_DEFLATE_FIELDS 8
+#define UNFLOW_DEFLATE_META 4
+#define UNFLOW_DEFLATE_CHUNK_MAX 65535
+#define UNFLOW_DEFLATE_CHUNK_DEFAULT 16384 /* DESIGN 7.12 has the A/B */
+int unflow_deflate(const unsigned char* in, long in_bytes, const long* desc, int n, int max_chunks, int chunk_bytes,
+                   unsigned char* scratch, long scratch_bytes, int* meta, long meta_chunks, unsigned char* out, long out_bytes,
+                   long* sizes, unflow_stream_t stream);
+/* Host only.  The most bytes a chunk's segment takes (stored: chunk_bytes + 5), the most a stream's zlib stream takes
+ * (2 + bytes + 5 * chunks + 4), and the size of a chunk's scratch slot; -1 for arguments out of range. */
+long unflow_deflate_segment_bound(int chunk_bytes);
+long unflow_deflate_stream_bound(long bytes, int chunk_bytes);
+long unflow_deflate_slot_bytes(int chunk_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,10 @@ def lib():
         _lib.unflow_sintel_gt.restype = ctypes.c_int
         _lib.unflow_supervised_geo_augment.restype = ctypes.c_int
         _lib.unflow_png_filter.restype = ctypes.c_int
+        _lib.unflow_deflate.restype = ctypes.c_int
+        _lib.unflow_stream_create.restype = ctypes.c_int
+        for name in ('unflow_deflate_segment_bound', 'unflow_deflate_stream_bound', 'unflow_deflate_slot_bytes'):
+            getattr(_lib, name).restype = ctypes.c_long
         _apply_env_options(_lib)
     return _lib
 
@@ -151,6 +155,34 @@ class PngSurface(ctypes.Structure):
     _fields_ = [('base', ctypes.c_void_p), ('image_stride', ctypes.c_long), ('row_stride', ctypes.c_long),
                 ('images', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int), ('channels', ctypes.c_int),
                 ('kind', ctypes.c_int)]
+
+
+DEFLATE_FIELDS = 8       # int64 per stream of unflow_deflate's table: src, bytes, dst, cap, scratch, meta, 0, 0
+DEFLATE_META = 4         # int per chunk: segment bytes, Adler a, Adler b, coding
+DEFLATE_CHUNK_MAX = 65535
+DEFLATE_CHUNK_DEFAULT = 16384
+
+
+def _deflate_size(fn, *args):
+    v = int(fn(*args))
+    if v < 0:
+        raise ValueError("deflate: chunk_bytes is an integer in [1, %d] and a stream has at least one byte" % DEFLATE_CHUNK_MAX)
+    return v
+
+
+def deflate_segment_bound(chunk_bytes=DEFLATE_CHUNK_DEFAULT):
+    """unflow_deflate_segment_bound: the most bytes one chunk's segment takes (host only)."""
+    return _deflate_size(lib().unflow_deflate_segment_bound, ctypes.c_int(int(chunk_bytes)))
+
+
+def deflate_stream_bound(nbytes, chunk_bytes=DEFLATE_CHUNK_DEFAULT):
+    """unflow_deflate_stream_bound: the most bytes the zlib stream of `nbytes` bytes takes (host only)."""
+    return _deflate_size(lib().unflow_deflate_stream_bound, cl(nbytes), ctypes.c_int(int(chunk_bytes)))
+
+
+def deflate_slot_bytes(chunk_bytes=DEFLATE_CHUNK_DEFAULT):
+    """unflow_deflate_slot_bytes: scratch bytes per chunk (host only)."""
+    return _deflate_size(lib().unflow_deflate_slot_bytes, ctypes.c_int(int(chunk_bytes)))
 
 
 class CarryBuf(ctypes.Structure):

@@ -178,11 +178,12 @@ class _Slot:
         self.event = None
         self.pending = None
         self.scan = self.scan_table = self.spans = None      # files through the device encode path (FlowEstimator._encoder)
+        self.scan_kind = 'png'                               # what slot.scan holds per span: scanlines, or 'png_z' zlib streams
 
     def scan_buffers(self, enc):
         """The pinned scanline buffer and table of this slot, sized like the estimator's device ones."""
         if self.scan is None:
-            self.scan = torch.zeros(enc.scan.numel(), dtype=torch.uint8, pin_memory=True)
+            self.scan = torch.zeros(enc.host_bytes, dtype=torch.uint8, pin_memory=True)
             self.scan_table = torch.zeros(tuple(enc.table.shape), dtype=torch.int64, pin_memory=True)
         return self.scan, self.scan_table
 
@@ -201,7 +202,9 @@ class _Slot:
 class _Encoder:
     """The device half of FlowEstimator's file output (csrc/png_encode.hip): the surfaces unflow_png_filter reads — the
     estimator's own output buffers, no staging copy — a device table and the device scanline buffer, sized for every file one
-    replay can ask for."""
+    replay can ask for.  deflater: the buffers of unflow_deflate (png_device.DeviceDeflater), allocated with the first
+    deflate='device' call; host_bytes: what a slot's pinned buffer holds at the most — the scanlines, or their zlib streams
+    at the stream bound."""
 
     def __init__(self, est):
         from .png_device import PngSurface
@@ -215,6 +218,8 @@ class _Encoder:
         self.surfaces = [PngSurface(t, images, Hm, Wm, ch, kind) for _, t, images, ch, kind in named]
         n_files = sum(s.images for s in self.surfaces)
         n_bytes = sum(s.images * Hm * (1 + Wm * s.bpp) for s in self.surfaces)
+        self.n_files, self.deflater = n_files, None
+        self.host_bytes = n_bytes + 5 * (n_bytes // _lib.DEFLATE_CHUNK_DEFAULT + n_files) + 6 * n_files
         with torch.cuda.device(est.dev):
             self.table = torch.zeros(n_files, _lib.PNG_FILTER_FIELDS, dtype=torch.int64, device=est.dev)
             self.scan = torch.zeros(n_bytes, dtype=torch.uint8, device=est.dev)
@@ -379,12 +384,17 @@ class FlowEstimator:
             self.graph = g
         self.graph.replay()
 
-    def _filter(self, slot, entries):
+    def _filter(self, slot, entries, deflate=False):
         """The files of one replay through the device encode path: entries [(surface name, image, h, w), ...] -> one
         unflow_png_filter launch on the current stream, right behind the replay and OUTSIDE the captured graph (the set of
         wanted files varies per call), and the copy of the scanlines into the slot's pinned buffer.  slot.spans: per entry
-        (offset, bytes, h, w, depth, colour type) in that buffer."""
-        from .png_device import filter_scanlines, plan_scanlines
+        (offset, bytes, h, w, depth, colour type) in that buffer.
+        deflate: the unflow_deflate launches follow the filter launch on the same stream and the pinned buffer
+        receives the zlib streams instead (slot.scan_kind 'png_z'; a span's bytes are the stream's).  Their sizes are known only
+        behind the kernels, so this waits for the replay once — the writer pool, not this thread, sets an export's pace — and
+        then queues one copy per stream of exactly its bytes."""
+        from .png_device import DeviceDeflater, filter_scanlines, plan_scanlines
+        slot.scan_kind = 'png_z' if deflate else 'png'
         if not entries:
             slot.spans = []
             return
@@ -397,8 +407,17 @@ class FlowEstimator:
         n = len(entries)
         table.numpy()[:n] = rows
         enc.table[:n].copy_(table[:n], non_blocking=True)
-        filter_scanlines(enc.surfaces, enc.table, n, max_h, max_row, enc.scan, torch.cuda.current_stream(self.dev))
-        scan[:total].copy_(enc.scan[:total], non_blocking=True)
+        cur = torch.cuda.current_stream(self.dev)
+        filter_scanlines(enc.surfaces, enc.table, n, max_h, max_row, enc.scan, cur)
+        if not deflate:
+            scan[:total].copy_(enc.scan[:total], non_blocking=True)
+            return
+        if enc.deflater is None:
+            enc.deflater = DeviceDeflater(self.dev, enc.n_files, enc.scan.numel())
+        plan = enc.deflater.launch(enc.scan, spans, cur)
+        cur.synchronize()
+        places = enc.deflater.fetch(plan, scan, cur)
+        slot.spans = [(o, nb) + sp[2:] for (o, nb), sp in zip(places, spans)]
 
     # ------------------------------------------------------------------------------------------ staging
     def _slot(self, k):
@@ -516,7 +535,7 @@ class FlowEstimator:
                 nv = len(VISUAL_IMAGES) if nmaps else len(FlowVisual._fields)
                 slot.vis[:nv].copy_(self.vis[:nv], non_blocking=True)
             if files is not None:
-                self._filter(slot, files(shapes, nmaps))
+                self._filter(slot, files(shapes, nmaps), getattr(files, 'deflate', False))
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -608,19 +627,26 @@ class FlowEstimator:
             out += [FlowVisual(*(v[k, i, :h, :w].copy() for k in range(3))) for i, (h, w) in enumerate(shapes)]
         return out
 
-    def pictures(self, batch_iter, num=None, scanlines=False):
+    def pictures(self, batch_iter, num=None, scanlines=False, deflate='host'):
         """The pictures of what KITTIInput.input_{train,test}_{2012,2015}() yields, one dict per example in iteration order:
         VISUAL_IMAGES' names -> uint8 [h, w, 3]; 'error' and 'gt' only when the input carries ground truth (two maps:
         flow_error_image(flow, flow_occ, mask_occ, mask_noc) and flow_to_color(flow_occ, mask_occ); one map: mask_noc = ones).
         scanlines: every dict also has 'scanlines': image name -> (h, w, depth, colour type, bytes), the picture's finished PNG
-        scanlines from the device encode path (unflow_png_filter), what png_device.DeviceFileWriter.submit takes."""
+        scanlines from the device encode path (unflow_png_filter), what png_device.DeviceFileWriter.submit takes.
+        deflate='device' (with scanlines): the bytes are the scanlines' finished zlib stream instead (unflow_deflate), and
+        'scanlines_kind' is 'png_z', the kind to submit them as ('png' otherwise)."""
+        from .png_device import check_deflate_mode
         self._pair_mode('pictures')
+        on_device = check_deflate_mode(deflate)
+        if on_device and not scanlines:
+            raise ValueError("pictures: deflate='device' codes the scanlines; it needs scanlines=True")
         if not self.visual:
             raise RuntimeError("pictures: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
         B, files = self.B, None
         if scanlines:
             def files(shapes, nmaps):
                 return [('vis', k * B + i, h, w) for i, (h, w) in enumerate(shapes) for k in range(len(VISUAL_IMAGES) if nmaps else 3)]
+            files.deflate = on_device
         for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, ('vis',), lambda exs: (len(exs[0]) - 3) // 2, files):
             v = slot.vis.numpy()
             spans = iter(slot.spans or ())
@@ -632,6 +658,7 @@ class FlowEstimator:
                         off, nb, _, _, depth, ctype = next(spans)
                         sc[name] = (h, w, depth, ctype, buf[off:off + nb].tobytes())
                     ex['scanlines'] = sc
+                    ex['scanlines_kind'] = slot.scan_kind
                 yield ex
 
     def evaluate(self, batch_iter, num=None):
@@ -743,7 +770,7 @@ class FlowEstimator:
         yield from self._pipeline_staged(it, want, nmaps_of, files)
 
     def export(self, batch_iter, out_dir, fmt='png', num=None, backward=False, occlusion=False, visual=False, workers=0,
-               level=6):
+               level=6, deflate='host'):
         """The benchmark files of eval_gui.py --output_benchmark (:247-263): for the k-th example in iteration order,
         out_dir/%06d_10.png (KITTI 16-bit RGB, --output_png) or out_dir/%06d_10.flo.  Input: what
         KITTIInput.input_{train,test}_{2012,2015}() yields.  Returns the written paths (per example: _10, _01, _10_occ, then
@@ -759,9 +786,14 @@ class FlowEstimator:
         row).  workers >= 1: the device encode path — unflow_png_filter chooses and applies a filter per row right
         behind each replay, the scanlines come back instead of the raw outputs, and a pool of `workers` threads
         (png_device.DeviceFileWriter) deflates at `level` and writes; .flo files go through the same pool.  The same paths in
-        the same order, files that decode to the same pixels (.flo: the same bytes), all written when the call returns."""
+        the same order, files that decode to the same pixels (.flo: the same bytes), all written when the call returns.
+        deflate='device' (needs workers >= 1): the scanlines are deflated on the device as well (unflow_deflate,
+        right behind the filter launch, outside the captured graph), only the zlib streams come back and the pool's threads form
+        the chunk CRCs and write; `level` does not apply.  .flo files are not compressed and go the same way as before."""
         from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
+        from .png_device import check_deflate_mode
         self._pair_mode('export')
+        on_device = check_deflate_mode(deflate, workers)
         if fmt not in ('png', 'flo'):
             raise ValueError("export: fmt must be 'png' or 'flo'")
         if (backward or occlusion) and not self.bidirectional:
@@ -781,7 +813,8 @@ class FlowEstimator:
         # the ground truth is staged only for the pictures that show it
         nmaps_of = (lambda exs: (len(exs[0]) - 3) // 2) if visual else (lambda exs: 0)
         if workers:
-            return self._export_pool(batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level)
+            return self._export_pool(batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level,
+                                     on_device)
         for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, nmaps_of):
             for i, (h, w) in enumerate(shapes):
                 flows = [('10', slot.u16, slot.flow)] + ([('01', slot.u16_bw, slot.flow_bw)] if backward else [])
@@ -805,7 +838,7 @@ class FlowEstimator:
                 n += 1
         return paths
 
-    def _export_pool(self, batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level):
+    def _export_pool(self, batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level, deflate=False):
         """export through the device encode path: the file list of export's loop, each PNG as an entry of the replay's
         unflow_png_filter launch and a job of the writer pool."""
         from .png_device import DeviceFileWriter, flo_file_bytes
@@ -822,6 +855,7 @@ class FlowEstimator:
                 if visual:
                     ents += [('vis', k * B + i, h, w) for k, _ in visual_files(0, nmaps > 0)]
             return ents
+        files.deflate = deflate
         want = tuple(flow for _, _, flow in tags) if fmt == 'flo' else ()
         n = 0
         with DeviceFileWriter(workers, level) as pool:
@@ -830,7 +864,7 @@ class FlowEstimator:
 
                 def png(name):
                     off, nb, h, w, depth, ctype = next(spans)
-                    pool.submit(os.path.join(out_dir, name), 'png', (h, w, depth, ctype, scan[off:off + nb].tobytes()))
+                    pool.submit(os.path.join(out_dir, name), slot.scan_kind, (h, w, depth, ctype, scan[off:off + nb].tobytes()))
                 for i, (h, w) in enumerate(shapes):
                     for tag, _, flow in tags:
                         if fmt == 'png':
@@ -881,7 +915,8 @@ class FlowEstimator:
 
     def _submit_sequence(self, frames, want=('flow',), encode=False):
         """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns (slot, valid
-        pair slots).  encode: the valid pairs' flow PNGs go through the device encode path (_filter) into slot.scan."""
+        pair slots).  encode: the valid pairs' flow PNGs go through the device encode path (_filter) into slot.scan; 'device':
+        deflated there too."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
@@ -913,7 +948,7 @@ class FlowEstimator:
             if 'u16' in want:
                 slot.u16.copy_(self.out_u16, non_blocking=True)
             if encode:
-                self._filter(slot, [('u16', i, h, w) for i in valid])
+                self._filter(slot, [('u16', i, h, w) for i in valid], encode == 'device')
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -959,12 +994,15 @@ class FlowEstimator:
             out += [fl[i, :h, :w].copy() for i in valid]
         return out
 
-    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6):
+    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host'):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
-        writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one)."""
+        writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
+        export ('device': unflow_deflate behind the filter launch; needs workers >= 1)."""
         from .input import write_flo, write_kitti_flow_png
+        from .png_device import check_deflate_mode
         self._sequence_mode('export_sequence')
+        on_device = check_deflate_mode(deflate, workers)
         if fmt not in ('png', 'flo'):
             raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
         os.makedirs(out_dir, exist_ok=True)
@@ -972,13 +1010,14 @@ class FlowEstimator:
             from .png_device import DeviceFileWriter, flo_file_bytes
             n = 0
             with DeviceFileWriter(workers, level) as pool:
-                for slot, valid in self._pipeline_sequence(frames, ('flow',) if fmt == 'flo' else (), encode=fmt == 'png'):
+                encode = ('device' if on_device else 'host') if fmt == 'png' else False
+                for slot, valid in self._pipeline_sequence(frames, ('flow',) if fmt == 'flo' else (), encode=encode):
                     h, w, _ = self._clip
                     for j, i in enumerate(valid):
                         path = os.path.join(out_dir, '%06d_10.%s' % (n, fmt))
                         if fmt == 'png':
                             off, nb, _, _, depth, ctype = slot.spans[j]
-                            pool.submit(path, 'png', (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
+                            pool.submit(path, slot.scan_kind, (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
                         else:
                             pool.submit(path, 'flo', flo_file_bytes(slot.flow.numpy()[i, :h, :w]))
                         n += 1

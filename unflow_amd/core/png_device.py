@@ -22,7 +22,9 @@ straight into the pinned staging slot and csrc/flo_decode.hip cuts the window an
 
 The output side mirrors it (the end of this file): unflow_png_filter (csrc/png_encode.hip) chooses and applies the
 PNG row filters on the device, DeviceFileWriter deflates and writes on a thread pool; encode_png_device is decode_png_device's
-counterpart.
+counterpart.  With deflate='device'  the entropy coder runs on the device too: unflow_deflate (csrc/deflate.hip)
+turns the scanlines into finished zlib streams (deflate_device, DeviceDeflater), only compressed bytes come back, and a writer
+thread forms the chunk CRCs and writes (kind 'png_z').
 
 There is no host fallback: without the library's kernels these raise."""
 import collections
@@ -504,6 +506,28 @@ class _Job:
         self.times = {}
 
 
+_loader_streams = {}
+_loader_streams_lock = threading.Lock()
+
+
+def loader_stream(dev):
+    """The side stream of the loaders on `dev`: ONE stream per device and process, created by the library
+    (unflow_stream_create) and never destroyed.  torch.cuda.Stream() returns the streams of a pool of 32 round-robin, so a
+    stream taken there can be the very stream on which the consumer's thread captures a hipGraph (torch.cuda.graph's default
+    capture stream, the engine's capture stream) — the producer thread's uploads and kernels would then be enqueued INSIDE the
+    capture, which ends with "capturing stream has unjoined work".  Whether that happens depends only on how many streams the
+    process created before, so it must not be left to chance.  Loaders that run at the same time share the stream: their work
+    is ordered by events as before, only serialised with each other."""
+    with _loader_streams_lock:
+        s = _loader_streams.get(dev.index)
+        if s is None:
+            handle = ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                check(_lib.lib().unflow_stream_create(ctypes.byref(handle)), "stream_create")
+            s = _loader_streams[dev.index] = torch.cuda.ExternalStream(handle.value, device=dev)
+        return s
+
+
 class _Pipeline:
     """What the producer thread owns: the worker pool, the side stream and the launches.  It does not refer to the iterator, so
     dropping the iterator stops it (_DeviceBatches.__del__).
@@ -516,7 +540,7 @@ class _Pipeline:
     def __init__(self, dev, dims, mean, stddev, workers, timing, window=False):
         self.dev, self.dims, self.mean, self.stddev, self.timing, self.window = dev, dims, mean, stddev, timing, window
         self.pool = ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS)), thread_name_prefix="png-inflate")
-        self.side = torch.cuda.Stream(dev)
+        self.side = loader_stream(dev)
         self.jobs = queue.Queue()
         self.closed = False
         self.thread = threading.Thread(target=self._run, name="png-producer", daemon=True)
@@ -909,15 +933,189 @@ def scanlines_device(images):
     return out, spans
 
 
-def encode_png_device(images, level=6):
+def assemble_png_z(h, w, depth, ctype, zstream):
+    """A finished zlib stream of an image's scanlines (deflate_device's) -> PNG file bytes: IHDR, one IDAT, IEND.  Host only:
+    the two chunk CRCs are all the work left."""
+    _check_variant(depth, ctype, 0)
+    return b''.join((PNG_SIGNATURE, _chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, depth, ctype, 0, 0, 0)),
+                     _chunk(b'IDAT', bytes(zstream)), _chunk(b'IEND', b'')))
+
+
+DEFLATE_MODES = ('host', 'device')
+
+
+def check_deflate_mode(deflate, workers=None):
+    """'host' or 'device'; the device coder feeds the writer pool, so it needs workers >= 1 (where `workers` is given)."""
+    if deflate not in DEFLATE_MODES:
+        raise ValueError("deflate must be one of %s, got %r" % (DEFLATE_MODES, deflate))
+    if deflate == 'device' and workers is not None and int(workers) < 1:
+        raise ValueError("deflate='device' writes through the pool of the device encode path: it needs workers >= 1")
+    return deflate == 'device'
+
+
+def check_chunk_bytes(chunk_bytes):
+    """None -> the default; otherwise an integer in [1, 65535] (one stored block must cover a chunk)."""
+    if chunk_bytes is None:
+        return _lib.DEFLATE_CHUNK_DEFAULT
+    if isinstance(chunk_bytes, bool) or int(chunk_bytes) != chunk_bytes or not 1 <= int(chunk_bytes) <= _lib.DEFLATE_CHUNK_MAX:
+        raise ValueError("chunk_bytes is an integer in [1, %d], got %r" % (_lib.DEFLATE_CHUNK_MAX, chunk_bytes))
+    return int(chunk_bytes)
+
+
+def deflate_slot_bytes(chunk):
+    """Scratch bytes per chunk (unflow_deflate_slot_bytes): the segment bound rounded to 16, and 16."""
+    return ((chunk + 5 + 15) & ~15) + 16
+
+
+class DeflatePlan:
+    """Host packing of unflow_deflate's table for streams [(offset, bytes, ...), ...] of one input buffer: rows int64 [n][8],
+    places [(dst, cap)], and the sizes of the buffers the launch needs (out_bytes, scratch_bytes, meta_chunks, max_chunks)."""
+
+    def __init__(self, spans, chunk_bytes=None):
+        self.chunk = check_chunk_bytes(chunk_bytes)
+        self.n = len(spans)
+        self.rows = np.zeros((self.n, _lib.DEFLATE_FIELDS), dtype=np.int64)
+        self.places, dst, scratch, meta, self.max_chunks = [], 0, 0, 0, 1
+        slot = deflate_slot_bytes(self.chunk)
+        for k, sp in enumerate(spans):
+            off, nb = int(sp[0]), int(sp[1])
+            chunks = max(1, -(-nb // self.chunk))
+            cap = 2 + nb + 5 * chunks + 4
+            self.rows[k, :6] = (off, nb, dst, cap, scratch, meta)
+            self.places.append((dst, cap))
+            dst, scratch, meta = dst + (-(-cap // 16)) * 16, scratch + chunks * slot, meta + chunks
+            self.max_chunks = max(self.max_chunks, chunks)
+        self.out_bytes, self.scratch_bytes, self.meta_chunks = dst, scratch, meta
+
+
+def check_deflate_table(rows, chunk, in_bytes, out_bytes, scratch_bytes, meta_chunks):
+    """Everything unflow_deflate would skip raises ValueError here, before any launch: a stream, an output range, a scratch range
+    or a meta range that leaves its buffer, a cap below the stream bound, output ranges that overlap."""
+    slot, taken = deflate_slot_bytes(chunk), []
+    for k, (src, nb, dst, cap, scratch, meta) in enumerate(np.asarray(rows)[:, :6].tolist()):
+        if nb < 1 or src < 0 or src + nb > in_bytes:
+            raise ValueError("deflate entry %d: bytes [%d, %d) leave the input buffer of %d bytes" % (k, src, src + nb, in_bytes))
+        chunks = -(-nb // chunk)
+        if cap < 2 + nb + 5 * chunks + 4:
+            raise ValueError("deflate entry %d: %d bytes of output for a stream whose bound is %d" % (k, cap, 2 + nb + 5 * chunks + 4))
+        if dst < 0 or dst + cap > out_bytes:
+            raise ValueError("deflate entry %d: output [%d, %d) leaves the buffer of %d bytes" % (k, dst, dst + cap, out_bytes))
+        if scratch < 0 or scratch % 16 or scratch + chunks * slot > scratch_bytes:
+            raise ValueError("deflate entry %d: scratch [%d, %d) leaves the buffer of %d bytes (or is not a multiple of 16)"
+                             % (k, scratch, scratch + chunks * slot, scratch_bytes))
+        if meta < 0 or meta + chunks > meta_chunks:
+            raise ValueError("deflate entry %d: meta entries [%d, %d) of %d" % (k, meta, meta + chunks, meta_chunks))
+        taken.append((dst, dst + cap))
+    taken.sort()
+    for (_, e0), (s1, _) in zip(taken, taken[1:]):
+        if s1 < e0:
+            raise ValueError("deflate: output ranges overlap at byte %d" % s1)
+
+
+def deflate_launch(in_dev, rows, table_dev, max_chunks, chunk, scratch_dev, meta_dev, out_dev, sizes_dev, stream):
+    """One unflow_deflate call on `stream` for the table `rows` (host; validated here) whose copy is table_dev (device)."""
+    chunk = check_chunk_bytes(chunk)
+    n = len(rows)
+    if n < 1 or table_dev.numel() < n * _lib.DEFLATE_FIELDS or sizes_dev.numel() < n:
+        raise ValueError("deflate: %d entries for a table of %d and %d sizes" % (n, table_dev.numel() // _lib.DEFLATE_FIELDS,
+                                                                              sizes_dev.numel()))
+    check_deflate_table(rows, chunk, in_dev.numel(), out_dev.numel(), scratch_dev.numel(), meta_dev.numel() // _lib.DEFLATE_META)
+    check(_lib.lib().unflow_deflate(ptr(in_dev), _lib.cl(in_dev.numel()), ptr(table_dev), n, int(max_chunks), chunk,
+                                    ptr(scratch_dev), _lib.cl(scratch_dev.numel()), ptr(meta_dev),
+                                    _lib.cl(meta_dev.numel() // _lib.DEFLATE_META), ptr(out_dev), _lib.cl(out_dev.numel()),
+                                    ptr(sizes_dev), _stream_ptr(stream)), "deflate")
+
+
+class DeviceDeflater:
+    """The buffers of unflow_deflate for up to max_streams streams of max_bytes bytes in all, allocated once (the estimator keeps
+    one beside its scanline buffer): the device table, scratch slots, chunk meta, the output and the sizes, and pinned twins of
+    the table and the sizes.  launch() enqueues the table upload, the two kernels and the copy of the sizes; once the caller
+    has synchronised behind it, fetch() enqueues one copy per stream of exactly its compressed bytes."""
+
+    def __init__(self, dev, max_streams, max_bytes, chunk_bytes=None):
+        self.chunk = check_chunk_bytes(chunk_bytes)
+        self.dev, self.max_streams = dev, int(max_streams)
+        chunks = int(max_bytes) // self.chunk + self.max_streams
+        self.host_bytes = int(max_bytes) + 5 * chunks + 6 * self.max_streams                 # the most fetch() packs
+        with torch.cuda.device(dev):
+            self.table = torch.zeros(self.max_streams, _lib.DEFLATE_FIELDS, dtype=torch.int64, device=dev)
+            self.sizes = torch.zeros(self.max_streams, dtype=torch.int64, device=dev)
+            self.scratch = torch.empty(chunks * deflate_slot_bytes(self.chunk), dtype=torch.uint8, device=dev)
+            self.meta = torch.zeros(chunks * _lib.DEFLATE_META, dtype=torch.int32, device=dev)
+            self.out = torch.empty(self.host_bytes + 16 * self.max_streams, dtype=torch.uint8, device=dev)
+        self.table_host = torch.zeros(self.max_streams, _lib.DEFLATE_FIELDS, dtype=torch.int64, pin_memory=True)
+        self.sizes_host = torch.zeros(self.max_streams, dtype=torch.int64, pin_memory=True)
+
+    def launch(self, in_dev, spans, stream):
+        plan = DeflatePlan(spans, self.chunk)
+        if plan.n > self.max_streams:
+            raise ValueError("deflate: %d streams in one launch (this deflater takes %d)" % (plan.n, self.max_streams))
+        self.table_host.numpy()[:plan.n] = plan.rows
+        with torch.cuda.stream(stream):
+            self.table[:plan.n].copy_(self.table_host[:plan.n], non_blocking=True)
+            deflate_launch(in_dev, plan.rows, self.table, plan.max_chunks, self.chunk, self.scratch, self.meta, self.out,
+                           self.sizes, stream)
+            self.sizes_host[:plan.n].copy_(self.sizes[:plan.n], non_blocking=True)
+        return plan
+
+    def fetch(self, plan, host, stream):
+        """Behind a synchronisation on launch(): the streams' bytes -> `host` (a pinned uint8 tensor) back to back; returns
+        [(offset, bytes)] in it.  The copies are enqueued on `stream`."""
+        sizes = self.sizes_host.numpy()[:plan.n].tolist()
+        out, pos = [], 0
+        with torch.cuda.stream(stream):
+            for (dst, cap), size in zip(plan.places, sizes):
+                if not 8 <= size <= cap:
+                    raise RuntimeError("unflow_deflate reported a stream of %d bytes (bound %d)" % (size, cap))
+                host[pos:pos + size].copy_(self.out[dst:dst + size], non_blocking=True)
+                out.append((pos, size))
+                pos += size
+        return out
+
+
+def deflate_device(scan_dev, spans, stream=None, chunk_bytes=None):
+    """Streams [(offset, bytes, ...), ...] of the device byte buffer scan_dev (scanlines_device's pair) -> [zlib stream bytes]:
+    one unflow_deflate launch pair on `stream` (default: the current one); only the compressed bytes are copied back.
+    chunk_bytes: the bytes coded per workgroup (default 16384).  A stream that leaves the buffer or a bad
+    chunk_bytes raises ValueError before anything is launched."""
+    chunk = check_chunk_bytes(chunk_bytes)
+    if not isinstance(scan_dev, torch.Tensor) or not scan_dev.is_cuda or scan_dev.dtype != torch.uint8 or not scan_dev.is_contiguous():
+        raise ValueError("deflate_device takes a contiguous uint8 device tensor")
+    spans = list(spans)
+    if not spans:
+        return []
+    plan = DeflatePlan(spans, chunk)
+    check_deflate_table(plan.rows, chunk, scan_dev.numel(), plan.out_bytes, plan.scratch_bytes, plan.meta_chunks)
+    dev = scan_dev.device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        d = DeviceDeflater(dev, plan.n, sum(int(sp[1]) for sp in spans), chunk)
+        done = d.launch(scan_dev, spans, stream)
+        stream.synchronize()
+        host = torch.empty(d.host_bytes, dtype=torch.uint8).pin_memory()
+        places = d.fetch(done, host, stream)
+        stream.synchronize()
+    buf = host.numpy()
+    return [buf[o:o + n].tobytes() for o, n in places]
+
+
+def encode_png_device(images, level=6, deflate='host', chunk_bytes=None):
     """[device tensor uint8 [h,w] / uint8 [h,w,3] / uint16 or int16 [h,w,3], ...] -> [PNG file bytes, ...]: the counterpart of
     decode_png_device — decode_png(encode_png_device([x])[0]) and decode_png_device(...) return x exactly (int16 as its uint16
     bit pattern).  The row filters are chosen and applied on the device (unflow_png_filter: least sum of absolute differences
-    per row); the host deflates at `level` and assembles IHDR, one IDAT and IEND."""
+    per row); deflate='host': the host deflates at `level` and assembles IHDR, one IDAT and IEND.  deflate='device': the
+    scanlines are coded on the device too (deflate_device; `level` does not apply, chunk_bytes as there) and the host only
+    wraps the stream."""
     level = check_level(level)
+    on_device = check_deflate_mode(deflate)
+    if on_device:
+        check_chunk_bytes(chunk_bytes)
     out, spans = scanlines_device(images)
     if out is None:
         return []
+    if on_device:
+        streams = deflate_device(out, spans, None, chunk_bytes)
+        return [assemble_png_z(h, w, depth, ctype, z) for (_, _, h, w, depth, ctype), z in zip(spans, streams)]
     host = out.cpu().numpy()
     return [assemble_png(h, w, depth, ctype, host[off:off + n], level) for off, n, h, w, depth, ctype in spans]
 
@@ -934,6 +1132,8 @@ class DeviceFileWriter:
     a worker deflates, forms the chunk CRCs and writes it.
 
         kind 'png': payload = (h, w, depth, ctype, scanlines) — host bytes that are already filtered (assemble_png);
+        kind 'png_z': payload = (h, w, depth, ctype, zlib stream) — scanlines the device has deflated already
+                      (deflate_device): the worker only forms the chunk CRCs and writes (assemble_png_z);
         kind 'flo': payload = the file's bytes (flo_file_bytes), written as they are through the same pool.
 
     workers is capped by MAX_WORKERS (never sized from os.cpu_count()).  At most `bound` = 2 * workers files are pending
@@ -944,7 +1144,7 @@ class DeviceFileWriter:
     launch nor a sync nor a copy — so they may run while another thread captures a graph.  `paths` lists the submitted paths in
     order; `written` and `file_bytes` count what the workers finished."""
 
-    KINDS = ('png', 'flo')
+    KINDS = ('png', 'png_z', 'flo')
 
     def __init__(self, workers=8, level=6, compress=zlib.compress):
         self.workers = max(1, min(int(workers), MAX_WORKERS))
@@ -978,6 +1178,8 @@ class DeviceFileWriter:
             if kind == 'png':
                 h, w, depth, ctype, scan = payload
                 data = assemble_png(h, w, depth, ctype, scan, self.level, self.compress)
+            elif kind == 'png_z':
+                data = assemble_png_z(*payload)
             else:
                 data = payload
             with open(path, 'wb') as f:

@@ -328,3 +328,16 @@ UNFLOW_API int unflow_png_to_flow_gt(const unsigned char* decoded, long decoded_
                                                              reinterpret_cast<float2*>(flow), mask);
   return launch_status();
 }
+
+// A stream of the loader's own (core/png_device.py::loader_stream).  torch.cuda.Stream() hands out the streams of a pool of 32
+// round-robin, so a loader's "side" stream can BE the stream on which another thread captures a hipGraph (torch.cuda.graph's
+// default capture stream, the engine's): the producer thread's uploads then land inside the capture.  A stream created here is
+// in no pool.  Non-blocking: no implicit ordering with the null stream.  Never destroyed by the caller (pinned buffers that were
+// read on it may be freed, and recorded on it, later).
+UNFLOW_API int unflow_stream_create(unflow_stream_t* stream) {
+  if (!stream) return UNFLOW_ERR_NULL;
+  hipStream_t s = nullptr;
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return UNFLOW_ERR_LAUNCH;
+  *stream = reinterpret_cast<unflow_stream_t>(s);
+  return UNFLOW_OK;
+}

@@ -13,7 +13,8 @@ The experiment's config.ini (<dirs.log>/ex/NAME/config.ini, else --config) gives
 and %06d_10_occ.png (8-bit, 255 = occluded) with --output_benchmark.  The pictures (colour wheel, error map, overlay) are
 python -m unflow_amd.visualize's; Sintel, FlyingChairs and Middlebury are python -m unflow_amd.evaluate_flo's.
 --workers N (N >= 1) writes the files through the device encode path: PNG row filters on the GPU, N threads that
-deflate at --level L (6) and write; the default and --host_encode: the host's writers, one file after another."""
+deflate at --level L (6) and write; the default and --host_encode: the host's writers, one file after another.
+--device_deflate (with --workers N): the GPU deflates the scanlines too and the threads only write."""
 import argparse
 import os
 import shutil
@@ -56,15 +57,22 @@ def add_encode_flags(ap):
     ap.add_argument('--level', type=int, default=6, metavar='L', help='deflate level of the PNG files, 0 .. 9')
     ap.add_argument('--host_encode', action='store_true',
                     help="write the files one after another with the host's PNG writers (filter 0), whatever --workers says")
+    ap.add_argument('--device_deflate', action='store_true',
+                    help='with --workers N >= 1: deflate the PNG scanlines on the GPU as well (DESIGN 7.12); the N threads only '
+                         'form the chunk CRCs and write, and --level does not apply')
 
 
 def check_encode_flags(ap, a):
-    """Refuses a bad --workers / --level (status 2); a.encode_workers: FlowEstimator.export's workers (0 with --host_encode)."""
+    """Refuses a bad --workers / --level / --device_deflate (status 2); a.encode_workers: FlowEstimator.export's workers (0 with
+    --host_encode), a.deflate: its deflate ('device' with --device_deflate)."""
     if a.workers < 0:
         ap.error("--workers must not be negative (0: the host's writers)")
     if not 0 <= a.level <= 9:
         ap.error("--level must be in 0 .. 9, got %d" % a.level)
     a.encode_workers = 0 if a.host_encode else a.workers
+    if a.device_deflate and a.encode_workers < 1:
+        ap.error("--device_deflate feeds the writer pool: it needs --workers N with N >= 1 (and no --host_encode)")
+    a.deflate = 'device' if a.device_deflate else 'host'
 
 
 def parse_args(argv=None):
@@ -137,7 +145,7 @@ def main(argv=None):
         os.makedirs(out_dir)
         shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
         paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=num, backward=a.output_backward,
-                           occlusion=a.occlusion, workers=a.encode_workers, level=a.level)
+                           occlusion=a.occlusion, workers=a.encode_workers, level=a.level, deflate=a.deflate)
         print("wrote %d files to %s" % (len(paths), out_dir))
     return 0
 

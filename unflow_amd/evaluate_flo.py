@@ -141,7 +141,8 @@ def main(argv=None):
         os.makedirs(out_dir)
         shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
         paths = est.export(batches(), out_dir, fmt='png' if a.output_png else 'flo', num=a.num, backward=a.output_backward,
-                           occlusion=a.occlusion, visual=a.visual, workers=a.encode_workers, level=a.level)
+                           occlusion=a.occlusion, visual=a.visual, workers=a.encode_workers, level=a.level,
+                           deflate=a.deflate)
         if a.sheet:
             paths += write_sheets(out_dir, sum(p.endswith('_img.png') for p in paths), a.has_gt, a.num_vis)
         print("wrote %d files to %s" % (len(paths), out_dir))

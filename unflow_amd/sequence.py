@@ -141,7 +141,8 @@ def main(argv=None):
                                                            a.frames))
     try:
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
-        paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level)
+        paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
+                                    deflate=a.deflate)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))

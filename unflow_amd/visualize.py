@@ -84,7 +84,8 @@ def sheet_name(page):
 def write_pictures(examples, out_dir, sheet=False, num_vis=100, workers=0, level=6):
     """Writes the picture files of every example (dicts of FlowEstimator.pictures) and, with sheet, the contact sheets of the
     first num_vis of them; returns the written paths.  workers >= 1: the per-example pictures go through a writer pool
-    (png_device.DeviceFileWriter) from the examples' 'scanlines' (FlowEstimator.pictures(..., scanlines=True)); the contact sheets
+    (png_device.DeviceFileWriter) from the examples' 'scanlines' (FlowEstimator.pictures(..., scanlines=True); zlib streams where
+    'scanlines_kind' says 'png_z': pictures(..., deflate='device')); the contact sheets
     are composed and written on the host either way."""
     from .core.inference import VISUAL_IMAGES, visual_files
     from .core.input import write_png_rgb8
@@ -106,7 +107,7 @@ def write_pictures(examples, out_dir, sheet=False, num_vis=100, workers=0, level
             for k, name in visual_files(n, 'error' in ex):
                 p = os.path.join(out_dir, name)
                 if pool is not None:
-                    pool.submit(p, 'png', ex['scanlines'][VISUAL_IMAGES[k]])
+                    pool.submit(p, ex.get('scanlines_kind', 'png'), ex['scanlines'][VISUAL_IMAGES[k]])
                 else:
                     write_png_rgb8(p, ex[VISUAL_IMAGES[k]])
                 paths.append(p)
@@ -145,7 +146,7 @@ def main(argv=None):
     shutil.copyfile(cfg_path, os.path.join(out_dir, 'config.ini'))
     print("-- visualising %s (step %s) on kitti %s" % (a.ex, est.global_step, a.variant))
     batches = getattr(kinput, 'input_' + a.variant)(device=None if a.host_decode else est.dev)
-    examples = est.pictures(batches, num=None if a.num < 0 else a.num, scanlines=a.encode_workers > 0)
+    examples = est.pictures(batches, num=None if a.num < 0 else a.num, scanlines=a.encode_workers > 0, deflate=a.deflate)
     paths = write_pictures(examples, out_dir, sheet=a.sheet, num_vis=a.num_vis, workers=a.encode_workers, level=a.level)
     print("wrote %d files to %s" % (len(paths), out_dir))
     return 0
