@@ -626,6 +626,14 @@ typedef struct {
  * every buffer has).  Rows other than row 0 are never written. */
 int unflow_sequence_carry(const unflow_carry_buf* bufs, int n_bufs, const int* src_row, int max_row, unflow_stream_t stream);
 
+/* Bidirectional sequence mode (FlowEstimator(..., sequence='bidirectional')): in each of the n_bufs (<= UNFLOW_CARRY_MAX)
+ * buffers of the HOST array bufs, copy the n consecutive sample rows [src0, src0 + n) to rows [dst0, dst0 + n), in one launch
+ * (bytes < stride: one channel segment; the other channels of the destination rows, and every other row, are left alone).  The
+ * vector width is chosen per buffer as for unflow_sequence_carry.  max_row: the last row every buffer has.  UNFLOW_ERR_SHAPE,
+ * and nothing is launched, when n < 1, a row lies outside [0, max_row] or the two ranges overlap. */
+int unflow_sequence_mirror(const unflow_carry_buf* bufs, int n_bufs, int src0, int dst0, int n, int max_row,
+                           unflow_stream_t stream);
+
 /* flow [B][fh][fw][2] (the last network's flow2, or flow0 at (H, W) with full_res) -> for every sample b with desc h > 0 and
  * every frame pixel (y < h, x < w):
  *   f = resize_tf1(resize_tf1(flow, H, W) * flow_scale, h, w) (full_res: resize_tf1(flow * flow_scale, h, w)),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof]
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
 of the replayed graph of FlowEstimator(..., sequence=True) in its steady state (a carried frame and B new frames: B pairs per
@@ -9,7 +9,12 @@ replay) and of the pair-mode estimator (B pairs per replay) — device events ar
 staging excluded; mean, standard deviation, minimum and maximum over the replays, and the ratio sequence / pair mode of the
 means.  Beside them the device memory of both estimators.  --rocprof: child runs under `rocprofv3 --kernel-trace --stats` give the
 times of the two sequence kernels at B = 8 (with the bytes they must move) and, for FlowNetC at B = 4, the kernels of ten
-replays of either graph, heaviest first — where the time of a replay goes in each mode."""
+replays of either graph, heaviest first — where the time of a replay goes in each mode.
+
+--bidirectional: the same table for FlowEstimator(..., sequence='bidirectional') against the pair-mode bidirectional
+estimator (both directions and the occlusion masks of B pairs per replay either way), the prediction made before the first run
+beside it, and — from a child run under rocprofv3 of ten replays of the FlowNetC graph at B = 4 — the time of
+unflow_sequence_mirror where it runs, behind conv2, with the bytes it must move."""
 import argparse
 import csv
 import glob
@@ -34,7 +39,8 @@ def _frames(n):
     return [np.roll(a, 2 * i, 1) for i in range(n)]
 
 
-def _estimator(spec, B, sequence):
+def _estimator(spec, B, sequence, bidirectional=False):
+    """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions."""
     import torch
     os.environ['UNFLOW_CONV_MATH'] = 'bf16x3'
     from unflow_amd.core.inference import FlowEstimator
@@ -43,14 +49,18 @@ def _estimator(spec, B, sequence):
     gc.collect()                               # an earlier case's estimator is freed now, not inside this measurement
     torch.cuda.synchronize()
     m0 = torch.cuda.memory_allocated(dev)
-    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence)
+    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
     est.engine.init_params(seed=1)
     est._params_changed()
     fr = _frames(3 * B + 1)
-    if sequence:
+    if sequence == 'bidirectional':
+        est.estimate_sequence_bidirectional(fr[:3 * B])
+    elif sequence:
         est.estimate_sequence(fr[:3 * B])      # the last replay: a carried frame and B new ones, every pair slot valid
+    elif bidirectional:
+        est.estimate_bidirectional(fr[:B], fr[1:B + 1])
     else:
         est.estimate(fr[:B], fr[1:B + 1])
     return est, mem
@@ -75,12 +85,12 @@ def _stats(ms, B):
                 min=round(min(ms) / B, 4), max=round(max(ms) / B, 4))
 
 
-def case(spec, B, iters, warmup):
+def case(spec, B, iters, warmup, bidirectional=False):
     import gc
     import torch
     out = dict(spec=spec, B=B)
-    for name, seq in (('pair', False), ('sequence', True)):
-        est, mem = _estimator(spec, B, seq)
+    for name, seq in (('pair', False), ('sequence', 'bidirectional' if bidirectional else True)):
+        est, mem = _estimator(spec, B, seq, bidirectional and not seq)
         out[name] = _stats(time_replays(est, iters, warmup), B)
         out[name]['estimator_MB'] = round(mem / 1e6, 1)
         del est
@@ -102,10 +112,10 @@ def kernels_only(iters):
     torch.cuda.synchronize()
 
 
-def graph_only(sequence, iters):
+def graph_only(sequence, iters, bidirectional=False):
     """Child: `iters` replays of the FlowNetC graph at B = 4 in one mode."""
     import torch
-    est, _ = _estimator('C', 4, sequence)
+    est, _ = _estimator('C', 4, sequence, bidirectional)
     for _ in range(iters):
         est.graph.replay()
     torch.cuda.synchronize()
@@ -131,6 +141,25 @@ def carry_bytes(B=8):
     c3 = (H // 8) * (W // 8) * 256 * (4 + 3 * 2)
     cat2 = (H // 4) * (W // 4) * 128 * (4 + 3 * 2)
     return 2 * (x0 + c3 + cat2)
+
+
+def mirror_bytes(B=4):
+    """Bytes unflow_sequence_mirror reads plus writes for FlowNetC at (H, W), bf16x3: B rows of the conv2 segment of cat2, fp32
+    and three planes."""
+    return 2 * B * (H // 4) * (W // 4) * 128 * (4 + 3 * 2)
+
+
+def mirror_case(iters=10):
+    """The mirror kernel inside the replayed FlowNetC graph at B = 4 (a rocprofv3 child run)."""
+    rows, err = _rocprof(['--graph-only', 'bidir', '--iters', str(iters)])
+    if err:
+        return err
+    for row in rows:
+        if 'sequence_mirror_kernel' in row['Name']:
+            ns, nbytes = float(row['AverageNs']), mirror_bytes(4)
+            return dict(B=4, calls=int(row['Calls']), us=round(ns / 1e3, 2), MB=round(nbytes / 1e6, 2),
+                        TBps=round(nbytes / ns / 1e3, 3), where='inside the replayed graph, behind conv2')
+    return dict(error='no sequence_mirror_kernel in the trace')
 
 
 def input_bytes(B=8):
@@ -172,12 +201,29 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--rocprof', action='store_true', help='also the kernel times of rocprofv3 child runs')
     ap.add_argument('--kernels-only', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('--graph-only', choices=('pair', 'sequence'), help=argparse.SUPPRESS)
+    ap.add_argument('--bidirectional', action='store_true',
+                    help="sequence='bidirectional' against the pair-mode bidirectional estimator (DESIGN 7.13)")
+    ap.add_argument('--graph-only', choices=('pair', 'sequence', 'bidir', 'pair_bidir'), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.kernels_only:
         return kernels_only(a.iters)
     if a.graph_only:
-        return graph_only(a.graph_only == 'sequence', a.iters)
+        seq = {'pair': False, 'sequence': True, 'bidir': 'bidirectional', 'pair_bidir': False}[a.graph_only]
+        return graph_only(seq, a.iters, a.graph_only == 'pair_bidir')
+    if a.bidirectional:
+        # the prediction of the issue that asked for the mode, from DESIGN 7.3 / 7.5's measurements at FlowNetC, B = 4; printed
+        # beside the measurement, never a threshold
+        res = dict(metric='bidirectional_sequence_ms_per_pair_over_pair_mode_bidirectional', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup,
+                   predicted=dict(C_B4=0.9, basis='pair-bidirectional 1.51 x 0.792 = 1.20 ms/pair; one-direction sequence 0.649 '
+                                  'ms/pair + the second direction behind the tower 0.51 x 0.792 = 0.40 ms -> 1.05 ms/pair + the '
+                                  'mirror, assuming the costs add; unmeasured when it was made'), cases=[])
+        for spec in ('C', 'CSS'):
+            for B in (1, 4, 8):
+                res['cases'].append(case(spec, B, a.iters, a.warmup, bidirectional=True))
+        res['mirror_kernel_C'] = mirror_case()
+        print(json.dumps(res))
+        return
     res = dict(metric='sequence_ms_per_pair_over_pair_mode', shape=[H, W], frames='uint8 %dx%d' % FRAME, math='bf16x3',
                iters=a.iters, warmup=a.warmup, predicted=dict(C=0.75, CSS='closer to 1'), cases=[])
     for spec in ('C', 'CSS'):

@@ -186,7 +186,7 @@ def deflate_slot_bytes(chunk_bytes=DEFLATE_CHUNK_DEFAULT):
 
 
 class CarryBuf(ctypes.Structure):
-    """unflow_carry_buf of include/unflow_hip.h (one buffer of unflow_sequence_carry)."""
+    """unflow_carry_buf of include/unflow_hip.h (one buffer of unflow_sequence_carry / unflow_sequence_mirror)."""
     _fields_ = [('base', ctypes.c_void_p), ('pixels', ctypes.c_long), ('bytes', ctypes.c_int), ('stride', ctypes.c_int)]
 
 

@@ -136,11 +136,13 @@ class ActView(dict):
 
 class _Op:
     """One forward launch of a stage: a layer (src slice -> dst slice) or the correlation; n: the samples (rows) it runs on,
-    r0: the first of them (0 everywhere but in the feature tower of a sequence engine, which computes rows [1, B + 1))."""
-    __slots__ = ('kind', 'l', 'src', 'dst', 'n', 'r0')
+    r0: the first of them (0 everywhere but in the feature tower of a sequence engine, which computes rows [1, B + 1)); d0: the
+    first row written (= r0 everywhere but where the bidirectional sequence engine keeps the tower's rows of cat2 behind the
+    backward block)."""
+    __slots__ = ('kind', 'l', 'src', 'dst', 'n', 'r0', 'd0')
 
     def __init__(self, kind, l, src, dst):
-        self.kind, self.l, self.src, self.dst, self.n, self.r0 = kind, l, src, dst, 0, 0
+        self.kind, self.l, self.src, self.dst, self.n, self.r0, self.d0 = kind, l, src, dst, 0, 0, 0
 
 
 def _rows(t, n):
@@ -281,6 +283,34 @@ class _Stage:
         # and the tower buffers of a first-stage FlowNetC have F rows; the tower layers compute rows [1, F) — the new frames of
         # a replay — and row 0 is carried over from the previous replay (unflow_sequence_carry), never computed
         seq = getattr(eng, 'sequence', False)
+        # Bidirectional sequence engine: the same F frame rows in the network input and the tower, and BOTH
+        # directions of every pair behind it — 2B rows from the cost volume on and in every buffer of a FlowNetS, the block of
+        # the B backward pairs (frame i + 1, frame i) at rows [0, B), the block of the B forward pairs at rows [B, 2B).  cat2
+        # holds the tower's F rows at [B, 2B + 1) (row0['cat2'] = B): frame i's conv2 output is then ALREADY the skip
+        # connection of forward pair i (decoder row B + i), the decoder runs on the contiguous rows [0, 2B), the last frame's
+        # row lies behind them, and unflow_sequence_mirror fills rows [0, B) — backward pair i takes frame i + 1's — from rows
+        # [B + 1, 2B + 1)
+        self.seq_bidir = bool(seq) and bool(getattr(eng, 'seq_bidir', False))
+        self.row0 = {}                    # buffer -> the row that holds the tower's row 0 (absent: 0)
+        if self.seq_bidir:
+            self.rows = {name: (nB + 1 if name in enc else 2 * nB) for name in B}
+            self.rows['x0'] = nB + 1
+            if self.is_c:
+                self.rows['cat2'], self.row0['cat2'] = 2 * nB + 1, nB
+            for op in self.ops:
+                name = None if op.kind != 'layer' else op.l.name.split('/')[-1]
+                if op.kind == 'corr':
+                    op.n = self.rows['c3']            # two launches, one per block: forward() issues them
+                elif op.dst[0] in enc and name in ('conv1', 'conv2', 'conv3'):
+                    op.n = nB
+                    op.r0, op.d0 = 1 + self.row0.get(op.src[0], 0), 1 + self.row0.get(op.dst[0], 0)
+                else:
+                    # (conv_redir: 2B destination rows from the F rows of c3, two launches of B rows: forward() issues them)
+                    op.n = 2 * nB
+            # forward only: no backward plan (its row bands assume that a tensor's later consumers run on no more rows)
+            self.bwd, self.bwd_names, self.bwd_zero_rows, self.bwd_post_act = [], [], {}, {}
+            self.split_at, self.part_bounds = 0, [0, 0]
+            return
         if seq:
             nN = nB + 1
         self.rows = {name: (nN if (not one_dir or name in enc) else nB) for name in B}
@@ -290,6 +320,7 @@ class _Stage:
             op.n = self.rows['c3'] if op.kind == 'corr' else min(self.rows[op.src[0]], self.rows[op.dst[0]])
             if seq and op.kind == 'layer' and op.dst[0] in enc and op.l.name.split('/')[-1] in ('conv1', 'conv2', 'conv3'):
                 op.n, op.r0 = nB, 1
+            op.d0 = op.r0
         self._plan_backward()
 
     # -------------------------------------------------------------- backward plan
@@ -419,7 +450,12 @@ class _Stage:
             x0s = self.act['x0s']
             pf = prev_flow2
             ph, pw = (0, 0) if pf is None else (pf.shape[1], pf.shape[2])
-            if e.one_dir:         # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B); sequence: rows [1, B + 1)
+            if self.seq_bidir:    # both directions of pair i = (frame row i, frame row i + 1): the backward block, then the forward
+                pb, pfw = (None, None) if pf is None else (pf[:B], pf[B:])
+                for first, second, flow, out in ((e.x0[1:], e.x0[:B], pb, x0s[:B]), (e.x0[:B], e.x0[1:], pfw, x0s[B:])):
+                    check(_lib.lib().unflow_stack_input_pair(ptr(first), ptr(second), ptr(flow), ptr(out), x0s.stride(2), B,
+                                                             e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
+            elif e.one_dir:       # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B); sequence: rows [1, B + 1)
                 r1 = 1 if e.sequence else B
                 check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[:B]), ptr(e.x0[r1:]), ptr(pf), ptr(x0s), x0s.stride(2), B,
                                                          e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
@@ -436,7 +472,13 @@ class _Stage:
                 C = op.src[2] - op.src[1]
                 h8, w8 = e.H // 8, e.W // 8
                 pl = self._corr_planes(c3, refresh=True)                      # bf16 x 3 planes: the matrix-core path
-                if e.one_dir:         # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
+                if self.seq_bidir:    # forward block (rows [B, 2B) of the cost volume): c3[0:B] against c3[1:F]; backward: swapped
+                    for a, b, o in ((1, 0, 0), (0, 1, B)):
+                        p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, a:a + B]), _lib.planes_of(pl[:, b:b + B]))
+                        check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[a:a + B]), ptr(c3.t[b:b + B]), c3.t.stride(2), p0, p1,
+                                                                        0, ptr(out.t[o:o + B]), out.t.stride(2), B, C, h8, w8, 1, 20,
+                                                                        20, 1, 2, e.stream()), "correlation")
+                elif e.one_dir:       # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
                     r1 = 1 if e.sequence else B           # sequence: the second frame of pair i is row i + 1
                     p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, r1:]))
                     check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[:B]), ptr(c3.t[r1:]), c3.t.stride(2), p0, p1, 0,
@@ -451,15 +493,45 @@ class _Stage:
                     L.planes_from_f32(out.t, out.pl)
                 continue
             l = op.l
-            x, y = _row_range(self.pt(op.src), op.r0, op.n), _row_range(self.pt(op.dst), op.r0, op.n)
-            if l.cout_p != l.cout:
-                y = L.PT(y.t.as_strided(y.t.shape[:3] + (l.cout_p,), y.t.stride(), y.t.storage_offset()),
-                         None if y.pl is None else y.pl)
-            po = op.dst[0] in self.planes_only
-            if l.kind == 'conv':
-                L.conv_fwd(x, l.w, l.wpl_t, l.b, y, l.stride, l.act, planes_only=po)
+            name = l.name.split('/')[-1]
+            if self.seq_bidir and name == 'conv_redir':
+                # the first frame's features of either block: backward rows [0, B) from c3[1:F], forward rows [B, 2B) from c3[0:B]
+                runs = [(1, 0, B), (0, B, B)]
             else:
-                L.deconv_fwd(x, l.w, l.wpl_d, l.b, y, l.act, planes_only=po)
+                runs = [(op.r0, op.d0, op.n)]
+            for r0, d0, n in runs:
+                x, y = _row_range(self.pt(op.src), r0, n), _row_range(self.pt(op.dst), d0, n)
+                if l.cout_p != l.cout:
+                    y = L.PT(y.t.as_strided(y.t.shape[:3] + (l.cout_p,), y.t.stride(), y.t.storage_offset()),
+                             None if y.pl is None else y.pl)
+                po = op.dst[0] in self.planes_only
+                if l.kind == 'conv':
+                    L.conv_fwd(x, l.w, l.wpl_t, l.b, y, l.stride, l.act, planes_only=po)
+                else:
+                    L.deconv_fwd(x, l.w, l.wpl_d, l.b, y, l.act, planes_only=po)
+            if self.seq_bidir and name == 'conv2' and self.is_c:
+                self.sequence_mirror()
+
+    def mirror_list(self):
+        """What unflow_sequence_mirror copies in a bidirectional sequence engine: the conv2 segment of cat2, fp32 and every
+        operand plane (descriptors relative to cat2's row 0)."""
+        lo, n = self.bufs['cat2'][1]['conv2']
+        n = pad4(n)
+        t, pl = self.A['cat2'].t, self.A['cat2'].pl
+        px = t.shape[1] * t.shape[2]
+        bufs = [_lib.CarryBuf(t[0, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4)]
+        for p in ([] if pl is None else range(pl.shape[0])):
+            bufs.append(_lib.CarryBuf(pl[p, 0, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
+        return bufs
+
+    def sequence_mirror(self):
+        """conv2's output of frames 1 .. B (cat2 rows [B + 1, 2B + 1)) -> the backward block's rows [0, B) of cat2: backward
+        pair i's decoder concatenates with the features of ITS first frame, frame i + 1."""
+        B = self.eng.B
+        bufs = self.mirror_list()
+        arr = (_lib.CarryBuf * len(bufs))(*bufs)
+        check(_lib.lib().unflow_sequence_mirror(arr, len(bufs), self.row0['cat2'] + 1, 0, B, self.rows['cat2'] - 1,
+                                                self.eng.stream()), "sequence_mirror")
 
     # -------------------------------------------------------------- backward
     def _corr_planes(self, c3, refresh=False):
@@ -626,7 +698,10 @@ class FlowNetEngine:
         sequence (with inference only, one direction): flow along a clip, every frame encoded once.  The network input and the
         feature tower of a first-stage FlowNetC hold F = B + 1 frame rows, pair i is (row i, row i + 1): the tower runs on rows
         [1, F) — B rows where the pair engine runs 2B — and row 0 is the previous replay's last frame, copied there by
-        sequence_carry().  set_frames() / sequence_input() fill rows [1, F)."""
+        sequence_carry().  set_frames() / sequence_input() fill rows [1, F).
+        sequence='bidirectional': the same F frame rows and tower, and both directions of every pair behind them (2B rows from
+        the cost volume on): sequence, bidirectional and seq_bidir are all True, final_flows() / flows() give
+        (fw, bw) with B rows each, in pair order."""
         assert height % 64 == 0 and width % 64 == 0, "FlowNet needs H, W divisible by 64"
         if bidirectional and supervised:
             raise ValueError("FlowNetEngine: bidirectional is for the inference engine; the supervised engine is one-direction")
@@ -634,12 +709,16 @@ class FlowNetEngine:
             raise ValueError("FlowNetEngine: bidirectional needs inference=True (the training engine is bidirectional already)")
         if supervised and inference:
             raise ValueError("FlowNetEngine: supervised and inference are exclusive")
+        if not isinstance(sequence, bool) and sequence != 'bidirectional':
+            raise ValueError("FlowNetEngine: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and (bidirectional or supervised or not inference):
-            raise ValueError("FlowNetEngine: sequence needs inference=True and is one-direction (neither bidirectional nor "
-                             "supervised)")
+            raise ValueError("FlowNetEngine: sequence needs inference=True without supervised or bidirectional=True (both "
+                             "directions of a clip: sequence='bidirectional')")
         self.supervised = bool(supervised)
         self.inference = bool(inference)
-        self.bidirectional = bool(bidirectional)
+        # sequence='bidirectional': both directions of every pair of the clip — bidirectional AND sequence
+        self.seq_bidir = sequence == 'bidirectional'
+        self.bidirectional = bool(bidirectional) or self.seq_bidir
         self.sequence = bool(sequence)
         # FlowNetC tower on 2B rows, everything after it on B rows
         self.one_dir = self.supervised or (self.inference and not self.bidirectional)
@@ -1125,18 +1204,19 @@ class FlowNetEngine:
         re-split from all F fp32 rows of c3 by every forward pass, after the carry."""
         bufs = []
 
-        def add(t, pl, lo, n):
-            """channels [lo, lo + n) of the fp32 tensor t [F, h, w, C] and of its planes pl [P, F, h, w, Cp]"""
+        def add(t, pl, lo, n, r=0):
+            """channels [lo, lo + n) of the fp32 tensor t [F, h, w, C] and of its planes pl [P, F, h, w, Cp]; r: the row that
+            holds the tower's row 0 (bidirectional sequence engine: cat2 keeps the tower behind the backward block)"""
             px = t.shape[1] * t.shape[2]
-            bufs.append(_lib.CarryBuf(t[0, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4))
+            bufs.append(_lib.CarryBuf(t[r, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4))
             for p in ([] if pl is None else range(pl.shape[0])):
-                bufs.append(_lib.CarryBuf(pl[p, 0, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
+                bufs.append(_lib.CarryBuf(pl[p, r, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
         add(self.x0, None, 0, 4)
         st = self.stages[0]
         if st.is_c:
             for name, seg in (('c3', 'conv3'), ('cat2', 'conv2')):
                 lo, n = st.bufs[name][1][seg]
-                add(st.A[name].t, st.A[name].pl, lo, pad4(n))
+                add(st.A[name].t, st.A[name].pl, lo, pad4(n), st.row0.get(name, 0))
         return bufs
 
     def sequence_carry(self, src_dev):
@@ -1753,7 +1833,13 @@ class FlowNetEngine:
                                                     cf(FLOW_SCALE * 4), self.stream()), "resize_bilinear")
         if self.one_dir:
             return self.final_flow, None
-        return self.final_flow[:self.B], self.final_flow[self.B:]
+        return self.fw_bw(self.final_flow)
+
+    def fw_bw(self, t):
+        """(forward rows, backward rows) of a tensor over the 2B directed rows: the forward block first — except in the
+        bidirectional sequence engine, whose backward block comes first."""
+        B = self.B
+        return (t[B:], t[:B]) if self.seq_bidir else (t[:B], t[B:])
 
     def flows(self):
         """(flows_fw, flows_bw): lists [flow2..flow6] ([flow0, flow1, flow2..] with full_res), NHWC, like
@@ -1762,9 +1848,8 @@ class FlowNetEngine:
         lv = self.stages[-1].flow_levels
         if self.one_dir:
             return [self.act['flow%d' % l] for l in lv], None
-        fw = [self.act['flow%d' % l][:B] for l in lv]
-        bw = [self.act['flow%d' % l][B:] for l in lv]
-        return fw, bw
+        both = [self.fw_bw(self.act['flow%d' % l]) for l in lv]
+        return [f for f, _ in both], [b for _, b in both]
 
 
 def flow_error_avg(flow_1, flow_2, mask=None):

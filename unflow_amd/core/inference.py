@@ -33,6 +33,12 @@ sequence=True: flow along a clip f0 .. fT-1, every frame uploaded once and encod
 
 with the frame table, the pair table and src in one device int32 buffer the host rewrites before each replay (push,
 estimate_sequence, export_sequence; sequence_tables is the host packing).
+
+sequence='bidirectional': both of the above along a clip.  The engine keeps the same F frame rows and tower and
+runs everything behind the tower on 2B rows, a block of B backward pairs (frame i + 1, frame i) and a block of B forward pairs;
+unflow_sequence_mirror, inside forward_net() behind conv2, gives the backward block's decoder the skip connection of ITS first
+frame.  The graph ends with unflow_inference_output on either block and unflow_inference_occlusion, all over the pair table
+(push_bidirectional, estimate_sequence_bidirectional, export_sequence(backward=, occlusion=)).
 """
 import collections
 import itertools
@@ -233,26 +239,33 @@ class FlowEstimator:
     export(visual=True)).
     sequence: the estimator of a clip — reset / push / estimate_sequence / export_sequence: the flow from every frame to the
     next, each frame uploaded and encoded once; the pair methods (estimate, evaluate, export, ...) then raise RuntimeError, as
-    the sequence methods do on a pair estimator.  Not with bidirectional (the backward pair's first frame is row i + 1: the
-    decoder's skip connection is no longer row-aligned) nor visual (that kernel reads the [2][B] frame layout)."""
+    the sequence methods do on a pair estimator.  sequence='bidirectional': the same along a clip in both directions —
+    push_bidirectional / estimate_sequence_bidirectional give the backward flow and both occlusion masks of every pair,
+    export_sequence its backward / occlusion files; push and estimate_sequence still return the forward flows alone.  (Not
+    spelt bidirectional=True with sequence: ValueError.)  Not with visual (that kernel reads the [2][B] frame layout)."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
                  visual=False, sequence=False):
-        if sequence and (bidirectional or visual):
-            raise ValueError("FlowEstimator: sequence=True is one-direction and without pictures (bidirectional / visual "
-                             "sequence mode is not built)")
+        if not isinstance(sequence, bool) and sequence != 'bidirectional':
+            raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
+        if sequence and bidirectional:
+            raise ValueError("FlowEstimator: both directions along a clip are sequence='bidirectional', not bidirectional=True "
+                             "with sequence")
+        if sequence and visual:
+            raise ValueError("FlowEstimator: a sequence estimator is without pictures (visual sequence mode is not built)")
         self.sequence = bool(sequence)
+        self.seq_bidir = sequence == 'bidirectional'
         self.params = dict(params)
         self.B = int(batch)
         self.H, self.W = (int(v) for v in net_size)
         self.Hmax, self.Wmax = (int(v) for v in (max_frame or net_size))
         self.dev = torch.device('cuda:0') if device is None else torch.device(device)
         self.use_graph = bool(use_graph)
-        self.bidirectional = bool(bidirectional)
+        self.bidirectional = bool(bidirectional) or self.seq_bidir
         self.visual = bool(visual)
         eng_params = {k: v for k, v in self.params.items() if k.endswith('_weight') or k in ENGINE_KEYS}
         self.engine = FlowNetEngine(self.B, self.H, self.W, params=eng_params or None, device=self.dev, seed=None,
-                                    inference=True, bidirectional=self.bidirectional, sequence=self.sequence)
+                                    inference=True, bidirectional=bool(bidirectional), sequence=sequence)
         e = self.engine
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         L = _lib.lib()
@@ -341,16 +354,28 @@ class FlowEstimator:
                                             ptr(self.vis_max), ptr(self.vis), None, st), "inference_visual")
 
     def _launch_sequence(self):
-        """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds)."""
+        """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds);
+        sequence='bidirectional': the output kernel on either block of the engine's 2B rows, then the occlusion kernel, all
+        three over the pair table and without ground truth."""
         e, B = self.engine, self.B
         L = _lib.lib()
         e.sequence_carry(self.tab[16 * B:])
         e.sequence_input(self.frames, self.tab, self.Hmax, self.Wmax)
         e.forward_net()
         f = self.flow_src
-        check(L.unflow_inference_output(ptr(f), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W,
-                                        ptr(self.tab[8 * B:]), B, self.Hmax, self.Wmax, ptr(self.out_flow), ptr(self.out_u16), None,
-                                        None, None, None, None, None, e.stream()), "inference_output")
+        pairs = self.tab[8 * B:]
+        outs = [(f, self.out_flow, self.out_u16)]
+        if self.seq_bidir:
+            fw, bw = e.fw_bw(f)
+            outs = [(fw, self.out_flow, self.out_u16), (bw, self.out_flow_bw, self.out_u16_bw)]
+        for src, flow, u16 in outs:
+            check(L.unflow_inference_output(ptr(src), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(pairs), B,
+                                            self.Hmax, self.Wmax, ptr(flow), ptr(u16), None, None, None, None, None, None,
+                                            e.stream()), "inference_output")
+        if self.seq_bidir:
+            check(L.unflow_inference_occlusion(ptr(self.out_flow), ptr(self.out_flow_bw), ptr(pairs), B, self.Hmax, self.Wmax,
+                                               None, ptr(self.occ[0]), ptr(self.occ[1]), ptr(self.occ_counts), e.stream()),
+                  "inference_occlusion")
 
     def _launch_backward(self, f, st):
         L = _lib.lib()
@@ -570,6 +595,11 @@ class FlowEstimator:
     def _sequence_mode(self, what):
         if not self.sequence:
             raise RuntimeError("%s: a pair estimator; build it with FlowEstimator(..., sequence=True)" % what)
+
+    def _sequence_bidir_mode(self, what):
+        if not self.seq_bidir:
+            raise RuntimeError("%s: %s; build it with FlowEstimator(..., sequence='bidirectional')"
+                               % (what, "a one-direction sequence estimator" if self.sequence else "a pair estimator"))
 
     @staticmethod
     def _pairs(frames1, frames2, what):
@@ -913,10 +943,11 @@ class FlowEstimator:
             out.append(a)
         return out
 
-    def _submit_sequence(self, frames, want=('flow',), encode=False):
+    def _submit_sequence(self, frames, want=('flow',), encode=False, surfaces=('u16',)):
         """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns (slot, valid
-        pair slots).  encode: the valid pairs' flow PNGs go through the device encode path (_filter) into slot.scan; 'device':
-        deflated there too."""
+        pair slots).  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ').  encode: the
+        valid pairs' PNGs — per pair the _Encoder surfaces named in `surfaces`, in that order — go through the device encode
+        path (_filter) into slot.scan; 'device': deflated there too."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
@@ -947,8 +978,14 @@ class FlowEstimator:
                 slot.flow.copy_(self.out_flow, non_blocking=True)
             if 'u16' in want:
                 slot.u16.copy_(self.out_u16, non_blocking=True)
+            if 'flow_bw' in want:
+                slot.flow_bw.copy_(self.out_flow_bw, non_blocking=True)
+            if 'u16_bw' in want:
+                slot.u16_bw.copy_(self.out_u16_bw, non_blocking=True)
+            if 'occ' in want:
+                slot.occ.copy_(self.occ, non_blocking=True)
             if encode:
-                self._filter(slot, [('u16', i, h, w) for i in valid], encode == 'device')
+                self._filter(slot, [(s, i, h, w) for i in valid for s in surfaces], encode == 'device')
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -966,14 +1003,38 @@ class FlowEstimator:
         fl = slot.flow.numpy()
         return [fl[i, :h, :w].copy() for i in valid]
 
-    def _pipeline_sequence(self, frames, want, encode=False):
+    def _bidirectional_of(self, slot, valid):
+        """The valid pairs of a finished bidirectional replay as BidirectionalFlow tuples."""
+        h, w, _ = self._clip
+        fl, fb, oc = slot.flow.numpy(), slot.flow_bw.numpy(), slot.occ.numpy()
+        return [BidirectionalFlow(fl[i, :h, :w].copy(), fb[i, :h, :w].copy(), oc[0, i, :h, :w].astype(bool),
+                                  oc[1, i, :h, :w].astype(bool)) for i in valid]
+
+    def push_bidirectional(self, frames):
+        """push on a sequence='bidirectional' estimator, both directions: one BidirectionalFlow(flow_fw, flow_bw, occ_fw, occ_bw)
+        per new pair (n, n + 1) — flow_fw from frame n to n + 1 (push's flow), flow_bw from frame n + 1 to n, the masks
+        losses.occlusion of the two, as estimate_bidirectional returns them.  The count is push's."""
+        self._sequence_bidir_mode('push_bidirectional')
+        slot, valid = self._submit_sequence(list(frames), ('flow', 'flow_bw', 'occ'))
+        slot.wait()
+        return self._bidirectional_of(slot, valid)
+
+    def estimate_sequence_bidirectional(self, frames):
+        """estimate_sequence in both directions: T >= 2 frames -> T - 1 BidirectionalFlow tuples (push_bidirectional's)."""
+        self._sequence_bidir_mode('estimate_sequence_bidirectional')
+        out = []
+        for slot, valid in self._pipeline_sequence(frames, ('flow', 'flow_bw', 'occ')):
+            out += self._bidirectional_of(slot, valid)
+        return out
+
+    def _pipeline_sequence(self, frames, want, encode=False, surfaces=('u16',)):
         """reset, then pipelined pushes of B frames: yields (slot, valid pair slots) per replay; replay k + 1 is staged and
         queued before replay k is handed out."""
         self.reset()
         prev, total = None, 0
         for chunk in chunks(frames, self.B):
             total += len(chunk)
-            cur = self._submit_sequence(chunk, want, encode)
+            cur = self._submit_sequence(chunk, want, encode, surfaces)
             if prev is not None:
                 prev[0].wait()
                 yield prev
@@ -994,42 +1055,66 @@ class FlowEstimator:
             out += [fl[i, :h, :w].copy() for i in valid]
         return out
 
-    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host'):
+    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
         writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
-        export ('device': unflow_deflate behind the filter launch; needs workers >= 1)."""
-        from .input import write_flo, write_kitti_flow_png
+        export ('device': unflow_deflate behind the filter launch; needs workers >= 1).
+        backward: also the backward flow (frame n + 1 -> frame n), %06d_01.png / .flo; occlusion: the forward occlusion mask,
+        %06d_10_occ.png (8-bit grey, 255 = occluded) — export's files, per pair in export's order (_10, _01, _10_occ).  Both need
+        an estimator built with sequence='bidirectional'."""
+        from .input import write_flo, write_kitti_flow_png, write_png_gray8
         from .png_device import check_deflate_mode
         self._sequence_mode('export_sequence')
         on_device = check_deflate_mode(deflate, workers)
         if fmt not in ('png', 'flo'):
             raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
+        if (backward or occlusion) and not self.seq_bidir:
+            raise ValueError("export_sequence: backward / occlusion files need FlowEstimator(..., sequence='bidirectional')")
         os.makedirs(out_dir, exist_ok=True)
+        tags = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
         if workers:
             from .png_device import DeviceFileWriter, flo_file_bytes
             n = 0
+            surfaces = (tuple(u16 for _, u16, _ in tags) if fmt == 'png' else ()) + (('occ',) if occlusion else ())
             with DeviceFileWriter(workers, level) as pool:
-                encode = ('device' if on_device else 'host') if fmt == 'png' else False
-                for slot, valid in self._pipeline_sequence(frames, ('flow',) if fmt == 'flo' else (), encode=encode):
+                encode = ('device' if on_device else 'host') if surfaces else False
+                want = tuple(flow for _, _, flow in tags) if fmt == 'flo' else ()
+                for slot, valid in self._pipeline_sequence(frames, want, encode=encode, surfaces=surfaces):
                     h, w, _ = self._clip
-                    for j, i in enumerate(valid):
-                        path = os.path.join(out_dir, '%06d_10.%s' % (n, fmt))
-                        if fmt == 'png':
-                            off, nb, _, _, depth, ctype = slot.spans[j]
-                            pool.submit(path, slot.scan_kind, (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
-                        else:
-                            pool.submit(path, 'flo', flo_file_bytes(slot.flow.numpy()[i, :h, :w]))
+                    spans = iter(slot.spans or ())
+
+                    def png(name):
+                        off, nb, _, _, depth, ctype = next(spans)
+                        pool.submit(os.path.join(out_dir, name), slot.scan_kind,
+                                    (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
+                    for i in valid:
+                        for tag, _, flow in tags:
+                            if fmt == 'png':
+                                png('%06d_%s.png' % (n, tag))
+                            else:
+                                pool.submit(os.path.join(out_dir, '%06d_%s.flo' % (n, tag)), 'flo',
+                                            flo_file_bytes(getattr(slot, flow).numpy()[i, :h, :w]))
+                        if occlusion:
+                            png('%06d_10_occ.png' % n)
                         n += 1
             return list(pool.paths)
         paths = []
-        for slot, valid in self._pipeline_sequence(frames, ('u16',) if fmt == 'png' else ('flow',)):
+        want = tuple(u16 if fmt == 'png' else flow for _, u16, flow in tags) + (('occ',) if occlusion else ())
+        n = 0
+        for slot, valid in self._pipeline_sequence(frames, want):
             h, w, _ = self._clip
             for i in valid:
-                path = os.path.join(out_dir, '%06d_10.%s' % (len(paths), fmt))
-                if fmt == 'png':
-                    write_kitti_flow_png(path, slot.u16.numpy()[i, :h, :w].view(np.uint16))
-                else:
-                    write_flo(path, slot.flow.numpy()[i, :h, :w])
-                paths.append(path)
+                for tag, u16, flow in tags:
+                    path = os.path.join(out_dir, '%06d_%s.%s' % (n, tag, fmt))
+                    if fmt == 'png':
+                        write_kitti_flow_png(path, getattr(slot, u16).numpy()[i, :h, :w].view(np.uint16))
+                    else:
+                        write_flo(path, getattr(slot, flow).numpy()[i, :h, :w])
+                    paths.append(path)
+                if occlusion:
+                    path = os.path.join(out_dir, '%06d_10_occ.png' % n)
+                    write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
+                    paths.append(path)
+                n += 1
         return paths

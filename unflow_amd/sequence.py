@@ -2,12 +2,15 @@
 once (core/inference.FlowEstimator(..., sequence=True)).
 
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
+                                  [--output_backward] [--occlusion]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
 experiment's config and latest checkpoint are found as python -m unflow_amd.evaluate finds them.  Files go to <--out>/NAME/:
 %06d_10.png (KITTI 16-bit flow) or, with --flo, %06d_10.flo — with --workers N (N >= 1) through the device encode path (DESIGN 7.11; --level L);
-the default and --host_encode: the host's writers."""
+the default and --host_encode: the host's writers.  --output_backward adds the backward flow of every pair (%06d_01.png / .flo),
+--occlusion its forward occlusion mask (%06d_10_occ.png); either one runs both directions along the clip
+(FlowEstimator(..., sequence='bidirectional'))."""
 import argparse
 import os
 import sys
@@ -90,6 +93,10 @@ def parser():
     ap.add_argument('--batch', type=int, default=4, metavar='B', help='new frames per graph replay')
     ap.add_argument('--net_size', type=int, nargs=2, default=(384, 1280), metavar=('H', 'W'),
                     help='network input size (multiples of 64)')
+    ap.add_argument('--output_backward', action='store_true',
+                    help='also the backward flow of every pair (frame n + 1 -> frame n): %%06d_01.png / .flo')
+    ap.add_argument('--occlusion', action='store_true',
+                    help='also the forward-backward occlusion mask of every pair: %%06d_10_occ.png (255 = occluded)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -135,14 +142,14 @@ def main(argv=None):
     convert_input_strings(params, config_dict(a.config).get('dirs', {}))
     params.update(config.get('train_kitti', {}))
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
-                                        sequence=True)
+                                        sequence='bidirectional' if (a.output_backward or a.occlusion) else True)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
     try:
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
-                                    deflate=a.deflate)
+                                    deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))
