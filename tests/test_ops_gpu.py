@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from warp_parity import area_weights as _area_weights      # the fp64 area weights, shared with the parity tests
+
 pytestmark = pytest.mark.gpu
 
 
@@ -401,19 +403,6 @@ def test_correlation_backward_both_math_modes(dev):
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-x", "-k", "correlation"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:]
-
-
-def _area_weights(n_in, n_out):
-    """[n_out, n_in] weights of tf.image.resize_area along one axis (TF's ResizeAreaOp): output i averages the source interval
-    [i*s, (i+1)*s), s = n_in / n_out, every source pixel weighted by the covered fraction — the independent restatement."""
-    import math
-    s = n_in / n_out
-    w = torch.zeros(n_out, n_in, dtype=torch.float64)
-    for i in range(n_out):
-        lo, hi = i * s, (i + 1) * s
-        for j in range(int(math.floor(lo)), min(n_in, int(math.ceil(hi)))):
-            w[i, j] = (min(hi, j + 1) - max(lo, j)) / s
-    return w
 
 
 def test_resize_area_integer_fractional_and_odd_sizes(dev):

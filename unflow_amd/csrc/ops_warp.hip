@@ -7,6 +7,7 @@
 //   downsample     <- ops/downsample_op.cu.cc:15-49       (box mean)
 #include "common.h"
 #include "image_warp.h"
+#include "options.h"
 
 // ------------------------------------------------------------------ backward_warp
 struct BwTaps {
@@ -352,6 +353,16 @@ __device__ __forceinline__ float splat_weight(float dx, float dy) {
   return expf(-(dx * dx + dy * dy) / 2.0f);  // gauss_divisor = 2*std^2 = 2 (ref :53-56)
 }
 
+// A footprint is 9 pixels per axis except where the fp32 sum t + 4 rounds UP to an integer (t one ulp below an integer and
+// t + 4 in the next binade: t in [4,8), [12,16), [28,32), [60,64), ...): then floorf(t - 4)..floorf(t + 4) is TEN pixels, and
+// the reference loops over all of them (the tenth weighs exp(-8) = 3.4e-4 of its row / column).  The unrolled nine-tap bodies
+// below hand such a footprint to a plain lo..hi loop (rare: a flow has to hit one value in 2^20).
+__device__ __forceinline__ bool fw_wide(const FwFoot& f) { return f.x_hi - f.x_lo > 8 || f.y_hi - f.y_lo > 8; }
+__device__ __forceinline__ float fw_w1(int n, float t) {
+  const float d = (float)n - t;
+  return expf(-(d * d) / 2.0f);      // the separable factor: the same expression (and bits) as the nine-tap bodies
+}
+
 // ---- tiled scatter --------------------------------------------------------------------------------------------------------
 // The reference kernel (forward_warp_op.cu.cc:16-65) is one thread per source pixel and <= 81 float atomicAdds into the output.
 // Its cost is the atomics: 81 device-scope read-modify-writes per pixel.  Here a workgroup owns a 64 x 16 tile of SOURCE pixels
@@ -377,7 +388,10 @@ constexpr double FW_QINV = 1.0 / 2147483648.0;
 // FAR: a source whose footprint does not lie inside the window as a whole is not scattered here at all — its linear index goes
 // to `far_list` (one global atomic per tile reserves the slots) and the binned gather below takes it; without FAR (no
 // workspace for the bins) its out-of-window taps take the global atomics directly, as before.
-constexpr int FB_T = 32;                              // target tile edge of the far path (>= 9: a footprint touches at most 2 x 2 tiles)
+constexpr int FB_T = 32;                              // target tile edge of the far path
+// A footprint is at most 10 pixels per axis (fw_wide), so it touches at most 2 x 2 target tiles: the far path's sizing
+// (4 bin entries per source, fw_ws_layout) holds for the ten-wide footprints as well.
+static_assert(FB_T >= 10, "a footprint must not span more than two target tiles per axis");
 constexpr int FB_MAP = 16;                            // a source tile's far sources are counted in an LDS map of 16 x 16 target tiles first
 
 // target tiles (<= 2 x 2) of a footprint -> callback(global tile index, index in the workgroup's map or -1)
@@ -483,27 +497,38 @@ __global__ __launch_bounds__(256) void forward_warp_tile_kernel(const float* __r
         }
         continue;
       }
+      // one tap: into the window, or (outside it, without FAR) straight to memory
+      auto put = [&](int nx, int ny, float w) {
+        const unsigned long long q = (unsigned long long)(unsigned)(w * FW_Q + 0.5f);
+        const int lx = nx - wx0, ly = ny - wy0;
+        if ((unsigned)lx < (unsigned)FW_WX && (unsigned)ly < (unsigned)FW_WY) {
+          atomicAdd(&win[ly * FW_WX + lx], q);
+        } else if (DET) {
+          atomicAdd(acc + img + (long)ny * W + nx, q);
+        } else {
+          atomicAdd(outf + img + (long)ny * W + nx, w);
+        }
+      };
+      if (fw_wide(f)) {                          // ten taps on an axis (never the 9 x 9 case above): the reference's own loops
+#pragma unroll 1
+        for (int ny = f.y_lo; ny <= f.y_hi; ny++) {
+          const float wy = fw_w1(ny, f.ty);
+#pragma unroll 1
+          for (int nx = f.x_lo; nx <= f.x_hi; nx++) put(nx, ny, wy * fw_w1(nx, f.tx));
+        }
+        continue;
+      }
 #pragma unroll
       for (int i = 0; i < 9; i++) {
         const int ny = f.y_lo + i;
         if (ny > f.y_hi) continue;
         const float dy = (float)ny - f.ty;
         const float wy = expf(-(dy * dy) / 2.0f);
-        const int ly = ny - wy0;
 #pragma unroll
         for (int j = 0; j < 9; j++) {
           const int nx = f.x_lo + j;
           if (nx > f.x_hi) continue;
-          const float w = wy * wxv[j];
-          const unsigned long long q = (unsigned long long)(unsigned)(w * FW_Q + 0.5f);
-          const int lx = nx - wx0;
-          if ((unsigned)lx < (unsigned)FW_WX && (unsigned)ly < (unsigned)FW_WY) {
-            atomicAdd(&win[ly * FW_WX + lx], q);
-          } else if (DET) {
-            atomicAdd(acc + img + (long)ny * W + nx, q);
-          } else {
-            atomicAdd(outf + img + (long)ny * W + nx, w);
-          }
+          put(nx, ny, wy * wxv[j]);
         }
       }
     }
@@ -540,7 +565,7 @@ __global__ __launch_bounds__(256) void forward_warp_tile_kernel(const float* __r
 // A field that tears a source tile apart (|flow| of tens of pixels, uncorrelated) leaves most footprints outside the tile's
 // window; as global atomics those taps cost 81 memory-side read-modify-writes per source (22 ms at 16 x 768 x 1024, U(-50, 50)).
 // Instead: (1) the tile kernel lists such sources and (2) counts them into the 32 x 32-pixel TARGET tiles their footprints touch
-// (<= 2 x 2: a footprint is 9 pixels wide) — per workgroup in an LDS map of 16 x 16 tiles first, (3) an exclusive scan turns the
+// (<= 2 x 2: a footprint is at most 10 pixels wide) — per workgroup in an LDS map of 16 x 16 tiles first, (3) an exclusive scan turns the
 // counts into bin offsets, (4) the sources are written into their bins, (5) one workgroup per target tile sums the taps of its bin's sources that fall inside the
 // tile in LDS (64-bit fixed point, as above) and adds the tile to the output with plain stores — every pixel has one owner, and
 // integer sums do not depend on the order of a bin's entries: bit-reproducible like the window path.  Everything is sized and
@@ -631,6 +656,17 @@ __global__ __launch_bounds__(256) void forward_warp_gather_kernel(const float* _
     const int X0 = tx * FB_T, Y0 = ty * FB_T;
     for (int e = e0 + threadIdx.x; e < e1; e += 256) {
       const FwFoot f = fw_foot_of(flow, entries[e], H, W);
+      if (fw_wide(f)) {                                // ten taps on an axis: the reference's own loops, clipped to this tile
+        const int ya = max(f.y_lo, Y0), yb = min(f.y_hi, Y0 + FB_T - 1), xa = max(f.x_lo, X0), xb = min(f.x_hi, X0 + FB_T - 1);
+#pragma unroll 1
+        for (int ny = ya; ny <= yb; ny++) {
+          const float wy = fw_w1(ny, f.ty);
+#pragma unroll 1
+          for (int nx = xa; nx <= xb; nx++)
+            atomicAdd(win + (ny - Y0) * FB_T + (nx - X0), (unsigned long long)(unsigned)(wy * fw_w1(nx, f.tx) * FW_Q + 0.5f));
+        }
+        continue;
+      }
       float wxv[9];                                    // separable weights, the same two expf per tap as the window path: same bits
 #pragma unroll
       for (int j = 0; j < 9; j++) {
@@ -672,6 +708,22 @@ __global__ void forward_warp_fixed_to_float_kernel(const unsigned long long* __r
     out[i] = (float)((double)acc[i] * FW_QINV);
 }
 
+// a ten-wide / ten-tall footprint (fw_wide): the reference's loops (:108-119), rows outer like the nine-tap bodies
+__device__ __forceinline__ void fw_bwd_wide(const float* __restrict__ img, const FwFoot& f, int W, float& du, float& dv) {
+#pragma unroll 1
+  for (int ny = f.y_lo; ny <= f.y_hi; ny++) {
+    const float dy = (float)ny - f.ty;
+    const float wy = expf(-(dy * dy) / 2.0f);
+#pragma unroll 1
+    for (int nx = f.x_lo; nx <= f.x_hi; nx++) {
+      const float dx = (float)nx - f.tx;
+      const float factor = img[(long)ny * W + nx] * (wy * expf(-(dx * dx) / 2.0f));
+      du += factor * dx;
+      dv += factor * dy;
+    }
+  }
+}
+
 // Gradient (forward_warp_op.cu.cc:67-125): a gather over the source's own footprint — no atomics in the reference either.
 // Same separable weights; dout is read through L1 (neighbouring sources share most of their 9 x 9 windows).
 __global__ void forward_warp_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ flow,
@@ -683,7 +735,9 @@ __global__ void forward_warp_bwd_kernel(const float* __restrict__ dout, const fl
     const float2 fl = reinterpret_cast<const float2*>(flow)[px.i];
     const FwFoot f = fw_footprint(px.x, px.y, fl.x, fl.y, W, H);
     float du = 0.f, dv = 0.f;
-    if (f.ok) {
+    if (f.ok && fw_wide(f)) {
+      fw_bwd_wide(dout + (long)px.n * H * W, f, W, du, dv);
+    } else if (f.ok) {
       const float* img = dout + (long)px.n * H * W;
       float wxv[9], dxv[9];
 #pragma unroll
@@ -724,7 +778,9 @@ __global__ void forward_warp_bwd_rows_kernel(const float* __restrict__ dout, con
     const float2 fl = reinterpret_cast<const float2*>(flow)[px.i];
     const FwFoot f = fw_footprint(px.x, px.y, fl.x, fl.y, W, H);
     float du = 0.f, dv = 0.f;
-    if (f.ok) {
+    if (f.ok && fw_wide(f)) {                    // (plain dword loads of taps inside the image: no wide rows here)
+      fw_bwd_wide(dout + (long)px.n * H * W, f, W, du, dv);
+    } else if (f.ok) {
       float wxv[9], dxv[9];
 #pragma unroll
       for (int j = 0; j < 9; j++) {
@@ -853,7 +909,7 @@ UNFLOW_API int unflow_forward_warp_bwd(const float* dout, const float* flows, fl
   if (!dout || !flows || !dflows) return UNFLOW_ERR_NULL;
   const long npx = (long)B * H * W;
   if (npx == 0) return UNFLOW_OK;
-  if (npx * 4 < (1l << 31) - 1024)
+  if (unflow::options().fw_bwd_rows && npx * 4 < (1l << 31) - 1024)
     forward_warp_bwd_rows_kernel<<<stream_grid(npx), 256, 0, as_stream(stream)>>>(dout, flows, dflows, B, H, W);
   else
     forward_warp_bwd_kernel<<<stream_grid(npx), 256, 0, as_stream(stream)>>>(dout, flows, dflows, B, H, W);

@@ -35,7 +35,8 @@
   X(corr_bwd_b128, 1)     /* 16-byte band loads in the correlation backward */                                            \
   X(corr_bwd_rot, -1)     /* rotated displacement-row order in the correlation backward (-1: narrow band only) */         \
   X(corr_bwd_planes, 1)   /* correlation backward from the feature planes */                                              \
-  X(corr_bwd_share, 1)    /* ... with the band operand fetched once per workgroup (C a multiple of 256) */
+  X(corr_bwd_share, 1)    /* ... with the band operand fetched once per workgroup (C a multiple of 256) */                                      \
+  X(fw_bwd_rows, 1)       /* forward_warp gradient with footprint rows as 16-byte buffer loads (tensors below 2 GiB); 0: the dword-load kernel at any size */
 
 namespace unflow {
 struct Options {
