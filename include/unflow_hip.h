@@ -705,6 +705,31 @@ int unflow_inference_visual(const void* frames, const int* desc, int B, int Hmax
                             const float* gt_flow, const float* gt_mask, float* shown, unsigned* max_bits, unsigned char* out_u8,
                             float* out_f32, unflow_stream_t stream);
 
+/* The pictures of one sequence replay (FlowEstimator(..., sequence=True | 'bidirectional', visual='sequence')), every frame of the
+ * clip resampled once.  frames [B][Hmax][Wmax][3]: the up to B NEW staged frames, as for unflow_inference_input_frames.  tab: the
+ * DEVICE int32 tables of the replay (core/inference.py sequence_tables): frame table [B][8] at word 0, pair table [B][8] at
+ * word 8B (pair i = engine rows i, i + 1; h = 0: not a pair of the clip), the carry source at word 16B and at word 16B + 1 the
+ * bit pattern of a clip-wide max_flow (0: every pair is coloured with its own maximum).  flow_fw [B][Hmax][Wmax][2]: the
+ * frame-size flow of unflow_inference_output per pair slot; flow_bw (the backward flow, the same layout) and occ_fw
+ * [B][Hmax][Wmax] uint8 (unflow_inference_occlusion's forward mask): both given or both NULL.
+ * shown: (B + 1) * Hmax * Wmax * 4 floats, 16-byte aligned, one shown frame (resized to (H, W) and back) per engine row; it must
+ * survive from one replay of a clip to the next.  Three launches:
+ *   unflow_sequence_carry on shown: row `carry source` (the previous replay's last frame) -> row 0 (0: nothing carried);
+ *   a frames kernel: staged frame j (frame-table slot j, h > 0) -> shown row j + 1, unflow_inference_visual's expression, and
+ *     max |flow_fw|, max |flow_bw| of pair slot j (not formed with a clip-wide max_flow);
+ *   an images kernel: for every pair i with h > 0 and every pixel (y < h, x < w), into image k of out
+ *     [UNFLOW_VISUAL_IMAGES][B][Hmax][Wmax][3] (nothing else is written), im1 = shown row i, im2 = shown row i + 1:
+ *       0 overlay, 1 brightness error, 2 flow colours of flow_fw: bit-identical to unflow_inference_visual on that pair;
+ *     and with flow_bw / occ_fw (without them images 3 and 4 are not written):
+ *       3 backward flow colours   flow_to_color(flow_bw), its own maximum per pair (eval_gui.py:166, commented out there);
+ *       4 non-occluded brightness error   image 1 where occ_fw == 0, exactly 0 where it is not.
+ * The max_flow of images 2 and 3 is the clip-wide one when word 16B + 1 is non-zero.  max_bits: 3 * B uint32 of scratch (the
+ * forward and backward maximum per pair slot, then B tickets), zero-initialised and left zero by every launch.  Deterministic:
+ * no float atomics.  Hmax * Wmax above 2^31 - 1 (2^28 - 1 for the carry): UNFLOW_ERR_SHAPE. */
+int unflow_sequence_visual(const void* frames, const int* tab, int B, int Hmax, int Wmax, int H, int W, const float* flow_fw,
+                           const float* flow_bw, const unsigned char* occ_fw, float* shown, unsigned* max_bits,
+                           unsigned char* out_u8, float* out_f32, unflow_stream_t stream);
+
 /* ===================================================================== */
 /* PNG decode on the device (csrc/png_decode.hip, core/png_device.py)      */
 /* ===================================================================== */

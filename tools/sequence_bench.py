@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional]
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
 of the replayed graph of FlowEstimator(..., sequence=True) in its steady state (a carried frame and B new frames: B pairs per
@@ -14,7 +14,11 @@ replays of either graph, heaviest first — where the time of a replay goes in e
 --bidirectional: the same table for FlowEstimator(..., sequence='bidirectional') against the pair-mode bidirectional
 estimator (both directions and the occlusion masks of B pairs per replay either way), the prediction made before the first run
 beside it, and — from a child run under rocprofv3 of ten replays of the FlowNetC graph at B = 4 — the time of
-unflow_sequence_mirror where it runs, behind conv2, with the bytes it must move."""
+unflow_sequence_mirror where it runs, behind conv2, with the bytes it must move.
+
+--visual: FlowNetC at B in {1, 4, 8}, the pair-mode visual estimator, then the sequence visual estimator (and the
+sequence estimator without pictures): ms per pair of each replayed graph.  With --rocprof, from one kernel-trace child run per
+mode, the picture kernels alone at B = 8 — the last `iters` dispatches of each, with the bytes they must move."""
 import argparse
 import csv
 import glob
@@ -39,8 +43,9 @@ def _frames(n):
     return [np.roll(a, 2 * i, 1) for i in range(n)]
 
 
-def _estimator(spec, B, sequence, bidirectional=False):
-    """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions."""
+def _estimator(spec, B, sequence, bidirectional=False, visual=False):
+    """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
+    pictures at the end of the graph."""
     import torch
     os.environ['UNFLOW_CONV_MATH'] = 'bf16x3'
     from unflow_amd.core.inference import FlowEstimator
@@ -49,7 +54,8 @@ def _estimator(spec, B, sequence, bidirectional=False):
     gc.collect()                               # an earlier case's estimator is freed now, not inside this measurement
     torch.cuda.synchronize()
     m0 = torch.cuda.memory_allocated(dev)
-    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional)
+    kw = dict(visual='sequence' if sequence else True) if visual else {}
+    est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
     est.engine.init_params(seed=1)
@@ -195,6 +201,98 @@ def rocprof_cases(iters):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --visual
+def visual_case(B, iters, warmup):
+    """FlowNetC at B: ms per pair of the pair-mode visual estimator, then of the sequence visual estimator (and of the sequence
+    estimator without pictures, for what the pictures add), each in its steady state."""
+    import gc
+    import torch
+    out = dict(spec='C', B=B)
+    for name, seq, vis in (('pair_visual', False, True), ('sequence_visual', True, True), ('sequence', True, False)):
+        est, mem = _estimator('C', B, seq, visual=vis)
+        out[name] = _stats(time_replays(est, iters, warmup), B)
+        out[name]['estimator_MB'] = round(mem / 1e6, 1)
+        del est
+        gc.collect()
+        torch.cuda.empty_cache()
+    out['sequence_visual_over_pair_visual'] = round(out['sequence_visual']['ms_per_pair'] / out['pair_visual']['ms_per_pair'], 4)
+    out['pictures_ms_per_pair_in_sequence'] = round(out['sequence_visual']['ms_per_pair'] - out['sequence']['ms_per_pair'], 4)
+    return out
+
+
+def visual_kernels_only(mode, iters, B=8):
+    """Child: the picture launches alone on a set-up FlowNetC visual estimator at B = 8, `iters` times — unflow_inference_visual
+    ('pair') or unflow_sequence_visual ('sequence': carry source B, every frame and pair slot valid)."""
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    est, _ = _estimator('C', B, mode == 'sequence', visual=True)
+    L, st = _lib.lib(), est.engine.stream()
+    torch.cuda.synchronize()
+    for _ in range(iters):
+        if mode == 'sequence':
+            check(L.unflow_sequence_visual(ptr(est.frames), ptr(est.tab), B, est.Hmax, est.Wmax, H, W, ptr(est.out_flow), None, None,
+                                           ptr(est.vis_shown), ptr(est.vis_max), ptr(est.vis), None, st), "sequence_visual")
+        else:
+            check(L.unflow_inference_visual(ptr(est.frames), ptr(est.desc), B, est.Hmax, est.Wmax, H, W, ptr(est.out_flow),
+                                            ptr(est.gt_flow), ptr(est.gt_mask), ptr(est.vis_shown), ptr(est.vis_max), ptr(est.vis),
+                                            None, st), "inference_visual")
+    torch.cuda.synchronize()
+
+
+def _last_dispatches(d, names, iters):
+    """Mean duration in ns of the LAST `iters` dispatches of every kernel in `names` (the child's own loop; what its set-up ran
+    before is left out), from the kernel trace of a rocprofv3 run in folder d; None when the trace cannot be read."""
+    files = glob.glob(os.path.join(d, '**', '*kernel_trace.csv'), recursive=True)
+    if not files:
+        return None
+    rows = list(csv.DictReader(open(files[0])))
+    if not rows or not {'Kernel_Name', 'Start_Timestamp', 'End_Timestamp'} <= set(rows[0]):
+        return None
+    out = {}
+    for name in names:
+        mine = sorted((int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in rows
+                      if name in r['Kernel_Name'] and ('sequence_' + name) not in r['Kernel_Name'])
+        if len(mine) >= iters:
+            out[name] = sum(e - s for s, e in mine[-iters:]) / float(iters)
+    return out
+
+
+def visual_bytes(B=8):
+    """Compulsory bytes per kernel at B (uint8 frames of FRAME, no ground truth; tap re-reads go through the caches): per frame
+    pixel — pair frames kernel 6 (two frames) + 8 (flow) read, 32 (two float4 frames) written; sequence frames kernel 3 + 8 read,
+    16 written; either images kernel 32 + 8 read, 9 (three byte images) written; the carry 16 + 16 per pixel of ONE (H, W)
+    staging row per replay."""
+    px = FRAME[0] * FRAME[1]
+    return {'visual_frames_kernel': (46, B * px * 46), 'visual_images_kernel': (49, B * px * 49),
+            'sequence_visual_frames_kernel': (27, B * px * 27), 'sequence_visual_images_kernel': (49, B * px * 49),
+            'sequence_carry_kernel': (32, H * W * 32)}
+
+
+def visual_rocprof(iters, B=8):
+    """Per-kernel times of the picture launches at B = 8, pair mode and sequence mode, one counters-free kernel-trace child each."""
+    nbytes = visual_bytes(B)
+    out = {}
+    for mode, names in (('pair', ('visual_frames_kernel', 'visual_images_kernel')),
+                        ('sequence', ('sequence_carry_kernel', 'sequence_visual_frames_kernel', 'sequence_visual_images_kernel'))):
+        d = tempfile.mkdtemp(prefix='seqvisprof_')
+        cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '-o', 'run', '--', sys.executable,
+               os.path.abspath(__file__), '--visual-kernels-only', mode, '--iters', str(iters)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+        if r.returncode != 0:
+            out[mode] = dict(error="rocprofv3 exit %d" % r.returncode, tail=r.stdout.decode(errors='replace')[-400:])
+            continue
+        ns = _last_dispatches(d, names, iters)
+        if ns is None:
+            out[mode] = dict(error="no readable kernel trace")
+            continue
+        k = {n: dict(us=round(ns[n] / 1e3, 2), B_per_px=nbytes[n][0], MB=round(nbytes[n][1] / 1e6, 2),
+                     TBps=round(nbytes[n][1] / ns[n] / 1e3, 3)) for n in names if n in ns}
+        k['total_us'] = round(sum(v['us'] for v in k.values()), 2)
+        out[mode] = k
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -204,7 +302,21 @@ def main():
     ap.add_argument('--bidirectional', action='store_true',
                     help="sequence='bidirectional' against the pair-mode bidirectional estimator (DESIGN 7.13)")
     ap.add_argument('--graph-only', choices=('pair', 'sequence', 'bidir', 'pair_bidir'), help=argparse.SUPPRESS)
+    ap.add_argument('--visual', action='store_true',
+                    help='the pair-mode visual estimator against the sequence visual estimator, FlowNetC (DESIGN 7.14)')
+    ap.add_argument('--visual-kernels-only', choices=('pair', 'sequence'), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.visual_kernels_only:
+        return visual_kernels_only(a.visual_kernels_only, a.iters)
+    if a.visual:
+        res = dict(metric='sequence_visual_ms_per_pair_over_pair_mode_visual', shape=[H, W], frames='uint8 %dx%d' % FRAME,
+                   math='bf16x3', iters=a.iters, warmup=a.warmup,
+                   expected='from the code, unmeasured when written: the frames kernel does B frames\' work instead of 2B, plus '
+                            'a 16-byte-per-pixel row copy', cases=[visual_case(B, a.iters, a.warmup) for B in (1, 4, 8)])
+        if a.rocprof:
+            res['kernels_B8'] = visual_rocprof(a.iters)
+        print(json.dumps(res))
+        return
     if a.kernels_only:
         return kernels_only(a.iters)
     if a.graph_only:

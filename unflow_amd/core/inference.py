@@ -39,6 +39,16 @@ runs everything behind the tower on 2B rows, a block of B backward pairs (frame 
 unflow_sequence_mirror, inside forward_net() behind conv2, gives the backward block's decoder the skip connection of ITS first
 frame.  The graph ends with unflow_inference_output on either block and unflow_inference_occlusion, all over the pair table
 (push_bidirectional, estimate_sequence_bidirectional, export_sequence(backward=, occlusion=)).
+
+sequence=True | 'bidirectional' with visual='sequence': pictures along a clip (visual=True is the pair estimator's
+flag and, with sequence, still a ValueError that names this spelling).  Either sequence graph ends with
+
+    unflow_sequence_visual         the new staged frames -> one shown frame per engine row, each frame of the clip resampled once
+                                   (row 0 carried like the engine's); per pair of the pair table the overlay, the brightness
+                                   error and the flow colours of unflow_inference_visual; bidirectional: also the backward flow's
+                                   colours and the brightness error of the non-occluded pixels
+
+(push_visual, visualize_sequence, export_sequence(visual=True)); a clip-wide max_flow of the colours travels in the tables.
 """
 import collections
 import itertools
@@ -54,6 +64,7 @@ from .engine import FLOW_SCALE, FlowNetEngine
 ENGINE_KEYS = ('flownet', 'train_all', 'full_res', 'pyramid_loss', 'border_mask', 'mask_occlusion')   # = Trainer.ENGINE_KEYS
 MAP_NAMES = {2: ('occluded', 'non-occluded'), 1: ('all',)}
 OCC_NAMES = ('occ/precision', 'occ/recall', 'occ/F1')
+_UNSET = object()
 
 # What estimate_bidirectional returns per pair: [h, w, 2] float32 flows, [h, w] bool occlusion masks (losses.occlusion)
 BidirectionalFlow = collections.namedtuple('BidirectionalFlow', ('flow_fw', 'flow_bw', 'occ_fw', 'occ_bw'))
@@ -67,6 +78,17 @@ VISUAL_TAGS = ('img', 'diff', 'flow', 'err', 'gt')
 def visual_files(n, has_gt):
     """The picture files of example n, in the order they are written: [(index into VISUAL_IMAGES, file name)]."""
     return [(k, '%06d_%s.png' % (n, VISUAL_TAGS[k])) for k in (0, 2, 1) + ((3, 4) if has_gt else ())]
+
+
+# What visualize_sequence returns per pair of a sequence='bidirectional' estimator: FlowVisual's three, the backward flow's colours
+# and the brightness error where the forward occlusion mask is 0 — the images of unflow_sequence_visual, in its order
+SequenceVisual = collections.namedtuple('SequenceVisual', FlowVisual._fields + ('flow_bw', 'warp_error_noc'))
+SEQUENCE_VISUAL_TAGS = VISUAL_TAGS[:3] + ('flow_bw', 'diff_noc')
+
+
+def sequence_visual_files(n, bidirectional):
+    """The picture files of pair n of a clip, in the order they are written: [(image of unflow_sequence_visual, file name)]."""
+    return [(k, '%06d_%s.png' % (n, SEQUENCE_VISUAL_TAGS[k])) for k in (0, 2, 1) + ((3, 4) if bidirectional else ())]
 
 
 def occlusion_scores(counts):
@@ -101,12 +123,14 @@ def pack_desc(shapes, batch, staged=None, nmaps=0, u8=False):
     return d
 
 
-def sequence_tables(shape, k, batch, carry, u8=False):
+def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None):
     """The device tables of one sequence replay, one int32 array [16 * batch + 4]: the frame table [batch][8] (pack_desc: the k
     new frames of size `shape` in rows 1 .. k of the engine, slots [0, k)), the pair table [batch][8] (slot i = rows i, i + 1:
-    valid when both hold frames of this clip — slot 0 needs a carried frame, slot i >= 1 needs i + 1 <= k) and the carry source
-    (row of the previous replay's last frame; 0: a clip's first replay, nothing carried).  Returns (table, slots of the valid
-    pairs in order, the next replay's carry source = k)."""
+    valid when both hold frames of this clip — slot 0 needs a carried frame, slot i >= 1 needs i + 1 <= k), the carry source
+    (row of the previous replay's last frame; 0: a clip's first replay, nothing carried) and, behind it, the max_flow of the
+    clip's flow colours (unflow_sequence_visual): 0 for None, every pair coloured with its own maximum, else the bit pattern of
+    float32 max(max_flow, 1) (flow_util.py:31-32).  Returns (table, slots of the valid pairs in order, the next replay's carry
+    source = k)."""
     batch, k, carry = int(batch), int(k), int(carry)
     if not 1 <= k <= batch:
         raise ValueError("a sequence replay takes 1 to %d new frames, got %d" % (batch, k))
@@ -120,6 +144,8 @@ def sequence_tables(shape, k, batch, carry, u8=False):
         pair[i] = (int(shape[0]), int(shape[1]), 0, 0, 0, int(bool(u8)), 0, 0)
     tab[8 * batch:16 * batch] = pair.reshape(-1)
     tab[16 * batch] = carry
+    if max_flow is not None:
+        tab[16 * batch + 1] = np.array([max(max_flow, 1)], dtype=np.float32).view(np.int32)[0]
     return tab, valid, k
 
 
@@ -242,7 +268,11 @@ class FlowEstimator:
     the sequence methods do on a pair estimator.  sequence='bidirectional': the same along a clip in both directions —
     push_bidirectional / estimate_sequence_bidirectional give the backward flow and both occlusion masks of every pair,
     export_sequence its backward / occlusion files; push and estimate_sequence still return the forward flows alone.  (Not
-    spelt bidirectional=True with sequence: ValueError.)  Not with visual (that kernel reads the [2][B] frame layout)."""
+    spelt bidirectional=True with sequence: ValueError.)  With visual='sequence' (visual=True with sequence: ValueError, as
+    before; the message names this spelling): the pictures of every pair of the clip, every frame
+    resampled once (push_visual, visualize_sequence, export_sequence(visual=True)): FlowVisual per pair, or SequenceVisual on a
+    sequence='bidirectional' estimator; max_flow there is one scale of the flow colours for the whole clip, set by the call that
+    starts the clip (None: every pair has its own maximum, as in pair mode)."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
                  visual=False, sequence=False):
@@ -251,8 +281,14 @@ class FlowEstimator:
         if sequence and bidirectional:
             raise ValueError("FlowEstimator: both directions along a clip are sequence='bidirectional', not bidirectional=True "
                              "with sequence")
-        if sequence and visual:
-            raise ValueError("FlowEstimator: a sequence estimator is without pictures (visual sequence mode is not built)")
+        if not isinstance(visual, bool) and visual != 'sequence':
+            raise ValueError("FlowEstimator: visual is False, True or 'sequence', got %r" % (visual,))
+        if sequence and visual is True:
+            raise ValueError("FlowEstimator: the pictures along a clip are visual='sequence' (a shown frame per engine row, "
+                             "unflow_sequence_visual), not visual=True with sequence")
+        if visual == 'sequence' and not sequence:
+            raise ValueError("FlowEstimator: visual='sequence' draws the pairs of a clip; it needs sequence=True or "
+                             "sequence='bidirectional' (a pair estimator's pictures are visual=True)")
         self.sequence = bool(sequence)
         self.seq_bidir = sequence == 'bidirectional'
         self.params = dict(params)
@@ -292,7 +328,8 @@ class FlowEstimator:
             self.vis = self.vis_shown = self.vis_max = None
             if self.visual:
                 self.vis = z(len(VISUAL_IMAGES), B, Hm, Wm, 3, dtype=torch.uint8)
-                self.vis_shown = z(2, B, Hm, Wm, 4)                  # the frames as shown: resized to the network and back
+                # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
+                self.vis_shown = z(B + 1, Hm, Wm, 4) if self.sequence else z(2, B, Hm, Wm, 4)
                 self.vis_max = z(3 * B, dtype=torch.int32)           # bit patterns of max |flow|, max |gt * mask|; B tickets
         last = e.stages[-1]
         self.flow_src = last.act['flow0'] if e.full_res else last.act['flow2']     # bidirectional: rows [0, B) fw, [B, 2B) bw
@@ -304,6 +341,7 @@ class FlowEstimator:
         self._carry = 0               # sequence: the row that holds the clip's last frame (0: none yet)
         self._clip = None             # sequence: (h, w, dtype is uint8) of the clip's frames
         self._seq_k = 0               # sequence: replays submitted (the pinned slot alternates)
+        self._max_flow = _UNSET       # sequence: the clip's max_flow of the flow colours (None: per pair), set by its first push
         self._enc = None              # _Encoder, built by the first export through the device encode path
 
     # ------------------------------------------------------------------------------------------ parameters
@@ -356,7 +394,7 @@ class FlowEstimator:
     def _launch_sequence(self):
         """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds);
         sequence='bidirectional': the output kernel on either block of the engine's 2B rows, then the occlusion kernel, all
-        three over the pair table and without ground truth."""
+        three over the pair table and without ground truth; visual: then the pictures, from the same tables."""
         e, B = self.engine, self.B
         L = _lib.lib()
         e.sequence_carry(self.tab[16 * B:])
@@ -376,6 +414,11 @@ class FlowEstimator:
             check(L.unflow_inference_occlusion(ptr(self.out_flow), ptr(self.out_flow_bw), ptr(pairs), B, self.Hmax, self.Wmax,
                                                None, ptr(self.occ[0]), ptr(self.occ[1]), ptr(self.occ_counts), e.stream()),
                   "inference_occlusion")
+        if self.visual:
+            bw, occ = (self.out_flow_bw, self.occ[0]) if self.seq_bidir else (None, None)
+            check(L.unflow_sequence_visual(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.H, self.W,
+                                           ptr(self.out_flow), ptr(bw), ptr(occ), ptr(self.vis_shown), ptr(self.vis_max),
+                                           ptr(self.vis), None, e.stream()), "sequence_visual")
 
     def _launch_backward(self, f, st):
         L = _lib.lib()
@@ -915,6 +958,22 @@ class FlowEstimator:
         """Start a new clip: the next push has no previous frame (nothing is carried across reset)."""
         self._sequence_mode('reset')
         self._carry, self._clip = 0, None
+        self._max_flow = _UNSET
+
+    def _clip_max_flow(self, max_flow, what):
+        """The max_flow of the clip's flow colours: taken from the call that starts the clip (None: a maximum per pair); a later
+        call may repeat it or leave it out."""
+        if max_flow is not None:
+            max_flow = float(max_flow)
+            if not self.visual:
+                raise RuntimeError("%s: max_flow scales the flow colours; build the estimator with FlowEstimator(..., sequence=%r, "
+                                   "visual='sequence')" % (what, 'bidirectional' if self.seq_bidir else True))
+        if self._max_flow is _UNSET:
+            self._max_flow = max_flow
+        elif max_flow is not None and max_flow != self._max_flow:
+            raise ValueError("%s: max_flow belongs to the clip (%s since its first frames, now %s); reset() starts a new clip"
+                             % (what, self._max_flow, max_flow))
+        return self._max_flow
 
     def _clip_frames(self, frames, what):
         out = []
@@ -943,14 +1002,16 @@ class FlowEstimator:
             out.append(a)
         return out
 
-    def _submit_sequence(self, frames, want=('flow',), encode=False, surfaces=('u16',)):
+    def _submit_sequence(self, frames, want=('flow',), encode=False, surfaces=('u16',), max_flow=None):
         """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns (slot, valid
-        pair slots).  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ').  encode: the
-        valid pairs' PNGs — per pair the _Encoder surfaces named in `surfaces`, in that order — go through the device encode
-        path (_filter) into slot.scan; 'device': deflated there too."""
+        pair slots).  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ'; visual: 'vis').
+        encode: the valid pairs' PNGs — per pair the _Encoder surfaces named in `surfaces`, in that order; ('vis', k): picture k
+        of the pair — go through the device encode path (_filter) into slot.scan; 'device': deflated there too.  max_flow: the
+        clip's (_clip_max_flow)."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
+        max_flow = self._clip_max_flow(max_flow, 'push')
         frames = self._clip_frames(frames, 'push')
         h, w, u8 = self._clip
         slot = self._slot(self._seq_k)
@@ -962,7 +1023,7 @@ class FlowEstimator:
         for i, a in enumerate(frames):
             if not isinstance(a, torch.Tensor):
                 fr[i, :h, :w] = a
-        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8)
+        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow)
         slot.tab.numpy()[:] = tab
         with torch.cuda.device(self.dev):
             cur = torch.cuda.current_stream(self.dev)
@@ -984,8 +1045,12 @@ class FlowEstimator:
                 slot.u16_bw.copy_(self.out_u16_bw, non_blocking=True)
             if 'occ' in want:
                 slot.occ.copy_(self.occ, non_blocking=True)
+            if 'vis' in want:                     # the last two pictures exist only with both directions
+                nv = len(SequenceVisual._fields if self.seq_bidir else FlowVisual._fields)
+                slot.vis[:nv].copy_(self.vis[:nv], non_blocking=True)
             if encode:
-                self._filter(slot, [(s, i, h, w) for i in valid for s in surfaces], encode == 'device')
+                ents = [(s, i, h, w) if isinstance(s, str) else (s[0], s[1] * B + i, h, w) for i in valid for s in surfaces]
+                self._filter(slot, ents, encode == 'device')
             ev = torch.cuda.Event()
             ev.record(cur)
         slot.event = ev
@@ -1027,14 +1092,47 @@ class FlowEstimator:
             out += self._bidirectional_of(slot, valid)
         return out
 
-    def _pipeline_sequence(self, frames, want, encode=False, surfaces=('u16',)):
+    def _sequence_visual_mode(self, what):
+        self._sequence_mode(what)
+        if not self.visual:
+            raise RuntimeError("%s: a sequence estimator without pictures; build it with FlowEstimator(..., sequence=%r, "
+                               "visual='sequence')" % (what, 'bidirectional' if self.seq_bidir else True))
+
+    def _visual_of(self, slot, valid):
+        """The valid pairs of a finished visual replay as FlowVisual tuples, SequenceVisual ones with both directions."""
+        h, w, _ = self._clip
+        v = slot.vis.numpy()
+        kind = SequenceVisual if self.seq_bidir else FlowVisual
+        return [kind(*(v[k, i, :h, :w].copy() for k in range(len(kind._fields)))) for i in valid]
+
+    def push_visual(self, frames, max_flow=None):
+        """push's frames as pictures: one tuple of uint8 [h, w, 3] images per new pair (the count is push's) — visualize's
+        FlowVisual(overlay, warp_error, flow), every frame of the clip resampled once; on a sequence='bidirectional' estimator
+        SequenceVisual(overlay, warp_error, flow, flow_bw, warp_error_noc): also flow_to_color of the backward flow (its own
+        maximum) and the brightness error where the forward occlusion mask is 0, black where it is 1.
+        max_flow: the scale of the flow colours (used as max(max_flow, 1)) for the whole clip, taken from the first push after
+        reset(); None: every pair has its own maximum, as in pair mode.  Another value later in the clip: ValueError."""
+        self._sequence_visual_mode('push_visual')
+        slot, valid = self._submit_sequence(list(frames), ('vis',), max_flow=max_flow)
+        slot.wait()
+        return self._visual_of(slot, valid)
+
+    def visualize_sequence(self, frames, max_flow=None):
+        """estimate_sequence's clip as pictures: T >= 2 frames -> T - 1 tuples (push_visual's), max_flow for the whole clip."""
+        self._sequence_visual_mode('visualize_sequence')
+        out = []
+        for slot, valid in self._pipeline_sequence(frames, ('vis',), max_flow=max_flow):
+            out += self._visual_of(slot, valid)
+        return out
+
+    def _pipeline_sequence(self, frames, want, encode=False, surfaces=('u16',), max_flow=None):
         """reset, then pipelined pushes of B frames: yields (slot, valid pair slots) per replay; replay k + 1 is staged and
         queued before replay k is handed out."""
         self.reset()
         prev, total = None, 0
         for chunk in chunks(frames, self.B):
             total += len(chunk)
-            cur = self._submit_sequence(chunk, want, encode, surfaces)
+            cur = self._submit_sequence(chunk, want, encode, surfaces, max_flow)
             if prev is not None:
                 prev[0].wait()
                 yield prev
@@ -1055,15 +1153,20 @@ class FlowEstimator:
             out += [fl[i, :h, :w].copy() for i in valid]
         return out
 
-    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False):
+    def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False,
+                        visual=False, max_flow=None):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
         writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
         export ('device': unflow_deflate behind the filter launch; needs workers >= 1).
         backward: also the backward flow (frame n + 1 -> frame n), %06d_01.png / .flo; occlusion: the forward occlusion mask,
         %06d_10_occ.png (8-bit grey, 255 = occluded) — export's files, per pair in export's order (_10, _01, _10_occ).  Both need
-        an estimator built with sequence='bidirectional'."""
-        from .input import write_flo, write_kitti_flow_png, write_png_gray8
+        an estimator built with sequence='bidirectional'.
+        visual (an estimator built with visual='sequence'): after those, per pair, the 8-bit pictures of push_visual —
+        sequence_visual_files' %06d_img.png (overlay), %06d_flow.png (flow colours), %06d_diff.png (brightness error) and, on a
+        sequence='bidirectional' estimator, %06d_flow_bw.png (the backward flow's colours) and %06d_diff_noc.png (the brightness
+        error of the non-occluded pixels); max_flow: the scale of the flow colours for the whole clip (None: per pair)."""
+        from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         from .png_device import check_deflate_mode
         self._sequence_mode('export_sequence')
         on_device = check_deflate_mode(deflate, workers)
@@ -1071,16 +1174,22 @@ class FlowEstimator:
             raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
         if (backward or occlusion) and not self.seq_bidir:
             raise ValueError("export_sequence: backward / occlusion files need FlowEstimator(..., sequence='bidirectional')")
+        if visual and not self.visual:
+            raise ValueError("export_sequence: the pictures need FlowEstimator(..., sequence=%r, visual='sequence')"
+                             % ('bidirectional' if self.seq_bidir else True))
+        if max_flow is not None and not visual:
+            raise ValueError("export_sequence: max_flow scales the flow colours of the pictures; it needs visual=True")
         os.makedirs(out_dir, exist_ok=True)
         tags = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
         if workers:
             from .png_device import DeviceFileWriter, flo_file_bytes
             n = 0
             surfaces = (tuple(u16 for _, u16, _ in tags) if fmt == 'png' else ()) + (('occ',) if occlusion else ())
+            surfaces += tuple(('vis', k) for k, _ in sequence_visual_files(0, self.seq_bidir)) if visual else ()
             with DeviceFileWriter(workers, level) as pool:
                 encode = ('device' if on_device else 'host') if surfaces else False
                 want = tuple(flow for _, _, flow in tags) if fmt == 'flo' else ()
-                for slot, valid in self._pipeline_sequence(frames, want, encode=encode, surfaces=surfaces):
+                for slot, valid in self._pipeline_sequence(frames, want, encode=encode, surfaces=surfaces, max_flow=max_flow):
                     h, w, _ = self._clip
                     spans = iter(slot.spans or ())
 
@@ -1097,12 +1206,15 @@ class FlowEstimator:
                                             flo_file_bytes(getattr(slot, flow).numpy()[i, :h, :w]))
                         if occlusion:
                             png('%06d_10_occ.png' % n)
+                        for _, name in sequence_visual_files(n, self.seq_bidir) if visual else ():
+                            png(name)
                         n += 1
             return list(pool.paths)
         paths = []
         want = tuple(u16 if fmt == 'png' else flow for _, u16, flow in tags) + (('occ',) if occlusion else ())
+        want += ('vis',) if visual else ()
         n = 0
-        for slot, valid in self._pipeline_sequence(frames, want):
+        for slot, valid in self._pipeline_sequence(frames, want, max_flow=max_flow):
             h, w, _ = self._clip
             for i in valid:
                 for tag, u16, flow in tags:
@@ -1115,6 +1227,10 @@ class FlowEstimator:
                 if occlusion:
                     path = os.path.join(out_dir, '%06d_10_occ.png' % n)
                     write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
+                    paths.append(path)
+                for k, name in sequence_visual_files(n, self.seq_bidir) if visual else ():
+                    path = os.path.join(out_dir, name)
+                    write_png_rgb8(path, slot.vis.numpy()[k, i, :h, :w])
                     paths.append(path)
                 n += 1
         return paths

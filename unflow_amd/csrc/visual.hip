@@ -10,6 +10,12 @@
 //                          kept as float4 rows [2][B][Hmax][Wmax] for the warp taps; and max |flow|, max |gt * mask| per sample
 //   visual_images_kernel   overlay, brightness error (image_warp's taps and tap order, csrc/image_warp.h), flow colours, and with
 //                          ground truth the KITTI error image and the ground truth's colours -> uint8 (and optionally fp32)
+// Sequence form, unflow_sequence_visual (FlowEstimator(..., sequence=..., visual='sequence')): the same pictures along a clip, driven by
+// the frame table, the pair table and the carry source of a sequence replay; a shown frame per engine row, [B + 1][Hmax][Wmax]:
+//   unflow_sequence_carry           shown row src (the previous replay's last frame) -> row 0
+//   sequence_visual_frames_kernel   staged frame j -> shown row j + 1 (every frame of the clip resampled once), the maxima of pair j
+//   sequence_visual_images_kernel   pair i = (row i, row i + 1): visual_images_kernel's three pictures, and with the backward flow
+//                                   and the forward occlusion mask its colours and the brightness error of the non-occluded pixels
 // max of non-negative floats = unsigned max of their bit patterns: an integer atomicMax, exact and independent of the order.
 // The slots clean themselves: every block of the kernel that reads a maximum takes an integer ticket when it is done, and the
 // last one zeroes the slot and the ticket for the next launch (graph replays included), as inference_output_kernel's ticket
@@ -267,6 +273,107 @@ __global__ __launch_bounds__(VIS_THREADS) void visual_images_kernel(const int* _
   release_max(max_bits + 2 * b, 2, max_bits + 2 * B + b, gridDim.x);   // every block of a sample with h > 0 gets here
 }
 
+// ------------------------------------------------------------------------------------------------ sequence form (tables)
+// The tables of one sequence replay (core/inference.py sequence_tables): frame table [B][8] at word 0, pair table [B][8] at word
+// 8B, carry source at word 16B, and at word 16B + 1 the bit pattern of a clip-wide max_flow (0: every pair has its own maximum).
+__device__ __forceinline__ unsigned clip_max_bits(const int* __restrict__ tab, int B) { return (unsigned)tab[16 * B + 1]; }
+
+// Block row j: staged frame j (frame slot j) -> shown row j + 1, each frame of the clip once; and the maxima of PAIR slot j,
+// max |flow_fw| and max |flow_bw|.  The two slots are valid independently; no maxima with a clip-wide max_flow.
+__global__ __launch_bounds__(VIS_THREADS) void sequence_visual_frames_kernel(const void* __restrict__ frames, const int* __restrict__ tab,
+                                                                             int B, int Hmax, int Wmax, int H, int W,
+                                                                             const float* __restrict__ flow_fw,
+                                                                             const float* __restrict__ flow_bw, float4* __restrict__ shown,
+                                                                             unsigned* __restrict__ max_bits) {
+  __shared__ unsigned red[VIS_THREADS / 64];
+  const int j = blockIdx.y;
+  const long plane = (long)Hmax * Wmax;
+  const FrameDesc d = load_desc(tab, j);
+  const int fh = min(max(d.h, 0), Hmax), fw = min(max(d.w, 0), Wmax);  // never past the (Hmax, Wmax) rows
+  if (fh > 0 && fw > 0) {                              // uniform per block row
+    const float sy2 = (float)H / (float)d.h, sx2 = (float)W / (float)d.w;
+    const long off = (long)j * plane * 3;
+    float4* row = shown + ((long)j + 1) * plane;
+    const int npx = fh * fw;                           // < 2^31 (the host checks Hmax * Wmax)
+    for (int p = blockIdx.x * VIS_THREADS + threadIdx.x; p < npx; p += gridDim.x * VIS_THREADS) {
+      const int y = p / fw, x = p - y * fw;
+      row[(long)y * Wmax + x] =
+          d.u8 ? shown_pixel(reinterpret_cast<const unsigned char*>(frames) + off, d, Hmax, Wmax, H, W, y, x, sy2, sx2)
+               : shown_pixel(reinterpret_cast<const float*>(frames) + off, d, Hmax, Wmax, H, W, y, x, sy2, sx2);
+    }
+  }
+  const FrameDesc pd = load_desc(tab + 8 * B, j);
+  const int h = min(max(pd.h, 0), Hmax), w = min(max(pd.w, 0), Wmax);
+  if (h == 0 || w == 0 || clip_max_bits(tab, B) != 0u) return;         // uniform per block row
+  const float2* ff = reinterpret_cast<const float2*>(flow_fw) + j * plane;
+  const float2* fb = flow_bw ? reinterpret_cast<const float2*>(flow_bw) + j * plane : nullptr;
+  float mx = 0.f, mx_bw = 0.f;
+  const int npx = h * w;
+  for (int p = blockIdx.x * VIS_THREADS + threadIdx.x; p < npx; p += gridDim.x * VIS_THREADS) {
+    const int y = p / w, x = p - y * w;
+    const long q = (long)y * Wmax + x;
+    const float2 f = ff[q];
+    mx = fmaxf(mx, fmaxf(abs_num(f.x), abs_num(f.y)));
+    if (fb) {
+      const float2 g = fb[q];
+      mx_bw = fmaxf(mx_bw, fmaxf(abs_num(g.x), abs_num(g.y)));
+    }
+  }
+  block_max_bits(mx, max_bits + 2 * j, red);
+  if (fb) block_max_bits(mx_bw, max_bits + 2 * j + 1, red);            // uniform per launch
+}
+
+// Pair i of the pair table: im1 = shown row i, im2 = shown row i + 1, flow_fw[i] -> images 0..2 with visual_images_kernel's
+// expressions; with flow_bw / occ_fw: 3 the backward flow's colours, 4 the brightness error where the pixel is not occluded.
+__global__ __launch_bounds__(VIS_THREADS) void sequence_visual_images_kernel(const int* __restrict__ tab, int B, int Hmax, int Wmax,
+                                                                             const float* __restrict__ flow_fw,
+                                                                             const float* __restrict__ flow_bw,
+                                                                             const unsigned char* __restrict__ occ_fw,
+                                                                             const float4* __restrict__ shown, unsigned* __restrict__ max_bits,
+                                                                             unsigned char* __restrict__ out_u8, float* __restrict__ out_f32) {
+  const int b = blockIdx.y;
+  const FrameDesc d = load_desc(tab + 8 * B, b);
+  const int h = min(max(d.h, 0), Hmax), w = min(max(d.w, 0), Wmax);
+  if (h == 0 || w == 0) return;
+  const long plane = (long)Hmax * Wmax;
+  const float2* fl = reinterpret_cast<const float2*>(flow_fw) + b * plane;
+  const float2* fb = flow_bw ? reinterpret_cast<const float2*>(flow_bw) + b * plane : nullptr;
+  const unsigned char* oc = flow_bw ? occ_fw + b * plane : nullptr;
+  const float4* im1 = shown + b * plane;
+  const float4* im2 = shown + ((long)b + 1) * plane;
+  const unsigned clip = clip_max_bits(tab, B);
+  const float mf = __uint_as_float(clip ? clip : max_bits[2 * b]), mf_bw = __uint_as_float(clip ? clip : max_bits[2 * b + 1]);
+  const int npx = h * w;
+  for (int p = blockIdx.x * VIS_THREADS + threadIdx.x; p < npx; p += gridDim.x * VIS_THREADS) {
+    const int y = p / w, x = p - y * w;
+    const long q = (long)y * Wmax + x;
+    const float4 a = im1[q], s = im2[q];
+    const float2 f = fl[q];
+    // image_warp(im2, flow): image_warp_fwd_kernel's taps and tap order (csrc/ops_warp.hip, flow_scale 1)
+    const IwTaps t = iw_sample(x, y, f.x * 1.0f, f.y * 1.0f, h, w, Wmax);
+    const float4 ta = im2[t.ia], tb = im2[t.ib], tc = im2[t.ic], td = im2[t.id];
+    const float3 wp = make_float3(((t.wa * ta.x + t.wb * tb.x) + t.wc * tc.x) + t.wd * td.x,
+                                  ((t.wa * ta.y + t.wb * tb.y) + t.wc * tc.y) + t.wd * td.y,
+                                  ((t.wa * ta.z + t.wb * tb.z) + t.wc * tc.z) + t.wd * td.z);
+    float3 img[N_IMAGES];
+    img[0] = make_float3((a.x * 0.5f + s.x * 0.5f) / 255.0f, (a.y * 0.5f + s.y * 0.5f) / 255.0f, (a.z * 0.5f + s.z * 0.5f) / 255.0f);
+    img[1] = make_float3(fabsf(a.x - wp.x) / 255.0f, fabsf(a.y - wp.y) / 255.0f, fabsf(a.z - wp.z) / 255.0f);
+    img[2] = wheel_color(f.x, f.y, 1.f, mf);
+    if (fb) {
+      const float2 g = fb[q];
+      img[3] = wheel_color(g.x, g.y, 1.f, mf_bw);
+      img[4] = oc[q] ? make_float3(0.f, 0.f, 0.f) : img[1];
+    }
+#pragma unroll
+    for (int k = 0; k < N_IMAGES; k++) {
+      if (k >= 3 && !fb) continue;
+      const long px = ((long)k * B + b) * plane + q;
+      put(out_f32, out_u8, px, img[k]);
+    }
+  }
+  release_max(max_bits + 2 * b, 2, max_bits + 2 * B + b, gridDim.x);   // every block of a valid pair gets here
+}
+
 // one launch dimension of the dense kernels: about four pixels per thread
 int dense_grid(long npx) { return (int)max(1L, min((npx + 4L * VIS_THREADS - 1) / (4L * VIS_THREADS), 4096L)); }
 
@@ -313,5 +420,24 @@ UNFLOW_API int unflow_inference_visual(const void* frames, const int* desc, int 
                                                      reinterpret_cast<float4*>(shown), max_bits);
   visual_images_kernel<<<grid, VIS_THREADS, 0, st>>>(desc, B, Hmax, Wmax, flow, gt_flow, gt_mask, reinterpret_cast<const float4*>(shown),
                                                      max_bits, out_u8, out_f32);
+  return launch_status();
+}
+
+UNFLOW_API int unflow_sequence_visual(const void* frames, const int* tab, int B, int Hmax, int Wmax, int H, int W, const float* flow_fw,
+                                      const float* flow_bw, const unsigned char* occ_fw, float* shown, unsigned* max_bits,
+                                      unsigned char* out_u8, float* out_f32, unflow_stream_t stream) {
+  if (!frames || !tab || !flow_fw || !shown || !max_bits || (!out_u8 && !out_f32)) return UNFLOW_ERR_NULL;
+  if ((flow_bw != nullptr) != (occ_fw != nullptr)) return UNFLOW_ERR_NULL;
+  if (B <= 0 || Hmax <= 0 || Wmax <= 0 || H <= 0 || W <= 0 || (long)Hmax * Wmax > 0x7fffffffL) return UNFLOW_ERR_SHAPE;
+  // the previous replay's last shown frame (row src) -> row 0, before the frames kernel overwrites rows [1, B]
+  const unflow_carry_buf row{shown, (long)Hmax * Wmax, 16, 16};
+  const int status = unflow_sequence_carry(&row, 1, tab + 16 * B, B, stream);
+  if (status != UNFLOW_OK) return status;
+  const hipStream_t st = as_stream(stream);
+  const dim3 grid(unflow_inference_output_blocks(Hmax, Wmax), B);
+  sequence_visual_frames_kernel<<<grid, VIS_THREADS, 0, st>>>(frames, tab, B, Hmax, Wmax, H, W, flow_fw, flow_bw,
+                                                              reinterpret_cast<float4*>(shown), max_bits);
+  sequence_visual_images_kernel<<<grid, VIS_THREADS, 0, st>>>(tab, B, Hmax, Wmax, flow_fw, flow_bw, occ_fw,
+                                                              reinterpret_cast<const float4*>(shown), max_bits, out_u8, out_f32);
   return launch_status();
 }

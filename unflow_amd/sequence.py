@@ -2,7 +2,7 @@
 once (core/inference.FlowEstimator(..., sequence=True)).
 
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
-                                  [--output_backward] [--occlusion]
+                                  [--output_backward] [--occlusion] [--visual] [--max_flow F]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -10,7 +10,9 @@ experiment's config and latest checkpoint are found as python -m unflow_amd.eval
 %06d_10.png (KITTI 16-bit flow) or, with --flo, %06d_10.flo — with --workers N (N >= 1) through the device encode path (DESIGN 7.11; --level L);
 the default and --host_encode: the host's writers.  --output_backward adds the backward flow of every pair (%06d_01.png / .flo),
 --occlusion its forward occlusion mask (%06d_10_occ.png); either one runs both directions along the clip
-(FlowEstimator(..., sequence='bidirectional'))."""
+(FlowEstimator(..., sequence='bidirectional')).  --visual adds the pictures of every pair: %06d_img.png,
+%06d_flow.png, %06d_diff.png and, where both directions run, %06d_flow_bw.png and %06d_diff_noc.png; --max_flow F colours the
+whole clip with one scale instead of every pair with its own maximum."""
 import argparse
 import os
 import sys
@@ -97,6 +99,11 @@ def parser():
                     help='also the backward flow of every pair (frame n + 1 -> frame n): %%06d_01.png / .flo')
     ap.add_argument('--occlusion', action='store_true',
                     help='also the forward-backward occlusion mask of every pair: %%06d_10_occ.png (255 = occluded)')
+    ap.add_argument('--visual', action='store_true',
+                    help='also the pictures of every pair: %%06d_img.png (overlay), %%06d_flow.png (flow colours), %%06d_diff.png '
+                         '(brightness error); with --output_backward or --occlusion also %%06d_flow_bw.png and %%06d_diff_noc.png')
+    ap.add_argument('--max_flow', type=float, default=None, metavar='F',
+                    help='with --visual: one scale of the flow colours for the whole clip (default: every pair its own maximum)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -112,6 +119,10 @@ def parse_args(argv=None):
     check_encode_flags(ap, a)
     if a.batch <= 0:
         ap.error("--batch must be positive")
+    if a.max_flow is not None and not a.visual:
+        ap.error("--max_flow scales the flow colours of the pictures: it needs --visual")
+    if a.max_flow is not None and not a.max_flow > 0:
+        ap.error("--max_flow must be positive")
     if a.net_size[0] % 64 or a.net_size[1] % 64 or min(a.net_size) <= 0:
         ap.error("--net_size: H and W must be positive multiples of 64")
     if not os.path.isdir(a.frames):
@@ -142,14 +153,16 @@ def main(argv=None):
     convert_input_strings(params, config_dict(a.config).get('dirs', {}))
     params.update(config.get('train_kitti', {}))
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
-                                        sequence='bidirectional' if (a.output_backward or a.occlusion) else True)
+                                        sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
+                                        visual='sequence' if a.visual else False)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
     try:
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
-                                    deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion)
+                                    deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion, visual=a.visual,
+                                    max_flow=a.max_flow)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))
