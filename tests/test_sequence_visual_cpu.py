@@ -57,6 +57,48 @@ def test_sequence_visual_files_names_and_order():
     assert SequenceVisual._fields[:3] == ('overlay', 'warp_error', 'flow')
 
 
+_PICTURES = {       # what follows the flow files of a pair: (index into the picture surface, tag), as the docstrings list them
+    'none': [],
+    'pair': [(0, 'img'), (2, 'flow'), (1, 'diff')],
+    'pair_gt': [(0, 'img'), (2, 'flow'), (1, 'diff'), (3, 'err'), (4, 'gt')],
+    'sequence': [(0, 'img'), (2, 'flow'), (1, 'diff')],
+    'sequence_bidir': [(0, 'img'), (2, 'flow'), (1, 'diff'), (3, 'flow_bw'), (4, 'diff_noc')],
+}
+
+
+@pytest.mark.parametrize("pictures", sorted(_PICTURES))
+@pytest.mark.parametrize("occlusion", [False, True])
+@pytest.mark.parametrize("backward", [False, True])
+@pytest.mark.parametrize("fmt", ['png', 'flo'])
+def test_pair_files_names_order_and_filter_entries(fmt, backward, occlusion, pictures):
+    """The one file plan of export / export_sequence: the names in the documented order (_10, _01, _10_occ, the pictures), a
+    .flo file never from an encode surface, and the PNGs exactly the entries the pool path asks unflow_png_filter for."""
+    from unflow_amd.core.inference import filter_entries, pair_files, sequence_visual_files, visual_files
+    n, B = 41, 3
+    pics = {'none': [], 'pair': visual_files(n, False), 'pair_gt': visual_files(n, True),
+            'sequence': sequence_visual_files(n, False), 'sequence_bidir': sequence_visual_files(n, True)}[pictures]
+    plan = pair_files(n, fmt, backward, occlusion, pics)
+    names = ['000041_10.' + fmt] + (['000041_01.' + fmt] if backward else []) + (['000041_10_occ.png'] if occlusion else [])
+    names += ['000041_%s.png' % tag for _, tag in _PICTURES[pictures]]
+    assert [name for name, _ in plan] == names
+    flows = ['flow'] + (['flow_bw'] if backward else [])
+    surfaces = {'u16', 'u16_bw', 'occ', 'vis'}
+    for name, src in plan:
+        if name.endswith('.flo'):
+            assert src[0] == 'flo' and src[1] not in surfaces and src == ('flo', flows.pop(0))
+        else:
+            assert src[0] == 'png' and src[1] in surfaces and len(src) == 3
+    rows = [(0, 90, 151), (2, 64, 128)]                      # a replay whose slot 1 holds no pair
+    want = []
+    for i, h, w in rows:
+        if fmt == 'png':
+            want += [('u16', i, h, w)] + ([('u16_bw', i, h, w)] if backward else [])
+        want += [('occ', i, h, w)] if occlusion else []
+        want += [('vis', k * B + i, h, w) for k, _ in _PICTURES[pictures]]
+    assert filter_entries(plan, rows, B) == want
+    assert filter_entries(pair_files(0, fmt, backward, occlusion, pics), rows, B) == want      # the pair number names files only
+
+
 def test_symbol_is_declared_and_exported(lib):
     txt = open(os.path.join(ROOT, "include", "unflow_hip.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)

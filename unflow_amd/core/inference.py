@@ -49,8 +49,15 @@ flag and, with sequence, still a ValueError that names this spelling).  Either s
                                    colours and the brightness error of the non-occluded pixels
 
 (push_visual, visualize_sequence, export_sequence(visual=True)); a clip-wide max_flow of the colours travels in the tables.
+
+The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
+_submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
+leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
+is the list of files of a pair, and _write_files the one loop that writes them, on the host or through the writer pool.  A new
+output is a row of output_buffers, a new file kind a row of pair_files and a branch of _write_files.
 """
 import collections
+import contextlib
 import itertools
 import os
 
@@ -89,6 +96,29 @@ SEQUENCE_VISUAL_TAGS = VISUAL_TAGS[:3] + ('flow_bw', 'diff_noc')
 def sequence_visual_files(n, bidirectional):
     """The picture files of pair n of a clip, in the order they are written: [(image of unflow_sequence_visual, file name)]."""
     return [(k, '%06d_%s.png' % (n, SEQUENCE_VISUAL_TAGS[k])) for k in (0, 2, 1) + ((3, 4) if bidirectional else ())]
+
+
+def pair_files(n, fmt, backward=False, occlusion=False, pictures=()):
+    """The files export / export_sequence write for pair n, in the order they are written — _10, _01, _10_occ, then the pictures
+    (visual_files' or sequence_visual_files' list) in their file order: [(file name, source)].  A source is
+
+        ('png', surface, k)   a PNG of image k * B + i of the encode surface of that name for row i of the replay (_Encoder; also
+                              the slot's pinned copy of it): 'u16', 'u16_bw', 'occ' with k = 0, 'vis' with the picture's index;
+        ('flo', attribute)    a .flo file of row i of that pinned flow of the slot: 'flow', 'flow_bw'.
+
+    Both back ends of FlowEstimator._write_files and the entries of the replay's unflow_png_filter launch (filter_entries) come
+    from this one list, so the span order and the file order cannot drift apart."""
+    flows = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
+    out = [('%06d_%s.%s' % (n, tag, fmt), ('png', u16, 0) if fmt == 'png' else ('flo', flow)) for tag, u16, flow in flows]
+    if occlusion:
+        out.append(('%06d_10_occ.png' % n, ('png', 'occ', 0)))
+    return out + [(name, ('png', 'vis', k)) for k, name in pictures]
+
+
+def filter_entries(files, rows, batch):
+    """_filter's entries [(surface name, image, h, w)] of the PNGs among `files` (pair_files' list of one pair; the names do not
+    matter) for every row (i, h, w) of a replay of `batch` rows, in the order the files are written."""
+    return [(src[1], src[2] * batch + i, h, w) for i, h, w in rows for _, src in files if src[0] == 'png']
 
 
 def occlusion_scores(counts):
@@ -185,6 +215,21 @@ def chunks(it, n):
         yield buf
 
 
+def output_buffers(B, Hm, Wm):
+    """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
+    and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
+    estimator has it).  Without its flag both attributes are None."""
+    return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
+            ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
+            ('sums', 'sums', (B, 2, 2), torch.float64, None),
+            ('counts', 'counts', (B, 2), torch.int32, None),
+            ('flow_bw', 'out_flow_bw', (B, Hm, Wm, 2), torch.float32, 'bidirectional'),
+            ('u16_bw', 'out_u16_bw', (B, Hm, Wm, 3), torch.int16, 'bidirectional'),
+            ('occ', 'occ', (2, B, Hm, Wm), torch.uint8, 'bidirectional'),                   # occ_fw, occ_bw
+            ('occ_counts', 'occ_counts', (B, 3), torch.int32, 'bidirectional'),
+            ('vis', 'vis', (len(VISUAL_IMAGES), B, Hm, Wm, 3), torch.uint8, 'visual'))
+
+
 class _Slot:
     """One set of pinned host buffers and the event of the last device work that read or wrote them."""
 
@@ -196,19 +241,10 @@ class _Slot:
         self.desc = pin(B, 8, dtype=torch.int32)
         self.tab = pin(16 * B + 4, dtype=torch.int32) if est.sequence else None   # sequence_tables
         self.gt_flow = self.gt_mask = None
-        self.flow = pin(B, Hm, Wm, 2)
-        self.u16 = pin(B, Hm, Wm, 3, dtype=torch.int16)
-        self.sums = pin(B, 2, 2, dtype=torch.float64)
-        self.counts = pin(B, 2, dtype=torch.int32)
-        self.flow_bw = self.u16_bw = self.occ = self.occ_counts = None
-        if est.bidirectional:
-            self.flow_bw = pin(B, Hm, Wm, 2)
-            self.u16_bw = pin(B, Hm, Wm, 3, dtype=torch.int16)
-            self.occ = pin(2, B, Hm, Wm, dtype=torch.uint8)          # occ_fw, occ_bw
-            self.occ_counts = pin(B, 3, dtype=torch.int32)
-        self.vis = pin(len(VISUAL_IMAGES), B, Hm, Wm, 3, dtype=torch.uint8) if est.visual else None
+        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm):
+            setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
-        self.pending = None
+        self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
         self.scan = self.scan_table = self.spans = None      # files through the device encode path (FlowEstimator._encoder)
         self.scan_kind = 'png'                               # what slot.scan holds per span: scanlines, or 'png_z' zlib streams
 
@@ -312,22 +348,13 @@ class FlowEstimator:
             # sequence: frame table, pair table and carry source in one buffer (sequence_tables); no ground truth
             self.tab = z(16 * B + 4, dtype=torch.int32) if self.sequence else None
             self.gt_flow, self.gt_mask = (None, None) if self.sequence else (z(2, B, Hm, Wm, 2), z(2, B, Hm, Wm))
-            self.out_flow = z(B, Hm, Wm, 2)
-            self.out_u16 = z(B, Hm, Wm, 3, dtype=torch.int16)
             nb = int(L.unflow_inference_output_blocks(Hm, Wm))
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
-            self.sums = z(B, 2, 2, dtype=torch.float64)
-            self.counts = z(B, 2, dtype=torch.int32)
-            self.out_flow_bw = self.out_u16_bw = self.occ = self.occ_counts = None
-            if self.bidirectional:
-                self.out_flow_bw = z(B, Hm, Wm, 2)
-                self.out_u16_bw = z(B, Hm, Wm, 3, dtype=torch.int16)
-                self.occ = z(2, B, Hm, Wm, dtype=torch.uint8)        # occ_fw, occ_bw
-                self.occ_counts = z(B, 3, dtype=torch.int32)
-            self.vis = self.vis_shown = self.vis_max = None
+            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm):      # out_flow, out_u16, sums, counts, ...
+                setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
+            self.vis_shown = self.vis_max = None
             if self.visual:
-                self.vis = z(len(VISUAL_IMAGES), B, Hm, Wm, 3, dtype=torch.uint8)
                 # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
                 self.vis_shown = z(B + 1, Hm, Wm, 4) if self.sequence else z(2, B, Hm, Wm, 4)
                 self.vis_max = z(3 * B, dtype=torch.int32)           # bit patterns of max |flow|, max |gt * mask|; B tickets
@@ -379,13 +406,9 @@ class FlowEstimator:
         check(L.unflow_inference_input(ptr(self.frames), ptr(self.desc), self.B, self.Hmax, self.Wmax, self.H, self.W,
                                        ptr(e.x0), e.mean_host, _lib.planes_of(self.in_planes), st), "inference_input")
         e.forward_net()
-        f = self.flow_src
-        check(L.unflow_inference_output(ptr(f), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(self.desc),
-                                        self.B, self.Hmax, self.Wmax, ptr(self.out_flow), ptr(self.out_u16), ptr(self.gt_flow),
-                                        ptr(self.gt_mask), ptr(self.partial), ptr(self.ticket), ptr(self.sums),
-                                        ptr(self.counts), st), "inference_output")
+        self._output(self.flow_src, self.desc, self.out_flow, self.out_u16, gt=True)
         if self.bidirectional:
-            self._launch_backward(f, st)
+            self._launch_backward()
         if self.visual:
             check(L.unflow_inference_visual(ptr(self.frames), ptr(self.desc), self.B, self.Hmax, self.Wmax, self.H, self.W,
                                             ptr(self.out_flow), ptr(self.gt_flow), ptr(self.gt_mask), ptr(self.vis_shown),
@@ -400,35 +423,42 @@ class FlowEstimator:
         e.sequence_carry(self.tab[16 * B:])
         e.sequence_input(self.frames, self.tab, self.Hmax, self.Wmax)
         e.forward_net()
-        f = self.flow_src
         pairs = self.tab[8 * B:]
-        outs = [(f, self.out_flow, self.out_u16)]
         if self.seq_bidir:
-            fw, bw = e.fw_bw(f)
-            outs = [(fw, self.out_flow, self.out_u16), (bw, self.out_flow_bw, self.out_u16_bw)]
-        for src, flow, u16 in outs:
-            check(L.unflow_inference_output(ptr(src), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(pairs), B,
-                                            self.Hmax, self.Wmax, ptr(flow), ptr(u16), None, None, None, None, None, None,
-                                            e.stream()), "inference_output")
-        if self.seq_bidir:
-            check(L.unflow_inference_occlusion(ptr(self.out_flow), ptr(self.out_flow_bw), ptr(pairs), B, self.Hmax, self.Wmax,
-                                               None, ptr(self.occ[0]), ptr(self.occ[1]), ptr(self.occ_counts), e.stream()),
-                  "inference_occlusion")
+            fw, bw = e.fw_bw(self.flow_src)
+            self._output(fw, pairs, self.out_flow, self.out_u16)
+            self._output(bw, pairs, self.out_flow_bw, self.out_u16_bw)
+            self._occlusion(pairs)
+        else:
+            self._output(self.flow_src, pairs, self.out_flow, self.out_u16)
         if self.visual:
             bw, occ = (self.out_flow_bw, self.occ[0]) if self.seq_bidir else (None, None)
             check(L.unflow_sequence_visual(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.H, self.W,
                                            ptr(self.out_flow), ptr(bw), ptr(occ), ptr(self.vis_shown), ptr(self.vis_max),
                                            ptr(self.vis), None, e.stream()), "sequence_visual")
 
-    def _launch_backward(self, f, st):
-        L = _lib.lib()
-        fb = f[self.B:]
-        check(L.unflow_inference_output(ptr(fb), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W, ptr(self.desc),
-                                        self.B, self.Hmax, self.Wmax, ptr(self.out_flow_bw), ptr(self.out_u16_bw), None, None,
-                                        None, None, None, None, st), "inference_output (backward)")
-        check(L.unflow_inference_occlusion(ptr(self.out_flow), ptr(self.out_flow_bw), ptr(self.desc), self.B, self.Hmax,
-                                           self.Wmax, ptr(self.gt_mask), ptr(self.occ[0]), ptr(self.occ[1]),
-                                           ptr(self.occ_counts), st), "inference_occlusion")
+    def _launch_backward(self):
+        self._output(self.flow_src[self.B:], self.desc, self.out_flow_bw, self.out_u16_bw, what="inference_output (backward)")
+        self._occlusion(self.desc, self.gt_mask)
+
+    def _output(self, src, table, flow, u16, gt=False, what="inference_output"):
+        """unflow_inference_output on rows `src` of the engine's flow, driven by `table` (the descriptor table or the pair
+        table): the frame-size flow and its 16-bit encoding.  gt: also scored against the staged ground truth (sums, counts);
+        only the forward rows of a pair estimator are."""
+        f = self.flow_src
+        scoring = [None] * 6
+        if gt:
+            scoring = [ptr(t) for t in (self.gt_flow, self.gt_mask, self.partial, self.ticket, self.sums, self.counts)]
+        check(_lib.lib().unflow_inference_output(ptr(src), f.shape[1], f.shape[2], _lib.cf(FLOW_SCALE * 4), self.H, self.W,
+                                                 ptr(table), self.B, self.Hmax, self.Wmax, ptr(flow), ptr(u16), *scoring,
+                                                 self.engine.stream()), what)
+
+    def _occlusion(self, table, gt_mask=None):
+        """unflow_inference_occlusion on the two frame-size flows: both masks; with KITTI's mask (pair mode), the counts."""
+        check(_lib.lib().unflow_inference_occlusion(ptr(self.out_flow), ptr(self.out_flow_bw), ptr(table), self.B, self.Hmax,
+                                                    self.Wmax, None if gt_mask is None else ptr(gt_mask), ptr(self.occ[0]),
+                                                    ptr(self.occ[1]), ptr(self.occ_counts), self.engine.stream()),
+              "inference_occlusion")
 
     def _run(self):
         e = self.engine
@@ -566,8 +596,7 @@ class FlowEstimator:
 
     def _submit(self, k, examples, staged=None, nmaps=0, want=('flow',), device_batch=None, files=None):
         """Stage batch k into its slot, copy it in, run, and queue the copies back; returns the slot.  device_batch: (batch,
-        n) — the first n examples of a batch of device tensors instead of `examples`.  files: a function (shapes, nmaps) ->
-        _filter's entries — the scanlines of those files come back in slot.scan instead of the raw outputs."""
+        n) — the first n examples of a batch of device tensors instead of `examples`.  want, files: _replay's."""
         slot = self._slot(k)
         slot.wait()                               # the last replay that read this slot's buffers (and its copies back) is done
         if device_batch is not None:
@@ -575,7 +604,6 @@ class FlowEstimator:
         else:
             shapes, nbytes = self._stage(slot, examples, staged, nmaps)
         with torch.cuda.device(self.dev):
-            cur = torch.cuda.current_stream(self.dev)
             if device_batch is None:
                 self.desc.copy_(slot.desc, non_blocking=True)
                 self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
@@ -583,66 +611,101 @@ class FlowEstimator:
                     gf, gm = slot.gt(self)
                     self.gt_flow[:nmaps].copy_(gf[:nmaps], non_blocking=True)
                     self.gt_mask[:nmaps].copy_(gm[:nmaps], non_blocking=True)
-            self._run()
-            if 'flow' in want:
-                slot.flow.copy_(self.out_flow, non_blocking=True)
-            if 'u16' in want:
-                slot.u16.copy_(self.out_u16, non_blocking=True)
-            if nmaps:
-                slot.sums.copy_(self.sums, non_blocking=True)
-                slot.counts.copy_(self.counts, non_blocking=True)
-            if 'flow_bw' in want:
-                slot.flow_bw.copy_(self.out_flow_bw, non_blocking=True)
-            if 'u16_bw' in want:
-                slot.u16_bw.copy_(self.out_u16_bw, non_blocking=True)
-            if 'occ' in want:
-                slot.occ.copy_(self.occ, non_blocking=True)
-            if 'occ_counts' in want and nmaps == 2:
-                slot.occ_counts.copy_(self.occ_counts, non_blocking=True)
-            if 'vis' in want:                     # the error image and the gt colours exist only with ground truth
-                nv = len(VISUAL_IMAGES) if nmaps else len(FlowVisual._fields)
-                slot.vis[:nv].copy_(self.vis[:nv], non_blocking=True)
-            if files is not None:
-                self._filter(slot, files(shapes, nmaps), getattr(files, 'deflate', False))
-            ev = torch.cuda.Event()
-            ev.record(cur)
-        slot.event = ev
-        slot.pending = (shapes, nmaps)
+            return self._replay(slot, [(i, h, w) for i, (h, w) in enumerate(shapes)], nmaps, want, files)
+
+    def _num_pictures(self, nmaps):
+        """How many of the pictures a replay draws: the last two exist only with ground truth (pair mode) or with both
+        directions (sequence mode)."""
+        return len(VISUAL_IMAGES) if nmaps or self.seq_bidir else len(FlowVisual._fields)
+
+    def _copy_back(self, slot, want, nmaps):
+        """Queue the copies of the outputs named in `want` into the slot's pinned buffers.  The scores come back whenever ground
+        truth was staged, the occlusion counts only when it had two maps."""
+        special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
+        nv = self._num_pictures(nmaps)
+        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax):
+            if special.get(name, name in want):
+                dst, src = getattr(slot, name), getattr(self, attr)
+                if name == 'vis':
+                    dst, src = dst[:nv], src[:nv]
+                dst.copy_(src, non_blocking=True)
+
+    def _replay(self, slot, rows, nmaps, want, files):
+        """What every replay ends with, once its inputs are staged and their copies queued: run, queue the copies back, the files'
+        scanlines (_filter), and record the slot's event behind the last of them.  rows: [(slot row i, h, w), ...] of the
+        replay's pairs — with nmaps, slot.pending, all the caller of a finished replay needs to know about it.  files: None, or
+        (a function (rows, nmaps) -> _filter's entries, deflate) — the scanlines of those files come back in slot.scan."""
+        self._run()
+        self._copy_back(slot, want, nmaps)
+        if files is not None:
+            self._filter(slot, files[0](rows, nmaps), files[1])
+        slot.event = torch.cuda.Event()
+        slot.event.record(torch.cuda.current_stream(self.dev))
+        slot.pending = (rows, nmaps)
         return slot
 
-    def _pipeline(self, batches, staged=None, nmaps_of=lambda b: 0, want=('flow',), files=None):
-        """Yields (slot, shapes, nmaps, examples) per batch, in order; batch k + 1 is staged and queued before batch k is
-        handed to the caller, so host packing overlaps the device."""
-        prev = None
-        for k, exs in enumerate(batches):
-            nm = nmaps_of(exs)
-            slot = self._submit(k, exs, staged, nm, want, files=files)
-            if prev is not None:
-                yield self._collect(*prev)
-            prev = (slot, exs)
-        if prev is not None:
-            yield self._collect(*prev)
-
     @staticmethod
-    def _collect(slot, exs):
-        slot.wait()
-        shapes, nmaps = slot.pending
-        return slot, shapes, nmaps, exs
+    def _one_ahead(submitted):
+        """Yields (slot, rows, nmaps) of every replay of `submitted` (an iterator that submits a replay per step and yields its
+        slot), in order and finished; replay k + 1 is staged and queued before replay k is handed to the caller, so host
+        packing overlaps the device."""
+        def finished(slot):
+            slot.wait()
+            return (slot,) + slot.pending
+        prev = None
+        for slot in submitted:
+            if prev is not None:
+                yield finished(prev)
+            prev = slot
+        if prev is not None:
+            yield finished(prev)
+
+    def _pipeline(self, batches, staged=None, nmaps_of=lambda b: 0, want=('flow',), files=None):
+        """_one_ahead over batches of host examples."""
+        return self._one_ahead(self._submit(k, exs, staged, nmaps_of(exs), want, files=files) for k, exs in enumerate(batches))
 
     # ------------------------------------------------------------------------------------------ public API
-    def _pair_mode(self, what):
-        if self.sequence:
-            raise RuntimeError("%s: a sequence estimator takes the frames of a clip (push, estimate_sequence, "
-                               "export_sequence); build a pair estimator without sequence=True" % what)
-
-    def _sequence_mode(self, what):
-        if not self.sequence:
-            raise RuntimeError("%s: a pair estimator; build it with FlowEstimator(..., sequence=True)" % what)
-
-    def _sequence_bidir_mode(self, what):
-        if not self.seq_bidir:
+    def _mode(self, what, sequence, bidirectional=False, visual=False):
+        """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
+        one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
+        if not sequence:
+            if self.sequence:
+                raise RuntimeError("%s: a sequence estimator takes the frames of a clip (push, estimate_sequence, "
+                                   "export_sequence); build a pair estimator without sequence=True" % what)
+            if bidirectional and not self.bidirectional:
+                raise RuntimeError("%s: a one-direction estimator; build it with FlowEstimator(..., bidirectional=True)" % what)
+            if visual and not self.visual:
+                raise RuntimeError("%s: an estimator without pictures; build it with FlowEstimator(..., visual=True)" % what)
+            return
+        if bidirectional and not self.seq_bidir:
             raise RuntimeError("%s: %s; build it with FlowEstimator(..., sequence='bidirectional')"
                                % (what, "a one-direction sequence estimator" if self.sequence else "a pair estimator"))
+        if not self.sequence:
+            raise RuntimeError("%s: a pair estimator; build it with FlowEstimator(..., sequence=True)" % what)
+        if visual and not self.visual:
+            raise RuntimeError("%s: a sequence estimator without pictures; build it with %s" % (what, self._visual_spelling()))
+
+    def _visual_spelling(self):
+        """How to build this sequence estimator with pictures, for the messages that ask for it."""
+        return "FlowEstimator(..., sequence=%r, visual='sequence')" % ('bidirectional' if self.seq_bidir else True)
+
+    @staticmethod
+    def _flows_of(slot, rows):
+        """The rows of a finished replay as [h, w, 2] float32 flows (copies: the slot's buffers are overwritten two replays on)."""
+        return [slot.flow.numpy()[i, :h, :w].copy() for i, h, w in rows]
+
+    @staticmethod
+    def _bidirectional_of(slot, rows):
+        """The rows of a finished bidirectional replay as BidirectionalFlow tuples."""
+        fl, fb, oc = slot.flow.numpy(), slot.flow_bw.numpy(), slot.occ.numpy()
+        return [BidirectionalFlow(fl[i, :h, :w].copy(), fb[i, :h, :w].copy(), oc[0, i, :h, :w].astype(bool),
+                                  oc[1, i, :h, :w].astype(bool)) for i, h, w in rows]
+
+    @staticmethod
+    def _visual_of(slot, rows, kind=FlowVisual):
+        """The rows of a finished visual replay as tuples of pictures: FlowVisual, or SequenceVisual with both directions."""
+        v = slot.vis.numpy()
+        return [kind(*(v[k, i, :h, :w].copy() for k in range(len(kind._fields)))) for i, h, w in rows]
 
     @staticmethod
     def _pairs(frames1, frames2, what):
@@ -662,27 +725,21 @@ class FlowEstimator:
     def estimate(self, frames1, frames2):
         """Flow of every pair (frames1[i] -> frames2[i]): frames [h_i, w_i, 3] uint8 or float32 in [0, 255], any size up to
         max_frame (both frames of a pair the same size).  Returns a list of [h_i, w_i, 2] float32 arrays."""
-        self._pair_mode('estimate')
+        self._mode('estimate', sequence=False)
         exs = self._pairs(frames1, frames2, 'estimate')
         out = []
-        for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B)):
-            fl = slot.flow.numpy()
-            out += [fl[i, :h, :w].copy() for i, (h, w) in enumerate(shapes)]
+        for slot, rows, _ in self._pipeline(chunks(exs, self.B)):
+            out += self._flows_of(slot, rows)
         return out
 
     def estimate_bidirectional(self, frames1, frames2):
         """estimate's pairs in both directions: one BidirectionalFlow(flow_fw, flow_bw, occ_fw, occ_bw) per pair — the flows
         [h_i, w_i, 2] float32 (flow_fw = estimate's flow), the masks [h_i, w_i] bool: losses.occlusion(flow_fw, flow_bw)."""
-        self._pair_mode('estimate_bidirectional')
-        if not self.bidirectional:
-            raise RuntimeError("estimate_bidirectional: a one-direction estimator; build it with FlowEstimator(..., "
-                               "bidirectional=True)")
+        self._mode('estimate_bidirectional', sequence=False, bidirectional=True)
         exs = self._pairs(frames1, frames2, 'estimate_bidirectional')
         out = []
-        for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B), want=('flow', 'flow_bw', 'occ')):
-            fl, fb, oc = slot.flow.numpy(), slot.flow_bw.numpy(), slot.occ.numpy()
-            out += [BidirectionalFlow(fl[i, :h, :w].copy(), fb[i, :h, :w].copy(), oc[0, i, :h, :w].astype(bool),
-                                      oc[1, i, :h, :w].astype(bool)) for i, (h, w) in enumerate(shapes)]
+        for slot, rows, _ in self._pipeline(chunks(exs, self.B), want=('flow', 'flow_bw', 'occ')):
+            out += self._bidirectional_of(slot, rows)
         return out
 
     def visualize(self, frames1, frames2):
@@ -690,14 +747,11 @@ class FlowEstimator:
         eval_gui.py:199-204 (:160-165): (0.5 im1 + 0.5 im2) / 255 and |im1 - image_warp(im2, flow)| / 255 on the frames as the
         reference shows them (resized to the network's size and back), and flow_to_color(flow) with max_flow per pair; bytes
         rounded to nearest."""
-        self._pair_mode('visualize')
-        if not self.visual:
-            raise RuntimeError("visualize: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
+        self._mode('visualize', sequence=False, visual=True)
         exs = self._pairs(frames1, frames2, 'visualize')
         out = []
-        for slot, shapes, _, _ in self._pipeline(chunks(exs, self.B), want=('vis',)):
-            v = slot.vis.numpy()
-            out += [FlowVisual(*(v[k, i, :h, :w].copy() for k in range(3))) for i, (h, w) in enumerate(shapes)]
+        for slot, rows, _ in self._pipeline(chunks(exs, self.B), want=('vis',)):
+            out += self._visual_of(slot, rows)
         return out
 
     def pictures(self, batch_iter, num=None, scanlines=False, deflate='host'):
@@ -709,22 +763,21 @@ class FlowEstimator:
         deflate='device' (with scanlines): the bytes are the scanlines' finished zlib stream instead (unflow_deflate), and
         'scanlines_kind' is 'png_z', the kind to submit them as ('png' otherwise)."""
         from .png_device import check_deflate_mode
-        self._pair_mode('pictures')
+        self._mode('pictures', sequence=False)
         on_device = check_deflate_mode(deflate)
         if on_device and not scanlines:
             raise ValueError("pictures: deflate='device' codes the scanlines; it needs scanlines=True")
-        if not self.visual:
-            raise RuntimeError("pictures: an estimator without pictures; build it with FlowEstimator(..., visual=True)")
+        self._mode('pictures', sequence=False, visual=True)
         B, files = self.B, None
-        if scanlines:
-            def files(shapes, nmaps):
-                return [('vis', k * B + i, h, w) for i, (h, w) in enumerate(shapes) for k in range(len(VISUAL_IMAGES) if nmaps else 3)]
-            files.deflate = on_device
-        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, ('vis',), lambda exs: (len(exs[0]) - 3) // 2, files):
+        if scanlines:         # per example its pictures by index, the order of the dict below: not the order of export's files
+            def entries(rows, nmaps):
+                return [('vis', k * B + i, h, w) for i, h, w in rows for k in range(self._num_pictures(nmaps))]
+            files = (entries, on_device)
+        for slot, rows, nmaps in self._staged_input(batch_iter, num, ('vis',), lambda exs: (len(exs[0]) - 3) // 2, files):
             v = slot.vis.numpy()
             spans = iter(slot.spans or ())
-            for i, (h, w) in enumerate(shapes):
-                ex = {name: v[k, i, :h, :w].copy() for k, name in enumerate(VISUAL_IMAGES) if k < 3 or nmaps}
+            for i, h, w in rows:
+                ex = {name: v[k, i, :h, :w].copy() for k, name in enumerate(VISUAL_IMAGES[:self._num_pictures(nmaps)])}
                 if scanlines:
                     sc, buf = {}, slot.scan.numpy()
                     for name in ex:
@@ -743,23 +796,23 @@ class FlowEstimator:
         `names` order).  num: at most that many examples.
         A bidirectional estimator on two-map input adds occlusion_scores' occ/precision, occ/recall and occ/F1 (%, pooled
         over all examples) and occ_counts (per example [tp, fp, fn])."""
-        self._pair_mode('evaluate')
+        self._mode('evaluate', sequence=False)
         names, rows, occ_rows = None, [], []
         want = ('occ_counts',) if self.bidirectional else ()
-        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, lambda exs: (len(exs[0]) - 3) // 2):
+        for slot, pairs, nmaps in self._staged_input(batch_iter, num, want, lambda exs: (len(exs[0]) - 3) // 2):
             if nmaps == 0:
                 raise ValueError("evaluate: the batches carry no ground truth (a test split); use export()")
             if names is None:
                 names = [n for m in MAP_NAMES[nmaps] for n in ('AEE/' + m, 'outliers/' + m)]
             sums, counts = slot.sums.numpy(), slot.counts.numpy()
-            for i in range(len(shapes)):
+            for i, _, _ in pairs:
                 row = []
                 for m in range(nmaps):
                     err, msk = float(sums[i, m, 0]), float(sums[i, m, 1])
                     row += [err / msk, 100.0 * float(counts[i, m]) / msk]
                 rows.append(row)
             if self.bidirectional and nmaps == 2:
-                occ_rows += [[int(v) for v in slot.occ_counts.numpy()[i]] for i in range(len(shapes))]
+                occ_rows += [[int(v) for v in slot.occ_counts.numpy()[i]] for i, _, _ in pairs]
         if not rows:
             raise ValueError("evaluate: the input yielded no examples")
         avg = np.mean(np.asarray(rows, dtype=np.float64), axis=0)
@@ -797,34 +850,31 @@ class FlowEstimator:
             t.device == torch.device('cuda', torch.cuda.current_device() if self.dev.index is None else self.dev.index)
 
     def _pipeline_device(self, batches, num, want, nmaps_of, files=None):
-        """_pipeline over batches of device tensors (DeviceEvalBatches): each is consumed as it comes, never re-chunked —
+        """_one_ahead over batches of device tensors (DeviceEvalBatches): each is consumed as it comes, never re-chunked —
         its tensors are valid only until the iterator's next next(), and batch k is staged (copies enqueued on the current
         stream) before batch k + 1 is asked for."""
-        self._dims = None
-        prev, done = None, 0
-        for k, batch in enumerate(batches):
-            if len(batch) not in (3, 5, 7):
-                raise ValueError("a batch is (im1, im2, input_shape) + 0, 1 or 2 (flow, mask) pairs; got %d arrays" % len(batch))
-            n = int(batch[0].shape[0])
-            if n > self.B:
-                raise ValueError("a device batch of %d examples for an estimator of batch %d: device batches are consumed "
-                                 "whole (build the input with batch_size <= %d)" % (n, self.B, self.B))
-            if num is not None:
-                n = min(n, int(num) - done)
-                if n <= 0:
-                    break
-            dims = tuple(int(v) for v in batch[0].shape[1:3])
-            if self._dims is None:
-                self._dims = dims
-            elif dims != tuple(self._dims):
-                raise ValueError("evaluate / export: the input's frames changed size (%s, then %s)" % (self._dims, dims))
-            slot = self._submit(k, None, dims, nmaps_of([batch]), want, device_batch=(batch, n), files=files)
-            done += n
-            if prev is not None:
-                yield self._collect(*prev)
-            prev = (slot, None)
-        if prev is not None:
-            yield self._collect(*prev)
+        def replays():
+            self._dims = None
+            done = 0
+            for k, batch in enumerate(batches):
+                if len(batch) not in (3, 5, 7):
+                    raise ValueError("a batch is (im1, im2, input_shape) + 0, 1 or 2 (flow, mask) pairs; got %d arrays" % len(batch))
+                n = int(batch[0].shape[0])
+                if n > self.B:
+                    raise ValueError("a device batch of %d examples for an estimator of batch %d: device batches are consumed "
+                                     "whole (build the input with batch_size <= %d)" % (n, self.B, self.B))
+                if num is not None:
+                    n = min(n, int(num) - done)
+                    if n <= 0:
+                        return
+                dims = tuple(int(v) for v in batch[0].shape[1:3])
+                if self._dims is None:
+                    self._dims = dims
+                elif dims != tuple(self._dims):
+                    raise ValueError("evaluate / export: the input's frames changed size (%s, then %s)" % (self._dims, dims))
+                done += n
+                yield self._submit(k, None, dims, nmaps_of([batch]), want, device_batch=(batch, n), files=files)
+        return self._one_ahead(replays())
 
     def _staged_input(self, batch_iter, num, want, nmaps_of, files=None):
         """The batches of evaluate / export / pictures: host arrays go example by example through _pipeline_staged; batches of
@@ -863,9 +913,8 @@ class FlowEstimator:
         deflate='device' (needs workers >= 1): the scanlines are deflated on the device as well (unflow_deflate,
         right behind the filter launch, outside the captured graph), only the zlib streams come back and the pool's threads form
         the chunk CRCs and write; `level` does not apply.  .flo files are not compressed and go the same way as before."""
-        from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         from .png_device import check_deflate_mode
-        self._pair_mode('export')
+        self._mode('export', sequence=False)
         on_device = check_deflate_mode(deflate, workers)
         if fmt not in ('png', 'flo'):
             raise ValueError("export: fmt must be 'png' or 'flo'")
@@ -873,90 +922,56 @@ class FlowEstimator:
             raise ValueError("export: backward / occlusion files need FlowEstimator(..., bidirectional=True)")
         if visual and not self.visual:
             raise ValueError("export: the pictures need FlowEstimator(..., visual=True)")
-        os.makedirs(out_dir, exist_ok=True)
-        paths = []
-        want = ('u16',) if fmt == 'png' else ('flow',)
-        if backward:
-            want += ('u16_bw',) if fmt == 'png' else ('flow_bw',)
-        if occlusion:
-            want += ('occ',)
-        if visual:
-            want += ('vis',)
-        n = 0
         # the ground truth is staged only for the pictures that show it
         nmaps_of = (lambda exs: (len(exs[0]) - 3) // 2) if visual else (lambda exs: 0)
-        if workers:
-            return self._export_pool(batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level,
-                                     on_device)
-        for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, nmaps_of):
-            for i, (h, w) in enumerate(shapes):
-                flows = [('10', slot.u16, slot.flow)] + ([('01', slot.u16_bw, slot.flow_bw)] if backward else [])
-                for tag, u16, flow in flows:
-                    path = os.path.join(out_dir, '%06d_%s.%s' % (n, tag, fmt))
-                    if fmt == 'png':
-                        write_kitti_flow_png(path, u16.numpy()[i, :h, :w].view(np.uint16))
-                    else:
-                        write_flo(path, flow.numpy()[i, :h, :w])
-                    paths.append(path)
-                if occlusion:
-                    path = os.path.join(out_dir, '%06d_10_occ.png' % n)
-                    write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
-                    paths.append(path)
-                if visual:
-                    vis = slot.vis.numpy()
-                    for k, name in visual_files(n, nmaps > 0):               # _img, _flow, _diff, _err, _gt
-                        path = os.path.join(out_dir, name)
-                        write_png_rgb8(path, vis[k, i, :h, :w])
-                        paths.append(path)
-                n += 1
-        return paths
 
-    def _export_pool(self, batch_iter, out_dir, fmt, num, backward, occlusion, visual, nmaps_of, workers, level, deflate=False):
-        """export through the device encode path: the file list of export's loop, each PNG as an entry of the replay's
-        unflow_png_filter launch and a job of the writer pool."""
+        def plan(n, nmaps):
+            return pair_files(n, fmt, backward, occlusion, visual_files(n, nmaps > 0) if visual else ())       # _img .. _gt
+        return self._write_files(lambda want, files: self._staged_input(batch_iter, num, want, nmaps_of, files), plan, out_dir,
+                                 workers, level, on_device)
+
+    def _write_files(self, replays, plan, out_dir, workers, level, deflate):
+        """The files of export / export_sequence, pair after pair.  plan: (pair number n, nmaps) -> pair_files' list for that
+        pair; replays: (want, files) -> the finished replays (_one_ahead's) of a pass submitted with those two.  Returns the paths
+        in the order written.
+        workers = 0: the outputs the plan names come back raw and the host writers of core/input.py write them on this thread.
+        workers >= 1: the plan's PNGs are the entries of each replay's unflow_png_filter launch (filter_entries: the same list,
+        so slot.spans is in file order), only their scanlines (deflate: zlib streams) and the .flo flows come back, and a
+        png_device.DeviceFileWriter pool finishes and writes them; every file is written when this returns."""
+        from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         from .png_device import DeviceFileWriter, flo_file_bytes
-        B = self.B
-        tags = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
-
-        def files(shapes, nmaps):
-            ents = []
-            for i, (h, w) in enumerate(shapes):
-                if fmt == 'png':
-                    ents += [(u16, i, h, w) for _, u16, _ in tags]
-                if occlusion:
-                    ents.append(('occ', i, h, w))
-                if visual:
-                    ents += [('vis', k * B + i, h, w) for k, _ in visual_files(0, nmaps > 0)]
-            return ents
-        files.deflate = deflate
-        want = tuple(flow for _, _, flow in tags) if fmt == 'flo' else ()
-        n = 0
-        with DeviceFileWriter(workers, level) as pool:
-            for slot, shapes, nmaps, _ in self._staged_input(batch_iter, num, want, nmaps_of, files):
-                spans, scan = iter(slot.spans), slot.scan.numpy()
-
-                def png(name):
-                    off, nb, h, w, depth, ctype = next(spans)
-                    pool.submit(os.path.join(out_dir, name), slot.scan_kind, (h, w, depth, ctype, scan[off:off + nb].tobytes()))
-                for i, (h, w) in enumerate(shapes):
-                    for tag, _, flow in tags:
-                        if fmt == 'png':
-                            png('%06d_%s.png' % (n, tag))
+        os.makedirs(out_dir, exist_ok=True)
+        want = tuple(src[1] for _, src in plan(0, 0) if not workers or src[0] == 'flo')
+        files = (lambda rows, nmaps: filter_entries(plan(0, nmaps), rows, self.B), deflate) if workers else None
+        pool = DeviceFileWriter(workers, level) if workers else None
+        paths, n = [], 0
+        with contextlib.nullcontext() if pool is None else pool:
+            for slot, rows, nmaps in replays(want, files):
+                spans = iter(slot.spans or ())
+                for i, h, w in rows:
+                    for name, (kind, attr, *k) in plan(n, nmaps):
+                        path = os.path.join(out_dir, name)
+                        if pool is not None and kind == 'png':
+                            off, nb, _, _, depth, ctype = next(spans)
+                            pool.submit(path, slot.scan_kind, (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
+                        elif pool is not None:
+                            pool.submit(path, 'flo', flo_file_bytes(getattr(slot, attr).numpy()[i, :h, :w]))
+                        elif kind == 'flo':
+                            write_flo(path, getattr(slot, attr).numpy()[i, :h, :w])
+                        elif attr == 'occ':
+                            write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
+                        elif attr == 'vis':
+                            write_png_rgb8(path, slot.vis.numpy()[k[0], i, :h, :w])
                         else:
-                            pool.submit(os.path.join(out_dir, '%06d_%s.flo' % (n, tag)), 'flo',
-                                        flo_file_bytes(getattr(slot, flow).numpy()[i, :h, :w]))
-                    if occlusion:
-                        png('%06d_10_occ.png' % n)
-                    if visual:
-                        for _, name in visual_files(n, nmaps > 0):
-                            png(name)
+                            write_kitti_flow_png(path, getattr(slot, attr).numpy()[i, :h, :w].view(np.uint16))
+                        paths.append(path)
                     n += 1
-        return list(pool.paths)
+        return paths
 
     # ------------------------------------------------------------------------------------------ sequence mode
     def reset(self):
         """Start a new clip: the next push has no previous frame (nothing is carried across reset)."""
-        self._sequence_mode('reset')
+        self._mode('reset', sequence=True)
         self._carry, self._clip = 0, None
         self._max_flow = _UNSET
 
@@ -966,8 +981,8 @@ class FlowEstimator:
         if max_flow is not None:
             max_flow = float(max_flow)
             if not self.visual:
-                raise RuntimeError("%s: max_flow scales the flow colours; build the estimator with FlowEstimator(..., sequence=%r, "
-                                   "visual='sequence')" % (what, 'bidirectional' if self.seq_bidir else True))
+                raise RuntimeError("%s: max_flow scales the flow colours; build the estimator with %s"
+                                   % (what, self._visual_spelling()))
         if self._max_flow is _UNSET:
             self._max_flow = max_flow
         elif max_flow is not None and max_flow != self._max_flow:
@@ -1002,12 +1017,10 @@ class FlowEstimator:
             out.append(a)
         return out
 
-    def _submit_sequence(self, frames, want=('flow',), encode=False, surfaces=('u16',), max_flow=None):
-        """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns (slot, valid
-        pair slots).  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ'; visual: 'vis').
-        encode: the valid pairs' PNGs — per pair the _Encoder surfaces named in `surfaces`, in that order; ('vis', k): picture k
-        of the pair — go through the device encode path (_filter) into slot.scan; 'device': deflated there too.  max_flow: the
-        clip's (_clip_max_flow)."""
+    def _submit_sequence(self, frames, want=('flow',), files=None, max_flow=None):
+        """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns the slot, its
+        rows the valid pair slots.  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ';
+        visual: 'vis'); files: _replay's.  max_flow: the clip's (_clip_max_flow)."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
@@ -1026,7 +1039,6 @@ class FlowEstimator:
         tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow)
         slot.tab.numpy()[:] = tab
         with torch.cuda.device(self.dev):
-            cur = torch.cuda.current_stream(self.dev)
             self.tab.copy_(slot.tab, non_blocking=True)
             if len(on_dev) < len(frames):
                 self.frames[:nbytes].copy_(slot.frames[:nbytes], non_blocking=True)
@@ -1034,76 +1046,35 @@ class FlowEstimator:
                 dv = self.frames[:nbytes].view(torch.uint8 if u8 else torch.float32).view(B, Hm, Wm, 3)
                 for i, a in on_dev:
                     dv[i, :h, :w].copy_(a, non_blocking=True)
-            self._run()
-            if 'flow' in want:
-                slot.flow.copy_(self.out_flow, non_blocking=True)
-            if 'u16' in want:
-                slot.u16.copy_(self.out_u16, non_blocking=True)
-            if 'flow_bw' in want:
-                slot.flow_bw.copy_(self.out_flow_bw, non_blocking=True)
-            if 'u16_bw' in want:
-                slot.u16_bw.copy_(self.out_u16_bw, non_blocking=True)
-            if 'occ' in want:
-                slot.occ.copy_(self.occ, non_blocking=True)
-            if 'vis' in want:                     # the last two pictures exist only with both directions
-                nv = len(SequenceVisual._fields if self.seq_bidir else FlowVisual._fields)
-                slot.vis[:nv].copy_(self.vis[:nv], non_blocking=True)
-            if encode:
-                ents = [(s, i, h, w) if isinstance(s, str) else (s[0], s[1] * B + i, h, w) for i in valid for s in surfaces]
-                self._filter(slot, ents, encode == 'device')
-            ev = torch.cuda.Event()
-            ev.record(cur)
-        slot.event = ev
-        slot.pending = ([(h, w)] * len(valid), 0)
-        return slot, valid
+            return self._replay(slot, [(i, h, w) for i in valid], 0, want, files)
+
+    def _push(self, frames, want, max_flow=None):
+        """One replay on its own: (slot, rows) once it has finished."""
+        slot = self._submit_sequence(list(frames), want, max_flow=max_flow)
+        slot.wait()
+        return slot, slot.pending[0]
 
     def push(self, frames):
         """The next 1..B frames of the clip ([h, w, 3] uint8 or float32 in [0, 255], all of the clip's size).  Returns one
         [h, w, 2] float32 flow per new pair, in order: from the frame before each new frame to it — len(frames) flows, or
         len(frames) - 1 for the first push after reset() (its first frame has no predecessor)."""
-        self._sequence_mode('push')
-        slot, valid = self._submit_sequence(list(frames))
-        slot.wait()
-        h, w, _ = self._clip
-        fl = slot.flow.numpy()
-        return [fl[i, :h, :w].copy() for i in valid]
-
-    def _bidirectional_of(self, slot, valid):
-        """The valid pairs of a finished bidirectional replay as BidirectionalFlow tuples."""
-        h, w, _ = self._clip
-        fl, fb, oc = slot.flow.numpy(), slot.flow_bw.numpy(), slot.occ.numpy()
-        return [BidirectionalFlow(fl[i, :h, :w].copy(), fb[i, :h, :w].copy(), oc[0, i, :h, :w].astype(bool),
-                                  oc[1, i, :h, :w].astype(bool)) for i in valid]
+        self._mode('push', sequence=True)
+        return self._flows_of(*self._push(frames, ('flow',)))
 
     def push_bidirectional(self, frames):
         """push on a sequence='bidirectional' estimator, both directions: one BidirectionalFlow(flow_fw, flow_bw, occ_fw, occ_bw)
         per new pair (n, n + 1) — flow_fw from frame n to n + 1 (push's flow), flow_bw from frame n + 1 to n, the masks
         losses.occlusion of the two, as estimate_bidirectional returns them.  The count is push's."""
-        self._sequence_bidir_mode('push_bidirectional')
-        slot, valid = self._submit_sequence(list(frames), ('flow', 'flow_bw', 'occ'))
-        slot.wait()
-        return self._bidirectional_of(slot, valid)
+        self._mode('push_bidirectional', sequence=True, bidirectional=True)
+        return self._bidirectional_of(*self._push(frames, ('flow', 'flow_bw', 'occ')))
 
     def estimate_sequence_bidirectional(self, frames):
         """estimate_sequence in both directions: T >= 2 frames -> T - 1 BidirectionalFlow tuples (push_bidirectional's)."""
-        self._sequence_bidir_mode('estimate_sequence_bidirectional')
+        self._mode('estimate_sequence_bidirectional', sequence=True, bidirectional=True)
         out = []
-        for slot, valid in self._pipeline_sequence(frames, ('flow', 'flow_bw', 'occ')):
-            out += self._bidirectional_of(slot, valid)
+        for slot, rows, _ in self._pipeline_sequence(frames, ('flow', 'flow_bw', 'occ')):
+            out += self._bidirectional_of(slot, rows)
         return out
-
-    def _sequence_visual_mode(self, what):
-        self._sequence_mode(what)
-        if not self.visual:
-            raise RuntimeError("%s: a sequence estimator without pictures; build it with FlowEstimator(..., sequence=%r, "
-                               "visual='sequence')" % (what, 'bidirectional' if self.seq_bidir else True))
-
-    def _visual_of(self, slot, valid):
-        """The valid pairs of a finished visual replay as FlowVisual tuples, SequenceVisual ones with both directions."""
-        h, w, _ = self._clip
-        v = slot.vis.numpy()
-        kind = SequenceVisual if self.seq_bidir else FlowVisual
-        return [kind(*(v[k, i, :h, :w].copy() for k in range(len(kind._fields)))) for i in valid]
 
     def push_visual(self, frames, max_flow=None):
         """push's frames as pictures: one tuple of uint8 [h, w, 3] images per new pair (the count is push's) — visualize's
@@ -1112,45 +1083,37 @@ class FlowEstimator:
         maximum) and the brightness error where the forward occlusion mask is 0, black where it is 1.
         max_flow: the scale of the flow colours (used as max(max_flow, 1)) for the whole clip, taken from the first push after
         reset(); None: every pair has its own maximum, as in pair mode.  Another value later in the clip: ValueError."""
-        self._sequence_visual_mode('push_visual')
-        slot, valid = self._submit_sequence(list(frames), ('vis',), max_flow=max_flow)
-        slot.wait()
-        return self._visual_of(slot, valid)
+        self._mode('push_visual', sequence=True, visual=True)
+        return self._visual_of(*self._push(frames, ('vis',), max_flow), SequenceVisual if self.seq_bidir else FlowVisual)
 
     def visualize_sequence(self, frames, max_flow=None):
         """estimate_sequence's clip as pictures: T >= 2 frames -> T - 1 tuples (push_visual's), max_flow for the whole clip."""
-        self._sequence_visual_mode('visualize_sequence')
+        self._mode('visualize_sequence', sequence=True, visual=True)
         out = []
-        for slot, valid in self._pipeline_sequence(frames, ('vis',), max_flow=max_flow):
-            out += self._visual_of(slot, valid)
+        for slot, rows, _ in self._pipeline_sequence(frames, ('vis',), max_flow=max_flow):
+            out += self._visual_of(slot, rows, SequenceVisual if self.seq_bidir else FlowVisual)
         return out
 
-    def _pipeline_sequence(self, frames, want, encode=False, surfaces=('u16',), max_flow=None):
-        """reset, then pipelined pushes of B frames: yields (slot, valid pair slots) per replay; replay k + 1 is staged and
-        queued before replay k is handed out."""
+    def _pipeline_sequence(self, frames, want, files=None, max_flow=None):
+        """reset, then _one_ahead over pushes of B frames."""
         self.reset()
-        prev, total = None, 0
-        for chunk in chunks(frames, self.B):
-            total += len(chunk)
-            cur = self._submit_sequence(chunk, want, encode, surfaces, max_flow)
-            if prev is not None:
-                prev[0].wait()
-                yield prev
-            prev = cur
-        if total < 2:
-            raise ValueError("a clip needs at least two frames, got %d" % total)
-        prev[0].wait()
-        yield prev
+
+        def replays():
+            total = 0
+            for chunk in chunks(frames, self.B):
+                total += len(chunk)
+                yield self._submit_sequence(chunk, want, files, max_flow)
+            if total < 2:                         # raised before the only replay, which holds no pair, would be handed out
+                raise ValueError("a clip needs at least two frames, got %d" % total)
+        yield from self._one_ahead(replays())
 
     def estimate_sequence(self, frames):
         """Flow along a clip: frames = T >= 2 frames (a list or an iterator; [h, w, 3] uint8 or float32 in [0, 255], one size)
         -> T - 1 flows [h, w, 2] float32, frame n -> frame n + 1."""
-        self._sequence_mode('estimate_sequence')
+        self._mode('estimate_sequence', sequence=True)
         out = []
-        for slot, valid in self._pipeline_sequence(frames, ('flow',)):
-            h, w, _ = self._clip
-            fl = slot.flow.numpy()
-            out += [fl[i, :h, :w].copy() for i in valid]
+        for slot, rows, _ in self._pipeline_sequence(frames, ('flow',)):
+            out += self._flows_of(slot, rows)
         return out
 
     def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False,
@@ -1166,71 +1129,19 @@ class FlowEstimator:
         sequence_visual_files' %06d_img.png (overlay), %06d_flow.png (flow colours), %06d_diff.png (brightness error) and, on a
         sequence='bidirectional' estimator, %06d_flow_bw.png (the backward flow's colours) and %06d_diff_noc.png (the brightness
         error of the non-occluded pixels); max_flow: the scale of the flow colours for the whole clip (None: per pair)."""
-        from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         from .png_device import check_deflate_mode
-        self._sequence_mode('export_sequence')
+        self._mode('export_sequence', sequence=True)
         on_device = check_deflate_mode(deflate, workers)
         if fmt not in ('png', 'flo'):
             raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
         if (backward or occlusion) and not self.seq_bidir:
             raise ValueError("export_sequence: backward / occlusion files need FlowEstimator(..., sequence='bidirectional')")
         if visual and not self.visual:
-            raise ValueError("export_sequence: the pictures need FlowEstimator(..., sequence=%r, visual='sequence')"
-                             % ('bidirectional' if self.seq_bidir else True))
+            raise ValueError("export_sequence: the pictures need %s" % self._visual_spelling())
         if max_flow is not None and not visual:
             raise ValueError("export_sequence: max_flow scales the flow colours of the pictures; it needs visual=True")
-        os.makedirs(out_dir, exist_ok=True)
-        tags = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
-        if workers:
-            from .png_device import DeviceFileWriter, flo_file_bytes
-            n = 0
-            surfaces = (tuple(u16 for _, u16, _ in tags) if fmt == 'png' else ()) + (('occ',) if occlusion else ())
-            surfaces += tuple(('vis', k) for k, _ in sequence_visual_files(0, self.seq_bidir)) if visual else ()
-            with DeviceFileWriter(workers, level) as pool:
-                encode = ('device' if on_device else 'host') if surfaces else False
-                want = tuple(flow for _, _, flow in tags) if fmt == 'flo' else ()
-                for slot, valid in self._pipeline_sequence(frames, want, encode=encode, surfaces=surfaces, max_flow=max_flow):
-                    h, w, _ = self._clip
-                    spans = iter(slot.spans or ())
 
-                    def png(name):
-                        off, nb, _, _, depth, ctype = next(spans)
-                        pool.submit(os.path.join(out_dir, name), slot.scan_kind,
-                                    (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
-                    for i in valid:
-                        for tag, _, flow in tags:
-                            if fmt == 'png':
-                                png('%06d_%s.png' % (n, tag))
-                            else:
-                                pool.submit(os.path.join(out_dir, '%06d_%s.flo' % (n, tag)), 'flo',
-                                            flo_file_bytes(getattr(slot, flow).numpy()[i, :h, :w]))
-                        if occlusion:
-                            png('%06d_10_occ.png' % n)
-                        for _, name in sequence_visual_files(n, self.seq_bidir) if visual else ():
-                            png(name)
-                        n += 1
-            return list(pool.paths)
-        paths = []
-        want = tuple(u16 if fmt == 'png' else flow for _, u16, flow in tags) + (('occ',) if occlusion else ())
-        want += ('vis',) if visual else ()
-        n = 0
-        for slot, valid in self._pipeline_sequence(frames, want, max_flow=max_flow):
-            h, w, _ = self._clip
-            for i in valid:
-                for tag, u16, flow in tags:
-                    path = os.path.join(out_dir, '%06d_%s.%s' % (n, tag, fmt))
-                    if fmt == 'png':
-                        write_kitti_flow_png(path, getattr(slot, u16).numpy()[i, :h, :w].view(np.uint16))
-                    else:
-                        write_flo(path, getattr(slot, flow).numpy()[i, :h, :w])
-                    paths.append(path)
-                if occlusion:
-                    path = os.path.join(out_dir, '%06d_10_occ.png' % n)
-                    write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
-                    paths.append(path)
-                for k, name in sequence_visual_files(n, self.seq_bidir) if visual else ():
-                    path = os.path.join(out_dir, name)
-                    write_png_rgb8(path, slot.vis.numpy()[k, i, :h, :w])
-                    paths.append(path)
-                n += 1
-        return paths
+        def plan(n, nmaps):
+            return pair_files(n, fmt, backward, occlusion, sequence_visual_files(n, self.seq_bidir) if visual else ())
+        return self._write_files(lambda want, files: self._pipeline_sequence(frames, want, files, max_flow), plan, out_dir,
+                                 workers, level, on_device)
