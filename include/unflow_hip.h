@@ -634,6 +634,37 @@ int unflow_sequence_carry(const unflow_carry_buf* bufs, int n_bufs, const int* s
 int unflow_sequence_mirror(const unflow_carry_buf* bufs, int n_bufs, int src0, int dst0, int n, int max_row,
                            unflow_stream_t stream);
 
+/* Tracks along a clip (FlowEstimator(..., sequence=True | 'bidirectional', track=...); csrc/track.hip): advance N
+ * tracks through the valid pairs of one sequence replay, in slot order, one launch.  A track is a pixel (x, y) of the clip's first
+ * frame (its anchor), the displacement disp = (u, v) to where it is now, and alive: still inside the frame and never occluded.
+ * flow_fw [B][Hmax][Wmax][2]: the frame-size forward flow per pair slot (unflow_inference_output); occ_fw [B][Hmax][Wmax] uint8
+ * (unflow_inference_occlusion's forward mask) or NULL: the one-direction estimator, no track is ever occluded.  tab: the DEVICE
+ * int32 tables of the replay (sequence_tables): the pair table [B][8] at word 8B (a slot with h = 0, or with h > Hmax or w > Wmax,
+ * is not a pair), the carry source at word 16B, and at words 16B + 2 and 16B + 3 the grid stride S and the number of tracks N —
+ * read on the device like the carry source, so a captured graph keeps addresses only.  N above Ncap is clamped to Ncap.
+ * Anchors: anchors [N][2] int32 (x, y) in DEVICE memory; or NULL: the dense grid of stride S over a slot's (h, w), track n at
+ * (S * (n % gw), S * (n / gw)) with gw = ceil(w / S) (S < 1: nothing is tracked, nothing is written).
+ * State, Ncap tracks, kept by the caller from one replay of a clip to the next and updated in place: disp [Ncap][2] fp32, alive
+ * [Ncap] uint8.  Carry source 0 (a clip's first replay): every track starts from disp = 0, alive = 1, whatever the state holds,
+ * and is then advanced; above 0: from the state.  So the state needs no initialisation, and an estimator's first replay ever,
+ * which runs the launch twice with carry source 0 (the eager pass, then the captured graph's first replay), gives what one run
+ * gives.  One step, for pair slot i of size (h, w), on an alive track (a dead one keeps disp and alive = 0 for good):
+ *   an anchor outside [0, w) x [0, h) ends the track;
+ *   t = image_warp's taps of (x, y) displaced by (u, v), clamped to (h, w), rows Wmax apart (csrc/image_warp.h: fp32 floorf);
+ *   with occ_fw: occluded — occ[ia], or yw > 0 and occ[ib], or xw > 0 and occ[ic], or xw > 0 and yw > 0 and occ[id], i.e. any tap of
+ *     non-zero weight — ends the track where it is: disp is not advanced;
+ *   disp += ((wa*a + wb*b) + wc*c) + wd*d per component, a..d slot i's flow at the taps, every product and sum rounded on its own
+ *     (unflow_image_warp_fwd's value, then one fp32 add);
+ *   the new disp outside the frame ends the track, which keeps that disp: inside iff 0 <= xi and (xi < w - 1 or (xi == w - 1 and
+ *     xw == 0)) with xi = x + (int)floorf(u), xw = u - floorf(u), likewise in y — integer decisions; a component that is not
+ *     finite or of magnitude >= 1e6 ends it too, tested before any conversion to an integer.
+ * After every valid slot i: out_disp[i][n] = disp, out_alive[i][n] = alive ([B][Ncap][2] fp32, [B][Ncap] uint8); slots that are
+ * not pairs and rows n >= N are not written.  Tracks are independent and each touches its own state element: deterministic, no
+ * atomics.  UNFLOW_ERR_SHAPE, and nothing is launched, for B < 1, Ncap < 1, Hmax or Wmax < 1 or Hmax * Wmax above 2^31 - 1. */
+int unflow_sequence_track(const float* flow_fw, const unsigned char* occ_fw, const int* tab, int B, int Hmax, int Wmax,
+                          const int* anchors, int Ncap, float* disp, unsigned char* alive, float* out_disp,
+                          unsigned char* out_alive, unflow_stream_t stream);
+
 /* flow [B][fh][fw][2] (the last network's flow2, or flow0 at (H, W) with full_res) -> for every sample b with desc h > 0 and
  * every frame pixel (y < h, x < w):
  *   f = resize_tf1(resize_tf1(flow, H, W) * flow_scale, h, w) (full_res: resize_tf1(flow * flow_scale, h, w)),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual]
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
 of the replayed graph of FlowEstimator(..., sequence=True) in its steady state (a carried frame and B new frames: B pairs per
@@ -18,7 +18,14 @@ unflow_sequence_mirror where it runs, behind conv2, with the bytes it must move.
 
 --visual: FlowNetC at B in {1, 4, 8}, the pair-mode visual estimator, then the sequence visual estimator (and the
 sequence estimator without pictures): ms per pair of each replayed graph.  With --rocprof, from one kernel-trace child run per
-mode, the picture kernels alone at B = 8 — the last `iters` dispatches of each, with the bytes they must move."""
+mode, the picture kernels alone at B = 8 — the last `iters` dispatches of each, with the bytes they must move.
+
+--track: FlowNetC at B = 4, both sequence modes, dense tracks of stride 1: ms per pair of the replayed graph of the
+tracking estimator, of the same estimator without tracks, and of the host alternative — the plain graph followed by B image_warp
+launches and B adds outside it (no visibility) — the three taken in turn, `--rounds` times, in one process; the flow heads are
+scaled down so that the tracks stay alive and the kernel does its whole work in every replay (the share alive is reported).  Beside
+them the track kernel alone (device events around 50 launches) with the bytes it must move, and the parent commit's recorded
+lines for the same estimators without tracks (profiles/sequence_bench_line.json, profiles/sequence_bidir_bench_line.json)."""
 import argparse
 import csv
 import glob
@@ -43,9 +50,9 @@ def _frames(n):
     return [np.roll(a, 2 * i, 1) for i in range(n)]
 
 
-def _estimator(spec, B, sequence, bidirectional=False, visual=False):
+def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
-    pictures at the end of the graph."""
+    pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
     os.environ['UNFLOW_CONV_MATH'] = 'bf16x3'
     from unflow_amd.core.inference import FlowEstimator
@@ -55,10 +62,15 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False):
     torch.cuda.synchronize()
     m0 = torch.cuda.memory_allocated(dev)
     kw = dict(visual='sequence' if sequence else True) if visual else {}
+    if track is not False:
+        kw['track'] = track
     est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
-    est.engine.init_params(seed=1)
+    tfp = est.engine.init_params(seed=1)
+    if head_scale is not None:
+        est.load_tf_params({k: (v * head_scale if k.split('/')[-2].startswith('flow') and k.endswith('/weights') else v)
+                            for k, v in tfp.items()})
     est._params_changed()
     fr = _frames(3 * B + 1)
     if sequence == 'bidirectional':
@@ -293,6 +305,106 @@ def visual_rocprof(iters, B=8):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --track
+TRACK_HEAD_SCALE = 0.01          # flows of a few hundredths of a pixel: every track but the border's stays alive
+
+
+def track_bytes(B=4, occ=False):
+    """Compulsory bytes of unflow_sequence_track per replay, dense stride 1 on FRAME: per track the state read and written (9 + 9),
+    and per pair the flow map read once (8; tap re-reads go through the caches), the mask with both directions (1) and the
+    outputs written (9)."""
+    px = FRAME[0] * FRAME[1]
+    per = 18 + B * (8 + 9 + (1 if occ else 0))
+    return per, px * per
+
+
+def _host_chain(est, disp):
+    """The alternative without the kernel: B image_warp launches and B adds behind the replay, outside the graph, on the whole
+    buffers (no crop to the frame, no visibility)."""
+    from unflow_amd.core.image_warp import image_warp
+    for i in range(est.B):
+        disp = disp + image_warp(est.out_flow[i:i + 1], disp)
+    return disp
+
+
+def _time(fn, iters, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(iters + 1)]
+    ev[0].record()
+    for i in range(iters):
+        fn()
+        ev[i + 1].record()
+    ev[-1].synchronize()
+    return [ev[i].elapsed_time(ev[i + 1]) for i in range(iters)]
+
+
+def _recorded(path, B=4):
+    """ms per pair of the FlowNetC sequence estimator at B in a recorded bench line of profiles/, or None."""
+    try:
+        with open(os.path.join(ROOT, 'profiles', path)) as f:
+            line = json.loads(f.read().strip().splitlines()[-1])
+        return [c['sequence']['ms_per_pair'] for c in line['cases'] if c['spec'] == 'C' and c['B'] == B][0]
+    except (OSError, ValueError, KeyError, IndexError):
+        return None
+
+
+def track_case(seq, iters, warmup, rounds, B=4):
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    plain, _ = _estimator('C', B, seq, head_scale=TRACK_HEAD_SCALE)
+    tracked, mem = _estimator('C', B, seq, track=True, head_scale=TRACK_HEAD_SCALE)
+    tracked.track_sequence(_frames(3 * B))                 # the tables of the last replay: a carried frame, B pairs, S = 1, N
+    disp0 = torch.zeros(1, plain.Hmax, plain.Wmax, 2, device=plain.dev)
+
+    def host():
+        plain.graph.replay()
+        _host_chain(plain, disp0)
+    runs = {'plain': plain.graph.replay, 'track': tracked.graph.replay, 'host_chain': host}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # the three in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence=seq if seq is True else str(seq), tracks=FRAME[0] * FRAME[1], rounds=rounds)
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['track']['estimator_MB'] = round(mem / 1e6, 1)
+    out['track_over_plain'] = round(out['track']['ms_per_pair'] / out['plain']['ms_per_pair'], 4)
+    out['host_chain_over_plain'] = round(out['host_chain']['ms_per_pair'] / out['plain']['ms_per_pair'], 4)
+    out['track_added_us_per_replay'] = round((out['track']['ms_per_pair'] - out['plain']['ms_per_pair']) * B * 1e3, 2)
+    out['host_chain_added_us_per_replay'] = round((out['host_chain']['ms_per_pair'] - out['plain']['ms_per_pair']) * B * 1e3, 2)
+    # the kernel alone: 50 launches between two events (its launch gaps included), the tables of the last replay
+    L, e = _lib.lib(), tracked
+
+    def kernel():
+        check(L.unflow_sequence_track(ptr(e.out_flow), ptr(e.occ[0]) if e.seq_bidir else None, ptr(e.tab), B, e.Hmax, e.Wmax,
+                                      ptr(e.track_anchors), e.track_cap, ptr(e.track_disp), ptr(e.track_alive),
+                                      ptr(e.out_track_disp), ptr(e.out_track_alive), e.engine.stream()), "sequence_track")
+    with torch.cuda.device(e.dev):
+        for _ in range(10):
+            kernel()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(50):
+            kernel()
+        b.record()
+        b.synchronize()
+    us = a.elapsed_time(b) * 1e3 / 50
+    per, nbytes = track_bytes(B, e.seq_bidir)
+    out['kernel'] = dict(us=round(us, 2), B_per_track=per, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / us / 1e6, 3),
+                         how='device events around 50 back-to-back launches, launch gaps included')
+    out['alive_share'] = round(float(e.track_alive[:FRAME[0] * FRAME[1]].float().mean().item()), 4)
+    out['parent_recorded_ms_per_pair'] = _recorded('sequence_bidir_bench_line.json' if e.seq_bidir else 'sequence_bench_line.json', B)
+    del plain, tracked
+    import gc
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -305,7 +417,19 @@ def main():
     ap.add_argument('--visual', action='store_true',
                     help='the pair-mode visual estimator against the sequence visual estimator, FlowNetC (DESIGN 7.14)')
     ap.add_argument('--visual-kernels-only', choices=('pair', 'sequence'), help=argparse.SUPPRESS)
+    ap.add_argument('--track', action='store_true',
+                    help='the tracking estimator against the same one without tracks and against image_warp launches behind '
+                         'the graph, FlowNetC at B = 4, both sequence modes (DESIGN 7.15)')
+    ap.add_argument('--rounds', type=int, default=3, help='--track: how often the compared estimators take turns')
     a = ap.parse_args()
+    if a.track:
+        res = dict(metric='sequence_track_ms_per_pair_over_the_same_estimator_without_tracks', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup,
+                   expected='no ratio was predicted; from the bytes the kernel is a few microseconds beside a replay of '
+                            'milliseconds',
+                   cases=[track_case(seq, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
+        print(json.dumps(res))
+        return
     if a.visual_kernels_only:
         return visual_kernels_only(a.visual_kernels_only, a.iters)
     if a.visual:

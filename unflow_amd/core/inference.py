@@ -50,6 +50,15 @@ flag and, with sequence, still a ValueError that names this spelling).  Either s
 
 (push_visual, visualize_sequence, export_sequence(visual=True)); a clip-wide max_flow of the colours travels in the tables.
 
+sequence=True | 'bidirectional' with track=True | S | anchors: tracks along a clip.  Behind the output (and
+occlusion) kernels either sequence graph runs
+
+    unflow_sequence_track          the forward flows of the replay's pairs (bidirectional: and the forward occlusion masks) -> per
+                                   pair, where every anchor of the clip's first frame is now and whether it is still visible; the
+                                   state (displacement, alive) stays on the device from one replay of the clip to the next
+
+(push_tracks, track_sequence, export_sequence(tracks=True)); the grid stride and the number of tracks travel in the tables.
+
 The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
 _submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
 leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
@@ -98,13 +107,52 @@ def sequence_visual_files(n, bidirectional):
     return [(k, '%06d_%s.png' % (n, SEQUENCE_VISUAL_TAGS[k])) for k in (0, 2, 1) + ((3, 4) if bidirectional else ())]
 
 
-def pair_files(n, fmt, backward=False, occlusion=False, pictures=()):
+# What push_tracks returns per pair (n, n + 1): disp float32, where every anchor of the clip's first frame is in frame n + 1, as
+# its displacement from the anchor, and alive bool, still in the frame and never occluded — [gh, gw, 2] and [gh, gw] for the dense
+# grid, [N, 2] and [N] for sparse anchors
+Track = collections.namedtuple('Track', ('disp', 'alive'))
+TRACK_DEAD = 1e10          # a dead track in %06d_track.flo: the .flo unknown-flow convention (read back as mask = 0)
+
+
+def track_option(track):
+    """FlowEstimator's track option -> None (no tracks), ('dense', S): the grid of stride S over the frame (True: S = 1), or
+    ('sparse', int32 [N, 2] array of (x, y) anchors).  Anything else: ValueError."""
+    if track is None or track is False:
+        return None
+    if track is True:
+        return ('dense', 1)
+    if isinstance(track, (int, np.integer)):
+        if int(track) < 1:
+            raise ValueError("FlowEstimator: track=S is a grid stride >= 1, got %d" % int(track))
+        return ('dense', int(track))
+    if isinstance(track, (str, bytes, dict)):
+        raise ValueError("FlowEstimator: track is True, a grid stride S >= 1 or an int array [N][2] of (x, y) anchors, got %r"
+                         % (track,))
+    try:
+        a = np.asarray(track.cpu().numpy() if isinstance(track, torch.Tensor) else track)
+    except Exception:
+        a = None
+    if a is None or a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("FlowEstimator: track is True, a grid stride S >= 1 or an int array [N][2] of (x, y) anchors, got %s"
+                         % ("%s %s" % (a.dtype, a.shape) if a is not None else repr(track)))
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("FlowEstimator: track anchors are int32 pixel coordinates")
+    return ('sparse', np.ascontiguousarray(a, dtype=np.int32))
+
+
+def track_grid(shape, stride):
+    """(gh, gw) of the dense anchor grid of that stride over a frame of shape (h, w): anchors (stride * gx, stride * gy)."""
+    return (-(-int(shape[0]) // int(stride)), -(-int(shape[1]) // int(stride)))
+
+
+def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False):
     """The files export / export_sequence write for pair n, in the order they are written — _10, _01, _10_occ, then the pictures
     (visual_files' or sequence_visual_files' list) in their file order: [(file name, source)].  A source is
 
         ('png', surface, k)   a PNG of image k * B + i of the encode surface of that name for row i of the replay (_Encoder; also
                               the slot's pinned copy of it): 'u16', 'u16_bw', 'occ' with k = 0, 'vis' with the picture's index;
-        ('flo', attribute)    a .flo file of row i of that pinned flow of the slot: 'flow', 'flow_bw'.
+        ('flo', attribute)    a .flo file of row i of that pinned flow of the slot: 'flow', 'flow_bw';
+        ('track', attribute)  track: the dense tracks of row i on their grid, %06d_track.flo (FlowEstimator._track_flo), last.
 
     Both back ends of FlowEstimator._write_files and the entries of the replay's unflow_png_filter launch (filter_entries) come
     from this one list, so the span order and the file order cannot drift apart."""
@@ -112,7 +160,8 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=()):
     out = [('%06d_%s.%s' % (n, tag, fmt), ('png', u16, 0) if fmt == 'png' else ('flo', flow)) for tag, u16, flow in flows]
     if occlusion:
         out.append(('%06d_10_occ.png' % n, ('png', 'occ', 0)))
-    return out + [(name, ('png', 'vis', k)) for k, name in pictures]
+    return out + [(name, ('png', 'vis', k)) for k, name in pictures] + \
+        ([('%06d_track.flo' % n, ('track', 'track_disp'))] if track else [])
 
 
 def filter_entries(files, rows, batch):
@@ -153,14 +202,15 @@ def pack_desc(shapes, batch, staged=None, nmaps=0, u8=False):
     return d
 
 
-def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None):
+def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None):
     """The device tables of one sequence replay, one int32 array [16 * batch + 4]: the frame table [batch][8] (pack_desc: the k
     new frames of size `shape` in rows 1 .. k of the engine, slots [0, k)), the pair table [batch][8] (slot i = rows i, i + 1:
     valid when both hold frames of this clip — slot 0 needs a carried frame, slot i >= 1 needs i + 1 <= k), the carry source
     (row of the previous replay's last frame; 0: a clip's first replay, nothing carried) and, behind it, the max_flow of the
     clip's flow colours (unflow_sequence_visual): 0 for None, every pair coloured with its own maximum, else the bit pattern of
-    float32 max(max_flow, 1) (flow_util.py:31-32).  Returns (table, slots of the valid pairs in order, the next replay's carry
-    source = k)."""
+    float32 max(max_flow, 1) (flow_util.py:31-32); behind that, the two words of unflow_sequence_track: track = (S, N), the grid
+    stride (0 with sparse anchors) and the number of tracks; None: both 0, as in every table without tracks.  Returns (table,
+    slots of the valid pairs in order, the next replay's carry source = k)."""
     batch, k, carry = int(batch), int(k), int(carry)
     if not 1 <= k <= batch:
         raise ValueError("a sequence replay takes 1 to %d new frames, got %d" % (batch, k))
@@ -176,6 +226,11 @@ def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None):
     tab[16 * batch] = carry
     if max_flow is not None:
         tab[16 * batch + 1] = np.array([max(max_flow, 1)], dtype=np.float32).view(np.int32)[0]
+    if track is not None:
+        S, N = int(track[0]), int(track[1])
+        if S < 0 or not 1 <= N < 2 ** 31:
+            raise ValueError("tracks: a grid stride >= 1 (0: sparse anchors) and 1 to 2^31 - 1 tracks, got S = %d, N = %d" % (S, N))
+        tab[16 * batch + 2], tab[16 * batch + 3] = S, N
     return tab, valid, k
 
 
@@ -215,10 +270,10 @@ def chunks(it, n):
         yield buf
 
 
-def output_buffers(B, Hm, Wm):
+def output_buffers(B, Hm, Wm, Ncap=0):
     """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
     and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
-    estimator has it).  Without its flag both attributes are None."""
+    estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator."""
     return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
             ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
             ('sums', 'sums', (B, 2, 2), torch.float64, None),
@@ -227,7 +282,9 @@ def output_buffers(B, Hm, Wm):
             ('u16_bw', 'out_u16_bw', (B, Hm, Wm, 3), torch.int16, 'bidirectional'),
             ('occ', 'occ', (2, B, Hm, Wm), torch.uint8, 'bidirectional'),                   # occ_fw, occ_bw
             ('occ_counts', 'occ_counts', (B, 3), torch.int32, 'bidirectional'),
-            ('vis', 'vis', (len(VISUAL_IMAGES), B, Hm, Wm, 3), torch.uint8, 'visual'))
+            ('vis', 'vis', (len(VISUAL_IMAGES), B, Hm, Wm, 3), torch.uint8, 'visual'),
+            ('track_disp', 'out_track_disp', (B, Ncap, 2), torch.float32, 'track'),
+            ('track_alive', 'out_track_alive', (B, Ncap), torch.uint8, 'track'))
 
 
 class _Slot:
@@ -241,7 +298,7 @@ class _Slot:
         self.desc = pin(B, 8, dtype=torch.int32)
         self.tab = pin(16 * B + 4, dtype=torch.int32) if est.sequence else None   # sequence_tables
         self.gt_flow = self.gt_mask = None
-        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm):
+        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap):
             setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
         self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
@@ -308,10 +365,16 @@ class FlowEstimator:
     before; the message names this spelling): the pictures of every pair of the clip, every frame
     resampled once (push_visual, visualize_sequence, export_sequence(visual=True)): FlowVisual per pair, or SequenceVisual on a
     sequence='bidirectional' estimator; max_flow there is one scale of the flow colours for the whole clip, set by the call that
-    starts the clip (None: every pair has its own maximum, as in pair mode)."""
+    starts the clip (None: every pair has its own maximum, as in pair mode).
+    track (with sequence): tracks along a clip — where the pixels of the clip's first frame are in every later frame, the forward
+    flows chained through image_warp's taps, and whether each is still visible (inside the frame; on a sequence='bidirectional'
+    estimator also: never under the forward occlusion mask).  True: an anchor at every pixel; an int S >= 1: at every S-th pixel
+    of every S-th row; an int array [N][2]: at those (x, y).  push_tracks / track_sequence return a Track(disp, alive) per pair,
+    export_sequence(tracks=True) writes them; every other method returns what it returns without track.  reset() starts a new
+    anchor frame."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
-                 visual=False, sequence=False):
+                 visual=False, sequence=False, track=False):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -325,6 +388,11 @@ class FlowEstimator:
         if visual == 'sequence' and not sequence:
             raise ValueError("FlowEstimator: visual='sequence' draws the pairs of a clip; it needs sequence=True or "
                              "sequence='bidirectional' (a pair estimator's pictures are visual=True)")
+        self.track_spec = track_option(track)
+        if self.track_spec is not None and not sequence:
+            raise ValueError("FlowEstimator: track follows the pixels of a clip's first frame; it needs sequence=True or "
+                             "sequence='bidirectional'")
+        self.track = self.track_spec is not None
         self.sequence = bool(sequence)
         self.seq_bidir = sequence == 'bidirectional'
         self.params = dict(params)
@@ -335,6 +403,11 @@ class FlowEstimator:
         self.use_graph = bool(use_graph)
         self.bidirectional = bool(bidirectional) or self.seq_bidir
         self.visual = bool(visual)
+        # track capacity: the dense grid over max_frame, or the anchors given
+        self.track_cap = 0
+        if self.track:
+            kind, arg = self.track_spec
+            self.track_cap = int(np.prod(track_grid((self.Hmax, self.Wmax), arg))) if kind == 'dense' else int(arg.shape[0])
         eng_params = {k: v for k, v in self.params.items() if k.endswith('_weight') or k in ENGINE_KEYS}
         self.engine = FlowNetEngine(self.B, self.H, self.W, params=eng_params or None, device=self.dev, seed=None,
                                     inference=True, bidirectional=bool(bidirectional), sequence=sequence)
@@ -351,8 +424,14 @@ class FlowEstimator:
             nb = int(L.unflow_inference_output_blocks(Hm, Wm))
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
-            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm):      # out_flow, out_u16, sums, counts, ...
+            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap):   # out_flow, out_u16, sums, counts, ...
                 setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
+            self.track_anchors = self.track_disp = self.track_alive = None
+            if self.track:
+                # the state of unflow_sequence_track, kept from one replay of a clip to the next; sparse: the anchor table
+                self.track_disp, self.track_alive = z(self.track_cap, 2), z(self.track_cap, dtype=torch.uint8)
+                if self.track_spec[0] == 'sparse':
+                    self.track_anchors = torch.from_numpy(self.track_spec[1]).to(self.dev)
             self.vis_shown = self.vis_max = None
             if self.visual:
                 # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
@@ -417,7 +496,8 @@ class FlowEstimator:
     def _launch_sequence(self):
         """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds);
         sequence='bidirectional': the output kernel on either block of the engine's 2B rows, then the occlusion kernel, all
-        three over the pair table and without ground truth; visual: then the pictures, from the same tables."""
+        three over the pair table and without ground truth; track: then the tracks, through the pairs of the table; visual: then
+        the pictures, from the same tables."""
         e, B = self.engine, self.B
         L = _lib.lib()
         e.sequence_carry(self.tab[16 * B:])
@@ -431,6 +511,11 @@ class FlowEstimator:
             self._occlusion(pairs)
         else:
             self._output(self.flow_src, pairs, self.out_flow, self.out_u16)
+        if self.track:
+            check(L.unflow_sequence_track(ptr(self.out_flow), ptr(self.occ[0]) if self.seq_bidir else None, ptr(self.tab), B,
+                                          self.Hmax, self.Wmax, ptr(self.track_anchors), self.track_cap, ptr(self.track_disp),
+                                          ptr(self.track_alive), ptr(self.out_track_disp), ptr(self.out_track_alive),
+                                          e.stream()), "sequence_track")
         if self.visual:
             bw, occ = (self.out_flow_bw, self.occ[0]) if self.seq_bidir else (None, None)
             check(L.unflow_sequence_visual(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.H, self.W,
@@ -470,7 +555,8 @@ class FlowEstimator:
             e.planes_external = True          # the weights are static: the graph does not re-split them
             self._launch()                    # eager pass first: grows the shared workspaces outside the capture
             # (sequence: the eager pass and the first replay both run the carry; the graph is built by an estimator's first
-            # replay ever, whose carry source is 0 — a no-op both times)
+            # replay ever, whose carry source is 0 — a no-op both times; unflow_sequence_track starts from disp = 0, alive = 1
+            # both times for the same reason)
             torch.cuda.current_stream(self.dev).synchronize()
             s = torch.cuda.Stream(self.dev)
             s.wait_stream(torch.cuda.current_stream(self.dev))
@@ -623,7 +709,7 @@ class FlowEstimator:
         truth was staged, the occlusion counts only when it had two maps."""
         special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
         nv = self._num_pictures(nmaps)
-        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax):
+        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap):
             if special.get(name, name in want):
                 dst, src = getattr(slot, name), getattr(self, attr)
                 if name == 'vis':
@@ -665,7 +751,7 @@ class FlowEstimator:
         return self._one_ahead(self._submit(k, exs, staged, nmaps_of(exs), want, files=files) for k, exs in enumerate(batches))
 
     # ------------------------------------------------------------------------------------------ public API
-    def _mode(self, what, sequence, bidirectional=False, visual=False):
+    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False):
         """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
         one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
         if not sequence:
@@ -684,6 +770,10 @@ class FlowEstimator:
             raise RuntimeError("%s: a pair estimator; build it with FlowEstimator(..., sequence=True)" % what)
         if visual and not self.visual:
             raise RuntimeError("%s: a sequence estimator without pictures; build it with %s" % (what, self._visual_spelling()))
+        if track and not self.track:
+            raise RuntimeError("%s: a sequence estimator without tracks; build it with FlowEstimator(..., sequence=%r, track=True) "
+                               "(or track=S, a grid stride, or track=anchors, an int array [N][2] of (x, y))"
+                               % (what, 'bidirectional' if self.seq_bidir else True))
 
     def _visual_spelling(self):
         """How to build this sequence estimator with pictures, for the messages that ask for it."""
@@ -941,7 +1031,8 @@ class FlowEstimator:
         from .input import write_flo, write_kitti_flow_png, write_png_gray8, write_png_rgb8
         from .png_device import DeviceFileWriter, flo_file_bytes
         os.makedirs(out_dir, exist_ok=True)
-        want = tuple(src[1] for _, src in plan(0, 0) if not workers or src[0] == 'flo')
+        want = tuple(src[1] for _, src in plan(0, 0) if not workers or src[0] in ('flo', 'track'))
+        want += ('track_alive',) if 'track_disp' in want else ()
         files = (lambda rows, nmaps: filter_entries(plan(0, nmaps), rows, self.B), deflate) if workers else None
         pool = DeviceFileWriter(workers, level) if workers else None
         paths, n = [], 0
@@ -951,7 +1042,13 @@ class FlowEstimator:
                 for i, h, w in rows:
                     for name, (kind, attr, *k) in plan(n, nmaps):
                         path = os.path.join(out_dir, name)
-                        if pool is not None and kind == 'png':
+                        if kind == 'track':
+                            grid = self._track_flo(slot, i, h, w)
+                            if pool is not None:
+                                pool.submit(path, 'flo', flo_file_bytes(grid))
+                            else:
+                                write_flo(path, grid)
+                        elif pool is not None and kind == 'png':
                             off, nb, _, _, depth, ctype = next(spans)
                             pool.submit(path, slot.scan_kind, (h, w, depth, ctype, slot.scan.numpy()[off:off + nb].tobytes()))
                         elif pool is not None:
@@ -1036,7 +1133,7 @@ class FlowEstimator:
         for i, a in enumerate(frames):
             if not isinstance(a, torch.Tensor):
                 fr[i, :h, :w] = a
-        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow)
+        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow, self._track_words(h, w))
         slot.tab.numpy()[:] = tab
         with torch.cuda.device(self.dev):
             self.tab.copy_(slot.tab, non_blocking=True)
@@ -1094,6 +1191,55 @@ class FlowEstimator:
             out += self._visual_of(slot, rows, SequenceVisual if self.seq_bidir else FlowVisual)
         return out
 
+    # tracks
+    def _track_shape(self, h, w):
+        """The shape of one pair's tracks for a clip of (h, w) frames: the dense grid (gh, gw), or (N,) with sparse anchors."""
+        kind, arg = self.track_spec
+        return track_grid((h, w), arg) if kind == 'dense' else (int(arg.shape[0]),)
+
+    def _track_words(self, h, w):
+        """(S, N) for sequence_tables: the grid stride (0: sparse anchors) and the number of tracks of a clip of (h, w) frames;
+        None without tracks.  More tracks than the buffers hold: ValueError before the replay (the kernel would clamp)."""
+        if not self.track:
+            return None
+        n = int(np.prod(self._track_shape(h, w)))
+        if n > self.track_cap:
+            raise ValueError("push: %d tracks on a %dx%d frame exceed the estimator's capacity of %d" % (n, h, w, self.track_cap))
+        return (self.track_spec[1] if self.track_spec[0] == 'dense' else 0, n)
+
+    def _tracks_of(self, slot, rows):
+        """The rows of a finished tracking replay as Track tuples (copies)."""
+        d, a = slot.track_disp.numpy(), slot.track_alive.numpy()
+        out = []
+        for i, h, w in rows:
+            shape = self._track_shape(h, w)
+            n = int(np.prod(shape))
+            out.append(Track(d[i, :n].reshape(shape + (2,)).copy(), a[i, :n].reshape(shape).astype(bool)))
+        return out
+
+    def _track_flo(self, slot, i, h, w):
+        """Row i of a finished tracking replay as the [gh, gw, 2] float32 array of %06d_track.flo: the displacement from the
+        clip's first frame, (TRACK_DEAD, TRACK_DEAD) where the track is dead."""
+        t, = self._tracks_of(slot, [(i, h, w)])
+        return np.where(t.alive[..., None], t.disp, np.float32(TRACK_DEAD)).astype(np.float32)
+
+    def push_tracks(self, frames):
+        """push's frames on an estimator built with track: one Track(disp, alive) per new pair (the count is push's).  For the
+        pair (n, n + 1), disp is where every anchor of the clip's first frame is in frame n + 1, as its displacement from the
+        anchor — float32 [gh, gw, 2] on the dense grid (anchor (S gx, S gy) at [gy, gx]) or [N, 2] for sparse anchors — and alive
+        bool [gh, gw] / [N]: still inside the frame and (sequence='bidirectional') never under a forward occlusion mask.  A dead
+        track keeps the disp it had when it died."""
+        self._mode('push_tracks', sequence=True, track=True)
+        return self._tracks_of(*self._push(frames, ('track_disp', 'track_alive')))
+
+    def track_sequence(self, frames):
+        """Tracks along a clip: T >= 2 frames -> T - 1 Track tuples (push_tracks'), anchored in the first frame."""
+        self._mode('track_sequence', sequence=True, track=True)
+        out = []
+        for slot, rows, _ in self._pipeline_sequence(frames, ('track_disp', 'track_alive')):
+            out += self._tracks_of(slot, rows)
+        return out
+
     def _pipeline_sequence(self, frames, want, files=None, max_flow=None):
         """reset, then _one_ahead over pushes of B frames."""
         self.reset()
@@ -1117,7 +1263,7 @@ class FlowEstimator:
         return out
 
     def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False,
-                        visual=False, max_flow=None):
+                        visual=False, max_flow=None, tracks=False):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
         writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
@@ -1128,9 +1274,16 @@ class FlowEstimator:
         visual (an estimator built with visual='sequence'): after those, per pair, the 8-bit pictures of push_visual —
         sequence_visual_files' %06d_img.png (overlay), %06d_flow.png (flow colours), %06d_diff.png (brightness error) and, on a
         sequence='bidirectional' estimator, %06d_flow_bw.png (the backward flow's colours) and %06d_diff_noc.png (the brightness
-        error of the non-occluded pixels); max_flow: the scale of the flow colours for the whole clip (None: per pair)."""
+        error of the non-occluded pixels); max_flow: the scale of the flow colours for the whole clip (None: per pair).
+        tracks (an estimator built with track): the tracks of push_tracks.  Dense: after a pair's other files %06d_track.flo,
+        the displacement from frame 0 to frame n + 1 on the gh x gw anchor grid, a dead track written as (1e10, 1e10) — the
+        .flo unknown-flow value, read back as mask = 0 — through the same writer as the other .flo files.  Sparse anchors: one
+        tracks.npz behind the last pair's files, with anchors [N, 2] int32, disp [T - 1, N, 2] float32, alive [T - 1, N] bool."""
         from .png_device import check_deflate_mode
         self._mode('export_sequence', sequence=True)
+        if tracks and not self.track:
+            raise ValueError("export_sequence: the tracks need FlowEstimator(..., sequence=%r, track=True) (or track=S, or "
+                             "track=anchors)" % ('bidirectional' if self.seq_bidir else True))
         on_device = check_deflate_mode(deflate, workers)
         if fmt not in ('png', 'flo'):
             raise ValueError("export_sequence: fmt must be 'png' or 'flo'")
@@ -1142,6 +1295,21 @@ class FlowEstimator:
             raise ValueError("export_sequence: max_flow scales the flow colours of the pictures; it needs visual=True")
 
         def plan(n, nmaps):
-            return pair_files(n, fmt, backward, occlusion, sequence_visual_files(n, self.seq_bidir) if visual else ())
-        return self._write_files(lambda want, files: self._pipeline_sequence(frames, want, files, max_flow), plan, out_dir,
-                                 workers, level, on_device)
+            return pair_files(n, fmt, backward, occlusion, sequence_visual_files(n, self.seq_bidir) if visual else (),
+                              track=dense)
+        dense = bool(tracks) and self.track_spec[0] == 'dense'
+        sparse = [] if tracks and not dense else None      # sparse anchors: the Track of every pair, for tracks.npz
+
+        def replays(want, files):
+            if sparse is not None:
+                want += ('track_disp', 'track_alive')
+            for slot, rows, nmaps in self._pipeline_sequence(frames, want, files, max_flow):
+                if sparse is not None:
+                    sparse.extend(self._tracks_of(slot, rows))
+                yield slot, rows, nmaps
+        paths = self._write_files(replays, plan, out_dir, workers, level, on_device)
+        if sparse is not None:
+            paths.append(os.path.join(out_dir, 'tracks.npz'))
+            np.savez(paths[-1], anchors=self.track_spec[1], disp=np.stack([t.disp for t in sparse]),
+                     alive=np.stack([t.alive for t in sparse]))
+        return paths

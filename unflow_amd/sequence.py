@@ -3,6 +3,7 @@ once (core/inference.FlowEstimator(..., sequence=True)).
 
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
                                   [--output_backward] [--occlusion] [--visual] [--max_flow F]
+                                  [--track] [--track_stride S] [--track_points FILE]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -12,7 +13,10 @@ the default and --host_encode: the host's writers.  --output_backward adds the b
 --occlusion its forward occlusion mask (%06d_10_occ.png); either one runs both directions along the clip
 (FlowEstimator(..., sequence='bidirectional')).  --visual adds the pictures of every pair: %06d_img.png,
 %06d_flow.png, %06d_diff.png and, where both directions run, %06d_flow_bw.png and %06d_diff_noc.png; --max_flow F colours the
-whole clip with one scale instead of every pair with its own maximum."""
+whole clip with one scale instead of every pair with its own maximum.  --track follows every pixel of the first frame along the
+clip and adds %06d_track.flo per pair: the displacement from frame 0 to frame n + 1, (1e10, 1e10) where the track
+has left the frame or — where both directions run — was occluded; --track_stride S: every S-th pixel of every S-th row instead;
+--track_points FILE: the pixels listed in FILE, `x y` per line, written as one tracks.npz (anchors, disp, alive)."""
 import argparse
 import os
 import sys
@@ -86,6 +90,32 @@ def png_size(path):
     return h, w
 
 
+def read_points(path):
+    """The anchors of --track_points: a text file with `x y` per line (integers; blank lines and lines that start with # are
+    skipped) -> int32 [N, 2]; anything else: ValueError naming the file and the line."""
+    import numpy as np
+    pts = []
+    try:
+        with open(path) as f:
+            lines = f.read().splitlines()
+    except (OSError, UnicodeDecodeError) as err:
+        raise ValueError("%s: not a readable text file (%s)" % (path, err))
+    for k, line in enumerate(lines, 1):
+        t = line.split()
+        if not t or t[0].startswith('#'):
+            continue
+        try:
+            x, y = (int(v) for v in t)
+        except ValueError:
+            raise ValueError("%s:%d: expected two integers `x y`, got %r" % (path, k, line))
+        if not (-2 ** 31 <= x < 2 ** 31 and -2 ** 31 <= y < 2 ** 31):
+            raise ValueError("%s:%d: a pixel coordinate outside int32: %r" % (path, k, line))
+        pts.append((x, y))
+    if not pts:
+        raise ValueError("%s: no points" % path)
+    return np.asarray(pts, dtype=np.int32)
+
+
 def parser():
     ap = argparse.ArgumentParser(prog='python -m unflow_amd.sequence', description=__doc__.split('\n')[0])
     ap.add_argument('--ex', required=True, help='experiment name')
@@ -104,6 +134,13 @@ def parser():
                          '(brightness error); with --output_backward or --occlusion also %%06d_flow_bw.png and %%06d_diff_noc.png')
     ap.add_argument('--max_flow', type=float, default=None, metavar='F',
                     help='with --visual: one scale of the flow colours for the whole clip (default: every pair its own maximum)')
+    ap.add_argument('--track', action='store_true',
+                    help='also follow every pixel of the first frame along the clip: %%06d_track.flo per pair, the displacement '
+                         'from frame 0 to frame n + 1, (1e10, 1e10) where the track is dead')
+    ap.add_argument('--track_stride', type=int, default=None, metavar='S',
+                    help='like --track, for every S-th pixel of every S-th row (files of ceil(h / S) x ceil(w / S) pixels)')
+    ap.add_argument('--track_points', default=None, metavar='FILE',
+                    help='follow the pixels listed in FILE (`x y` per line) instead: one tracks.npz with anchors, disp and alive')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -123,6 +160,18 @@ def parse_args(argv=None):
         ap.error("--max_flow scales the flow colours of the pictures: it needs --visual")
     if a.max_flow is not None and not a.max_flow > 0:
         ap.error("--max_flow must be positive")
+    if a.track_stride is not None and a.track_stride < 1:
+        ap.error("--track_stride must be at least 1")
+    if a.track_points is not None and (a.track or a.track_stride is not None):
+        ap.error("--track_points follows the listed pixels; --track / --track_stride follow a grid: give one or the other")
+    a.track_option = False                        # FlowEstimator's track
+    if a.track_points is not None:
+        try:
+            a.track_option = read_points(a.track_points)
+        except ValueError as err:
+            ap.error("--track_points %s" % err)
+    elif a.track or a.track_stride is not None:
+        a.track_option = a.track_stride if a.track_stride is not None else True
     if a.net_size[0] % 64 or a.net_size[1] % 64 or min(a.net_size) <= 0:
         ap.error("--net_size: H and W must be positive multiples of 64")
     if not os.path.isdir(a.frames):
@@ -154,7 +203,7 @@ def main(argv=None):
     params.update(config.get('train_kitti', {}))
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
                                         sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
-                                        visual='sequence' if a.visual else False)
+                                        visual='sequence' if a.visual else False, track=a.track_option)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
@@ -162,7 +211,7 @@ def main(argv=None):
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
                                     deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion, visual=a.visual,
-                                    max_flow=a.max_flow)
+                                    max_flow=a.max_flow, tracks=a.track_option is not False)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))
