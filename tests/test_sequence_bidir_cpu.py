@@ -42,6 +42,10 @@ def test_row_plan(spec, B):
     for i, st in enumerate(eng.stages):
         tower = st.is_c
         assert st.seq_bidir and st.rows['x0'] == F
+        # two blocks on every stage, refinement stages included (they read the shared x0): the backward pairs (frame i + 1,
+        # frame i) at rows [0, B), then the forward pairs at rows [B, 2B)
+        assert st.pairs == [(1, 0, 0), (0, 1, B)]
+        assert pair.stages[i].pairs is None                  # bidirectional=True: the directed batch
         for name in st.bufs:
             if tower and name == 'cat2':
                 # the chosen layout: backward block, then the tower's F rows — 2B rows for the decoder, the last frame behind

@@ -27,6 +27,7 @@ def test_row_plan_of_a_flownet_c(B):
     st = _Stage(_Shape(B, True, True), 'C', 0)
     F = B + 1
     assert st.rows['x0'] == F
+    assert st.pairs == [(0, 1, 0)]                           # one block: pair i = (frame row i, frame row i + 1) -> row i
     for name in st.bufs:
         assert st.rows[name] == (F if name in ENC else B), name
     for op in st.ops:
@@ -43,6 +44,7 @@ def test_row_plan_of_a_flownet_s_changes_x0_alone(B):
     seq, pair = _Stage(_Shape(B, True, True), 'S', 0), _Stage(_Shape(B, True, False), 'S', 0)
     assert seq.rows.pop('x0') == B + 1 and pair.rows.pop('x0') == 2 * B
     assert seq.rows == pair.rows and all(v == B for v in seq.rows.values())
+    assert seq.pairs == [(0, 1, 0)] and pair.pairs == [(0, B, 0)]     # the stage input reads the pair's frames from x0
     assert _plan(seq) == _plan(pair) and all(op.r0 == 0 for op in seq.ops)
 
 
@@ -54,6 +56,7 @@ def test_without_the_flag_the_plan_is_the_parents(kind, one_dir):
     B = 3
     old, off = _Stage(_Shape(B, one_dir), kind, 0), _Stage(_Shape(B, one_dir, False), kind, 0)
     assert old.rows == off.rows and _plan(old) == _plan(off)
+    assert old.pairs == off.pairs == ([(0, B, 0)] if one_dir else None)     # None: the directed batch, one launch over N rows
     assert all(op.r0 == 0 for op in off.ops)
     for name, n in off.rows.items():
         assert n == (2 * B if (not one_dir or name in (ENC if kind == 'C' else ()) or name == 'x0') else B), name
@@ -79,6 +82,8 @@ def test_sequence_engine_layout_and_flags():
     for a, b in zip(pair.layers, seq.layers):               # the flat parameter layout is unchanged
         assert a.name == b.name and a.w.data_ptr() - pair.P.data_ptr() == b.w.data_ptr() - seq.P.data_ptr()
     assert seq.stages[0].rows['c3'] == 3 and seq.stages[1].rows['c3'] == 2     # only the first network has a tower
+    # ... but the refinement stage has the same pair blocks: its input takes the frames from x0, which the stages share
+    assert seq.stages[0].pairs == seq.stages[1].pairs == [(0, 1, 0)] and pair.stages[0].pairs == pair.stages[1].pairs == [(0, 2, 0)]
     for kw in (dict(inference=True, bidirectional=True), dict(supervised=True), dict(), dict(inference=False)):
         with pytest.raises(ValueError, match="sequence"):
             FlowNetEngine(2, 64, 128, device='cpu', layout_only=True, seed=None, sequence=True, **kw)

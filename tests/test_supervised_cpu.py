@@ -85,6 +85,7 @@ def test_one_direction_engine_plan(spec):
     B = 2
     eng = FlowNetEngine(B, 64, 128, params=dict(flownet=spec, train_all=True), device='cpu', layout_only=True, supervised=True)
     for st in eng.stages:
+        assert st.pairs == [(0, B, 0)]        # one block on every stage: first frames at x0 rows [0, B), second at [B, 2B)
         enc = {'c1', 'cat2', 'c3'} if st.is_c else set()
         for name in st.bufs:
             assert st.rows[name] == (2 * B if name in enc else B), (st.kind, name)
@@ -99,6 +100,7 @@ def test_one_direction_engine_plan(spec):
             assert all(op.n == B for op in st.ops)
     bi = FlowNetEngine(B, 64, 128, params=dict(flownet=spec), device='cpu', layout_only=True)
     for st in bi.stages:
+        assert st.pairs is None               # the training engine: the directed batch
         assert not st.bwd_zero_rows and not st.bwd_post_act and all(op.n == 2 * B for op in st.ops)
     # the same parameters either way
     assert bi.n_params == eng.n_params and [l.name for l in bi.layers] == [l.name for l in eng.layers]

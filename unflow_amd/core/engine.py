@@ -73,11 +73,12 @@ class Layer:
     """One conv / conv_transpose variable pair.  in_map: [(physical lo, tf lo, n)] — where the reference's input channels
     live in the (padded, segment-aligned) physical input of the layer; cout_p >= cout is the physical output width
     (pad columns keep zero weights / bias and receive exactly zero gradient)."""
-    __slots__ = ('name', 'kind', 'k', 'cin', 'cout', 'stride', 'act', 'cin_p', 'cout_p', 'in_map', 'w', 'b', 'dw', 'db', 'mw', 'vw', 'mb', 'vb',
-                 'wpl_d', 'wpl_t')
+    __slots__ = ('name', 'short', 'kind', 'k', 'cin', 'cout', 'stride', 'act', 'cin_p', 'cout_p', 'in_map', 'w', 'b', 'dw', 'db', 'mw', 'vw',
+                 'mb', 'vb', 'wpl_d', 'wpl_t')
 
     def __init__(self, name, kind, k, cin, cout, stride, act, in_map=None, cin_p=None):
         self.name, self.kind, self.k, self.cin, self.cout, self.stride, self.act = name, kind, k, cin, cout, stride, act
+        self.short = name.split('/')[-1]                    # the name without its variable scope
         self.in_map = in_map or [(0, 0, cin)]
         if cin_p is None:
             cin_p = cin if (kind == 'deconv' and cin == 2) else pad4(max(lo + n for lo, _, n in self.in_map))
@@ -102,6 +103,19 @@ class Layer:
 
     def uses_planes(self):
         return self.cout > 4 and self.cin_p >= 4
+
+    def _in_run(self, t, plo, n):
+        """Input channels [plo, plo + n) and the cout real output channels of a physical weight-shaped tensor."""
+        return t[:, :, plo:plo + n, :self.cout] if self.kind == 'conv' else t[:, :, :self.cout, plo:plo + n]
+
+    def scatter_tf(self, dst, w):
+        """TF-layout weights w (tf_wshape) -> the physical weight-shaped tensor dst: every run of in_map into its slot."""
+        for plo, tlo, n in self.in_map:
+            self._in_run(dst, plo, n).copy_(w.narrow(2 if self.kind == 'conv' else 3, tlo, n))
+
+    def gather_tf(self, src):
+        """Inverse of scatter_tf: the TF-layout view of the physical weight-shaped tensor src, as a new tensor."""
+        return torch.cat([self._in_run(src, plo, n) for plo, _, n in self.in_map], 2 if self.kind == 'conv' else 3)
 
 
 def concat_layout(parts):
@@ -157,6 +171,16 @@ def _row_range(t, r0, n):
     if r0 == 0:
         return _rows(t, n)
     return L.PT(t.t[r0:r0 + n], None if t.pl is None else t.pl[:, r0:r0 + n], t.scale)
+
+
+def _carry_bufs(t, pl, lo, n, r=0):
+    """CarryBuf descriptors of channels [lo, lo + n) of the fp32 tensor t [F, h, w, C] and of every plane of pl [P, F, h, w, Cp]
+    (or None), relative to row r."""
+    px = t.shape[1] * t.shape[2]
+    bufs = [_lib.CarryBuf(t[r, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4)]
+    for p in ([] if pl is None else range(pl.shape[0])):
+        bufs.append(_lib.CarryBuf(pl[p, r, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
+    return bufs
 
 
 class _Stage:
@@ -271,7 +295,7 @@ class _Stage:
             layer(fr, 'deconv0', 'deconv', 4, whole('cat1'), seg('cat0', 'deconv0'), c(16), 2, True)
             layer(fr, 'flow1_up0', 'deconv', 4, seg('flow1', 'flow'), seg('cat0', 'up'), 2, 2, False)
             layer(fr, 'flow0', 'conv', 3, whole('cat0'), seg('flow0', 'flow'), 2, 1, False)
-        self.by_name = {l.name.split('/')[-1]: l for l in self.layers}
+        self.by_name = {l.short: l for l in self.layers}
         # samples (rows) of every buffer and op.  Bidirectional engine: all N = 2B.  One-direction (supervised) engine: the
         # FlowNetC feature tower (conv1 .. conv3, the conv2 segment of cat2) runs on both frames, 2B rows; everything from
         # conv_redir and the correlation on, and every buffer of a FlowNetS, has B rows
@@ -282,7 +306,7 @@ class _Stage:
         # Sequence engine (one-direction, forward only): F = B + 1 frame rows, pair i = (row i, row i + 1).  The network input
         # and the tower buffers of a first-stage FlowNetC have F rows; the tower layers compute rows [1, F) — the new frames of
         # a replay — and row 0 is carried over from the previous replay (unflow_sequence_carry), never computed
-        seq = getattr(eng, 'sequence', False)
+        seq = bool(getattr(eng, 'sequence', False))
         # Bidirectional sequence engine: the same F frame rows in the network input and the tower, and BOTH
         # directions of every pair behind it — 2B rows from the cost volume on and in every buffer of a FlowNetS, the block of
         # the B backward pairs (frame i + 1, frame i) at rows [0, B), the block of the B forward pairs at rows [B, 2B).  cat2
@@ -290,38 +314,41 @@ class _Stage:
         # connection of forward pair i (decoder row B + i), the decoder runs on the contiguous rows [0, 2B), the last frame's
         # row lies behind them, and unflow_sequence_mirror fills rows [0, B) — backward pair i takes frame i + 1's — from rows
         # [B + 1, 2B + 1)
-        self.seq_bidir = bool(seq) and bool(getattr(eng, 'seq_bidir', False))
-        self.row0 = {}                    # buffer -> the row that holds the tower's row 0 (absent: 0)
+        self.seq_bidir = seq and bool(getattr(eng, 'seq_bidir', False))
+        # Pair blocks: None for the directed batch (training, bidirectional inference: one launch over N rows, the second
+        # frame of row i at row (i + B) % N); otherwise a list of (a, b, o): B pairs whose first frames are the frame rows
+        # [a, a + B), whose second frames are the frame rows [b, b + B), and whose rows behind the tower are [o, o + B).  Frame
+        # rows are rows of the network input, shared by every stage of a stack, so a refinement stage has the same blocks.
         if self.seq_bidir:
-            self.rows = {name: (nB + 1 if name in enc else 2 * nB) for name in B}
-            self.rows['x0'] = nB + 1
-            if self.is_c:
-                self.rows['cat2'], self.row0['cat2'] = 2 * nB + 1, nB
-            for op in self.ops:
-                name = None if op.kind != 'layer' else op.l.name.split('/')[-1]
-                if op.kind == 'corr':
-                    op.n = self.rows['c3']            # two launches, one per block: forward() issues them
-                elif op.dst[0] in enc and name in ('conv1', 'conv2', 'conv3'):
-                    op.n = nB
-                    op.r0, op.d0 = 1 + self.row0.get(op.src[0], 0), 1 + self.row0.get(op.dst[0], 0)
-                else:
-                    # (conv_redir: 2B destination rows from the F rows of c3, two launches of B rows: forward() issues them)
-                    op.n = 2 * nB
+            self.pairs = [(1, 0, 0), (0, 1, nB)]
+        elif seq:
+            self.pairs = [(0, 1, 0)]
+        else:
+            self.pairs = [(0, nB, 0)] if one_dir else None
+        n_in = nB + 1 if seq else nN                                        # frame rows: the network input and the tower
+        n_out = nN if self.pairs is None else nB * len(self.pairs)          # rows of everything behind the tower
+        self.rows = {name: (n_in if name in enc else n_out) for name in B}
+        self.rows['x0'] = n_in
+        self.row0 = {}                    # buffer -> the row that holds the tower's row 0 (absent: 0)
+        if self.seq_bidir and self.is_c:
+            self.rows['cat2'], self.row0['cat2'] = 2 * nB + 1, nB
+        for op in self.ops:
+            if op.kind == 'corr':
+                # (the correlation reads and, backward, writes all rows of c3: both frames' features; one launch per block)
+                op.n = n_in
+            elif self.is_c and op.l.short in ('conv1', 'conv2', 'conv3'):
+                op.n = n_in
+                if seq:
+                    op.n, op.r0, op.d0 = nB, 1 + self.row0.get(op.src[0], 0), 1 + self.row0.get(op.dst[0], 0)
+            else:
+                # (conv_redir reads frame rows of c3: one launch of B rows per block, forward() issues them)
+                op.n = n_out
+        if self.seq_bidir:
             # forward only: no backward plan (its row bands assume that a tensor's later consumers run on no more rows)
             self.bwd, self.bwd_names, self.bwd_zero_rows, self.bwd_post_act = [], [], {}, {}
             self.split_at, self.part_bounds = 0, [0, 0]
-            return
-        if seq:
-            nN = nB + 1
-        self.rows = {name: (nN if (not one_dir or name in enc) else nB) for name in B}
-        self.rows['x0'] = nN
-        for op in self.ops:
-            # (the correlation reads and, backward, writes all rows of c3: both frames' features)
-            op.n = self.rows['c3'] if op.kind == 'corr' else min(self.rows[op.src[0]], self.rows[op.dst[0]])
-            if seq and op.kind == 'layer' and op.dst[0] in enc and op.l.name.split('/')[-1] in ('conv1', 'conv2', 'conv3'):
-                op.n, op.r0 = nB, 1
-            op.d0 = op.r0
-        self._plan_backward()
+        else:
+            self._plan_backward()
 
     # -------------------------------------------------------------- backward plan
     def _plan_backward(self):
@@ -381,7 +408,7 @@ class _Stage:
                         assert a1 == b0, "activation ranges of one data gradient must be contiguous"
                     act_lo, act_hi = rng[0][0], rng[-1][1]
             self.bwd.append((op, first, act_lo, act_hi))
-        names = [op.l.name.split('/')[-1] if op.kind == 'layer' else 'corr' for op, _, _, _ in self.bwd]
+        names = [op.l.short if op.kind == 'layer' else 'corr' for op, _, _, _ in self.bwd]
         self.bwd_names = names
         self.split_at = names.index('conv4') + 1            # part 0 = [0, split_at): decoder + conv6_1 .. conv4
         self.part_bounds = [0, self.split_at, len(self.bwd)]
@@ -397,10 +424,7 @@ class _Stage:
         """Flat range of eng.G holding the filter gradients that are complete after backward(part) (the layers of a part
         are a contiguous run of the forward order, hence of the flat weight region)."""
         ls = [op.l for op, _, _, _ in self.bwd[self.part_bounds[part]:self.part_bounds[part + 1]] if op.kind == 'layer']
-        G = self.eng.G
-        lo = min(l.dw.data_ptr() for l in ls) - G.data_ptr()
-        hi = max(l.dw.data_ptr() + l.dw.numel() * 4 for l in ls) - G.data_ptr()
-        return lo // 4, hi // 4
+        return self.eng.weight_range(ls)
 
     # -------------------------------------------------------------- buffers
     def alloc(self):
@@ -450,18 +474,15 @@ class _Stage:
             x0s = self.act['x0s']
             pf = prev_flow2
             ph, pw = (0, 0) if pf is None else (pf.shape[1], pf.shape[2])
-            if self.seq_bidir:    # both directions of pair i = (frame row i, frame row i + 1): the backward block, then the forward
-                pb, pfw = (None, None) if pf is None else (pf[:B], pf[B:])
-                for first, second, flow, out in ((e.x0[1:], e.x0[:B], pb, x0s[:B]), (e.x0[:B], e.x0[1:], pfw, x0s[B:])):
-                    check(_lib.lib().unflow_stack_input_pair(ptr(first), ptr(second), ptr(flow), ptr(out), x0s.stride(2), B,
-                                                             e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
-            elif e.one_dir:       # one direction: first = im1 rows [0, B), second = im2 rows [B, 2B); sequence: rows [1, B + 1)
-                r1 = 1 if e.sequence else B
-                check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[:B]), ptr(e.x0[r1:]), ptr(pf), ptr(x0s), x0s.stride(2), B,
-                                                         e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()), "stack_input_pair")
-            else:
+            if self.pairs is None:
                 check(_lib.lib().unflow_stack_input(ptr(e.x0), ptr(pf), ptr(x0s), x0s.stride(2), B, N, e.H, e.W, ph, pw,
                                                     cf(4 * FLOW_SCALE), e.stream()), "stack_input")
+            else:
+                for a, b, o in self.pairs:    # first frames at rows [a, a + B), second at [b, b + B), pair rows [o, o + B)
+                    flow = None if pf is None else pf[o:o + B]
+                    check(_lib.lib().unflow_stack_input_pair(ptr(e.x0[a:]), ptr(e.x0[b:]), ptr(flow), ptr(x0s[o:o + B]),
+                                                             x0s.stride(2), B, e.H, e.W, ph, pw, cf(4 * FLOW_SCALE), e.stream()),
+                          "stack_input_pair")
             inp = self.A[self.bin]
             if inp.pl is not None:
                 w_in = pad4(self.in_ch)
@@ -472,31 +493,24 @@ class _Stage:
                 C = op.src[2] - op.src[1]
                 h8, w8 = e.H // 8, e.W // 8
                 pl = self._corr_planes(c3, refresh=True)                      # bf16 x 3 planes: the matrix-core path
-                if self.seq_bidir:    # forward block (rows [B, 2B) of the cost volume): c3[0:B] against c3[1:F]; backward: swapped
-                    for a, b, o in ((1, 0, 0), (0, 1, B)):
-                        p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, a:a + B]), _lib.planes_of(pl[:, b:b + B]))
-                        check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[a:a + B]), ptr(c3.t[b:b + B]), c3.t.stride(2), p0, p1,
-                                                                        0, ptr(out.t[o:o + B]), out.t.stride(2), B, C, h8, w8, 1, 20,
-                                                                        20, 1, 2, e.stream()), "correlation")
-                elif e.one_dir:       # one direction: in0 = features of im1 (rows [0, B)), in1 = of im2 (rows [B, 2B))
-                    r1 = 1 if e.sequence else B           # sequence: the second frame of pair i is row i + 1
-                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, r1:]))
-                    check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[:B]), ptr(c3.t[r1:]), c3.t.stride(2), p0, p1, 0,
-                                                                    ptr(out.t), out.t.stride(2), B, C, h8, w8, 1, 20, 20, 1, 2,
-                                                                    e.stream()), "correlation")
-                else:
+                if self.pairs is None:
                     c3pl = _lib.planes_of(pl)
                     check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t), ptr(c3.t), c3.t.stride(2), c3pl, c3pl, B,
                                                                     ptr(out.t), out.t.stride(2), N, C, h8, w8, 1, 20, 20, 1, 2,
                                                                     e.stream()), "correlation")
+                else:
+                    for a, b, o in self.pairs:    # in0 = the features of the first frames, in1 = of the second frames
+                        p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, a:a + B]), _lib.planes_of(pl[:, b:b + B]))
+                        check(_lib.lib().unflow_correlation_nhwc_fwd_pl(ptr(c3.t[a:a + B]), ptr(c3.t[b:b + B]), c3.t.stride(2), p0, p1,
+                                                                        0, ptr(out.t[o:o + B]), out.t.stride(2), B, C, h8, w8, 1, 20,
+                                                                        20, 1, 2, e.stream()), "correlation")
                 if out.pl is not None:       # operand planes of the cost volume for conv3_1 (pad channels zeroed)
                     L.planes_from_f32(out.t, out.pl)
                 continue
             l = op.l
-            name = l.name.split('/')[-1]
-            if self.seq_bidir and name == 'conv_redir':
-                # the first frame's features of either block: backward rows [0, B) from c3[1:F], forward rows [B, 2B) from c3[0:B]
-                runs = [(1, 0, B), (0, B, B)]
+            if self.pairs is not None and l.short == 'conv_redir':
+                # the first frames' features of every block: B rows of c3 from row a to the block's rows [o, o + B)
+                runs = [(a, o, B) for a, _, o in self.pairs]
             else:
                 runs = [(op.r0, op.d0, op.n)]
             for r0, d0, n in runs:
@@ -509,20 +523,14 @@ class _Stage:
                     L.conv_fwd(x, l.w, l.wpl_t, l.b, y, l.stride, l.act, planes_only=po)
                 else:
                     L.deconv_fwd(x, l.w, l.wpl_d, l.b, y, l.act, planes_only=po)
-            if self.seq_bidir and name == 'conv2' and self.is_c:
+            if self.seq_bidir and l.short == 'conv2' and self.is_c:
                 self.sequence_mirror()
 
     def mirror_list(self):
         """What unflow_sequence_mirror copies in a bidirectional sequence engine: the conv2 segment of cat2, fp32 and every
         operand plane (descriptors relative to cat2's row 0)."""
         lo, n = self.bufs['cat2'][1]['conv2']
-        n = pad4(n)
-        t, pl = self.A['cat2'].t, self.A['cat2'].pl
-        px = t.shape[1] * t.shape[2]
-        bufs = [_lib.CarryBuf(t[0, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4)]
-        for p in ([] if pl is None else range(pl.shape[0])):
-            bufs.append(_lib.CarryBuf(pl[p, 0, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
-        return bufs
+        return _carry_bufs(self.A['cat2'].t, self.A['cat2'].pl, lo, pad4(n))
 
     def sequence_mirror(self):
         """conv2's output of frames 1 .. B (cat2 rows [B + 1, 2B + 1)) -> the backward block's rows [0, B) of cat2: backward
@@ -595,13 +603,11 @@ class _Stage:
                         fn(*a)
                     counter[0] += 1
             pending.clear()
-            if e.wgrad_sync_each:
-                main.wait_stream(side)
 
         # the Cout = 2 layers (flow heads, 2 -> 2 flow upsamplers): their filter gradients leave as ONE batch as soon as the
         # last of them has been visited (all their gradients are final then)
         flow_jobs = []
-        n_flow = sum(1 for op, _, _, _ in self.bwd[lo:hi] if op.kind == 'layer' and op.l.cout <= 2) if e.batch_flow_wgrad else 0
+        n_flow = sum(1 for op, _, _, _ in self.bwd[lo:hi] if op.kind == 'layer' and op.l.cout <= 2)
 
         for k, (op, first, act_lo, act_hi) in enumerate(self.bwd[lo:hi], lo):
             if op.kind == 'corr':
@@ -610,18 +616,21 @@ class _Stage:
                 h8, w8 = e.H // 8, e.W // 8
                 assert first
                 pl = self._corr_planes(c3)                                    # bf16 x 3 planes: feature operand by LDS-DMA
-                if e.supervised:      # separate gradients: grad0 -> d c3[0, B), grad1 -> d c3[B, 2B)
-                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, :B]), _lib.planes_of(pl[:, B:]))
-                    check(_lib.lib().unflow_correlation_nhwc_bwd_pl(ptr(gout.t), gout.t.stride(2), ptr(c3.t[:B]), ptr(c3.t[B:]),
-                                                                    c3.t.stride(2), p0, p1, 0, ptr(g3.t[:B]), ptr(g3.t[B:]),
-                                                                    g3.t.stride(2), 0, B, C, h8, w8, 1, 20, 20, 1, 2, e.stream()),
-                          "correlation_grad")
-                else:
+                if self.pairs is None:
                     c3pl = _lib.planes_of(pl)
                     check(_lib.lib().unflow_correlation_nhwc_bwd_pl(ptr(gout.t), gout.t.stride(2), ptr(c3.t), ptr(c3.t),
                                                                     c3.t.stride(2), c3pl, c3pl, B, ptr(g3.t), ptr(None),
                                                                     g3.t.stride(2), 1, N, C, h8, w8, 1, 20, 20, 1, 2, e.stream()),
                           "correlation_grad")
+                else:
+                    # separate gradients: grad0 -> d c3 of the first frames, grad1 -> of the second frames (the supervised
+                    # engine's one block; the engines of several blocks are forward only)
+                    (a, b, o), = self.pairs
+                    p0, p1 = (None, None) if pl is None else (_lib.planes_of(pl[:, a:a + B]), _lib.planes_of(pl[:, b:b + B]))
+                    check(_lib.lib().unflow_correlation_nhwc_bwd_pl(ptr(gout.t[o:o + B]), gout.t.stride(2), ptr(c3.t[a:a + B]),
+                                                                    ptr(c3.t[b:b + B]), c3.t.stride(2), p0, p1, 0, ptr(g3.t[a:a + B]),
+                                                                    ptr(g3.t[b:b + B]), g3.t.stride(2), 0, B, C, h8, w8, 1, 20, 20, 1, 2,
+                                                                    e.stream()), "correlation_grad")
                 for r0, r1, clo, chi in self.bwd_post_act.get(k, ()):
                     self._leaky_bwd_rows(g3, c3, r0, r1, clo, chi)
                 continue
@@ -633,7 +642,7 @@ class _Stage:
                 e._bias_jobs.append((dz.t, l))       # bias gradients: one batched column-sum launch at the end
             xv = op.src[0] not in self.planes_only      # a planes-only source has no valid fp32 copy: the filter gradient must take the planes
             wg = (L.conv_bwd_filter, (x, dz, l.dw, l.stride, xv)) if l.kind == 'conv' else (L.deconv_bwd_filter, (x, dz, l.dw, xv))
-            if n_flow and l.cout <= 2:
+            if l.cout <= 2:
                 flow_jobs.append((l.kind, x, dz, l.dw))
                 wg = (L.flow_wgrad_batched, (flow_jobs,)) if len(flow_jobs) == n_flow else None
             if wg is None:
@@ -745,12 +754,10 @@ class FlowNetEngine:
         self.wgrad_group = int(os.environ.get('UNFLOW_WGRAD_GROUP', '6'))
         self.wgrad_stream = None
         self.planes_external = False      # True: the captured forward does not re-split the weights (StepRunner does, per bucket)
-        self.wgrad_sync_each = False      # debug: join after every group (no concurrency, still two graph branches)
         self.wgrad_unique_ws = False      # debug: one scratch buffer per deferred filter gradient
         # True: the Cout = 2 layers' filter gradients (flow heads, 2 -> 2 upsamplers: small latency-bound kernels) stay on the main
         # stream; False (default): they join the groups on the second stream like every other filter gradient
         self.wgrad_inline_tiny = False
-        self.batch_flow_wgrad = True      # all Cout = 2 filter gradients of a decoder in one batched launch pair
         self.n_planes = {'bf16x3': 3, 'f16': 1}.get(self.math, 0)
         # UNFLOW_FUSED_ADAM=1: L2 + Adam and the re-split of the updated weights in one pass (csrc/conv_planes.hip
         # adam_planes_kernel; round 6).  Built, bit-identical, and NOT faster: 267.7 / 269.5 us against
@@ -876,9 +883,13 @@ class FlowNetEngine:
             return        # the step runner re-splits each bucket right after its optimizer update, outside the graphs
         if not (force or capturing or self._wplanes_version != self.P._version):
             return
-        n, w, taps, R, Cc, d, t = self._wp_table
-        check(_lib.lib().unflow_weight_planes_batched(n, w, taps, R, Cc, d, t, self.n_planes, self.stream()), "weight_planes")
+        self._split_weights(self._wp_table)
         self._wplanes_version = self.P._version
+
+    def _split_weights(self, table):
+        """One batched launch: the weight tensors of a _wp_table_of() table -> their operand planes, on the current stream."""
+        n, w, taps, R, Cc, d, t = table
+        check(_lib.lib().unflow_weight_planes_batched(n, w, taps, R, Cc, d, t, self.n_planes, self.stream()), "weight_planes")
 
     def refresh_weight_planes_ranges(self, ranges):
         """Re-split the weight tensors that lie in the flat parameter ranges [(lo, hi), ...] on the current stream (the
@@ -893,10 +904,8 @@ class FlowNetEngine:
                      if any(lo <= (l.w.data_ptr() - base) // 4 < hi for lo, hi in ranges)]
             tab = self._wp_table_of(users) if users else (0,)
             self._wp_range_tables[key] = tab
-        if tab[0] == 0:
-            return
-        n, w, taps, R, Cc, d, t = tab
-        check(_lib.lib().unflow_weight_planes_batched(n, w, taps, R, Cc, d, t, self.n_planes, self.stream()), "weight_planes")
+        if tab[0] != 0:
+            self._split_weights(tab)
 
     def init_params(self, seed=0):
         """layers.variance_scaling_initializer() (flownet.py:177): truncated normal, stddev sqrt(1.3*2/fan_in);
@@ -921,22 +930,14 @@ class FlowNetEngine:
         for l in self.layers:
             w = tf_params[l.name + '/weights'].to(self.dev, torch.float32)
             assert tuple(w.shape) == l.tf_wshape(), (l.name, tuple(w.shape), l.tf_wshape())
-            for plo, tlo, n in l.in_map:
-                if l.kind == 'conv':
-                    l.w[:, :, plo:plo + n, :l.cout] = w[:, :, tlo:tlo + n, :]
-                else:
-                    l.w[:, :, :l.cout, plo:plo + n] = w[:, :, :, tlo:tlo + n]
+            l.scatter_tf(l.w, w)
             l.b[:l.cout].copy_(tf_params[l.name + '/biases'].to(self.dev, torch.float32))
         self._wplanes_version = None
 
     def _export(self, wattr, battr):
         out = OrderedDict()
         for l in self.layers:
-            w = getattr(l, wattr)
-            parts = []
-            for plo, tlo, n in l.in_map:
-                parts.append(w[:, :, plo:plo + n, :l.cout] if l.kind == 'conv' else w[:, :, :l.cout, plo:plo + n])
-            out[l.name + '/weights'] = torch.cat(parts, 2 if l.kind == 'conv' else 3).detach().cpu().clone()
+            out[l.name + '/weights'] = l.gather_tf(getattr(l, wattr)).detach().cpu().clone()
             out[l.name + '/biases'] = getattr(l, battr)[:l.cout].detach().cpu().clone()
         return out
 
@@ -961,13 +962,7 @@ class FlowNetEngine:
             for l in self.layers:
                 kw, kb = l.name + '/weights' + suffix, l.name + '/biases' + suffix
                 if kw in tf_slots:
-                    w = tf_slots[kw].to(self.dev, torch.float32)
-                    dst = getattr(l, wa)
-                    for plo, tlo, n in l.in_map:
-                        if l.kind == 'conv':
-                            dst[:, :, plo:plo + n, :l.cout] = w[:, :, tlo:tlo + n, :]
-                        else:
-                            dst[:, :, :l.cout, plo:plo + n] = w[:, :, :, tlo:tlo + n]
+                    l.scatter_tf(getattr(l, wa), tf_slots[kw].to(self.dev, torch.float32))
                 if kb in tf_slots:
                     getattr(l, ba)[:l.cout].copy_(tf_slots[kb].to(self.dev, torch.float32))
 
@@ -994,38 +989,29 @@ class FlowNetEngine:
         self.act.update(last.act)
         self.act.update(x0=self.x0, im01=self.im01)
         self.grad = last.grad
+        self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
+        # the output of final_flows(): one row per pair and direction
+        self.final_flow = z(self.B if self.one_dir else N, H, W, 2)
+        self.lv = []                      # loss-side pyramid: the unsupervised engine alone
         if self.inference:
-            # the output of final_flows() (both directions: N rows); no targets, no loss pyramid, no masks
-            self.lv = []
-            self.final_flow = z(N if self.bidirectional else self.B, H, W, 2)
-            self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
-            self._seq_tab = None
+            self._seq_tab = None          # no targets, no loss, no masks
             return
+        self.loss_acc = z(1)
         if self.supervised:
             # engine-owned targets (fixed addresses for the captured graphs; set_input copies into them); no loss pyramid
             self.flow_gt, self.mask_gt = z(self.B, H, W, 2), z(self.B, H, W, 1)
-            self.lv = []
-            self.loss_acc = z(1)
-            self.final_flow = z(self.B, H, W, 2)
-            self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
-            self.epe_out = z(2)
             return
-        # loss-side pyramid: one level per flow output of the last network (unsupervised.py:85-104)
+        # one level per flow output of the last network (unsupervised.py:85-104)
         self.layer_weights = LAYER_WEIGHTS_FULL_RES if self.full_res else LAYER_WEIGHTS
         self.patch_distances = LAYER_PATCH_DISTANCES_FULL_RES if self.full_res else LAYER_PATCH_DISTANCES
         self.final_flow_scale = FLOW_SCALE * 4 if self.full_res else FLOW_SCALE
-        self.lv = []
         for i, lvl in enumerate(last.flow_levels):
             d = 2 ** lvl
             h, w = H // d, W // d
             im = self.im01 if d == 1 else z(N, h, w, 3)
-            self.lv.append(dict(h=h, w=w, im=im, gray1=z(N, h, w), gray2w=z(N, h, w), dist=z(N, h, w), dgray=z(N, h, w),
+            self.lv.append(dict(h=h, w=w, im=im, gray1=z(N, h, w), gray2w=z(N, h, w), dist=z(N, h, w),
                                 flow=last.act['flow%d' % lvl], gflow=last.grad['flow%d' % lvl],
                                 fs=self.final_flow_scale / (2 ** i), lw=self.layer_weights[i], pd=self.patch_distances[i]))
-        self.loss_acc = z(1)
-        self.final_flow = z(N, H, W, 2)
-        self.mean_host = (_lib.ctypes.c_float * 3)(*CHANNEL_MEAN)
-        self.epe_out = z(2)
 
     def _build_masks(self):
         """create_border_mask(im, 0.1) (losses.py:338-344) then downsample 4, 2, 2, 2, 2 (unsupervised.py:101,147); with
@@ -1071,19 +1057,9 @@ class FlowNetEngine:
             return self._set_input_inference(im1, im2, augment, target)
         if target is not None:
             raise ValueError("set_input: a target is for the supervised engine (FlowNetEngine(..., supervised=True))")
-        # the kernels below take raw device pointers: bring whatever the input pipeline delivers (numpy batches of
-        # core/input.py, host tensors, strided views) to contiguous fp32 on this engine's device — a no-op for a conforming tensor
-        im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
-        im2 = torch.as_tensor(im2).to(device=self.dev, dtype=torch.float32).contiguous()
-        if tuple(im1.shape) != (B, H, W, 3) or tuple(im2.shape) != (B, H, W, 3):
-            raise ValueError("set_input: expected two [%d,%d,%d,3] batches, got %s and %s"
-                             % (B, H, W, tuple(im1.shape), tuple(im2.shape)))
+        im1, im2 = self._device_pair(im1, im2)
         if augment is None:
-            # one launch: both frames -> mean-free network input (+ its operand planes for conv1 of a FlowNetC) and the [0,1]
-            # images of the losses
-            pl = self.X0.pl if (self.X0.pl is not None and self.stages[0].is_c) else None
-            check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(self.im01),
-                                                self.mean_host, _lib.planes_of(pl), st), "prepare_image_pair")
+            self._prepare_image_pair(im1, im2, self.im01, planes=True)
             if self._mask_aug:
                 for lv in self.lv:
                     for b in range(B):
@@ -1095,8 +1071,7 @@ class FlowNetEngine:
             z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)
             self._aug = dict(tmp=z(N, H, W, 3), mg=z(B, H, W, 1), ml=z(B, H, W, 1))
         a = self._aug
-        check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(a['tmp']), self.mean_host,
-                                            None, st), "prepare_image_pair")
+        self._prepare_image_pair(im1, im2, a['tmp'], planes=False)
         tg, tl = augment['theta_global'], augment['theta_local']
         A.transformer(a['tmp'], tg, out=self.im01, n_samples=N)            # im1_geo, first pass of im2 (:40-44)
         A.transformer(self.im01[B:], tl, out=a['tmp'][B:], n_samples=B)    # im2 locally (:47-50)
@@ -1119,11 +1094,7 @@ class FlowNetEngine:
         B, H, W = self.B, self.H, self.W
         lib = _lib.lib()
         st = self.stream()
-        im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
-        im2 = torch.as_tensor(im2).to(device=self.dev, dtype=torch.float32).contiguous()
-        if tuple(im1.shape) != (B, H, W, 3) or tuple(im2.shape) != (B, H, W, 3):
-            raise ValueError("set_input: expected two [%d,%d,%d,3] batches, got %s and %s"
-                             % (B, H, W, tuple(im1.shape), tuple(im2.shape)))
+        im1, im2 = self._device_pair(im1, im2)
         if target is None:
             raise ValueError("set_input: the supervised engine needs target=(flow_gt, mask_gt)")
         flow_gt, mask_gt = target
@@ -1136,20 +1107,15 @@ class FlowNetEngine:
         if mask_gt is None:
             self.mask_gt.fill_(1.0)
         else:
-            mask_gt = torch.as_tensor(mask_gt).to(device=self.dev, dtype=torch.float32).contiguous()
-            if tuple(mask_gt.shape) != (B, H, W, 1):
-                raise ValueError("set_input: mask_gt must be [%d,%d,%d,1], got %s" % (B, H, W, tuple(mask_gt.shape)))
+            mask_gt = self._device_mask_gt(mask_gt)
             check(lib.unflow_copy(ptr(self.mask_gt), ptr(mask_gt), _lib.csz(mask_gt.numel() * 4), st), "copy")
         if augment is None:
-            pl = self.X0.pl if (self.X0.pl is not None and self.stages[0].is_c) else None
-            check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(self.im01),
-                                                self.mean_host, _lib.planes_of(pl), st), "prepare_image_pair")
+            self._prepare_image_pair(im1, im2, self.im01, planes=True)
             return
         # random_photometric of both frames with the SAME per-pair draws (sample n of the 2B rows uses draw n % B), then
         # the mean subtraction (supervised.py:21-35)
         from . import augment as A
-        check(lib.unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(self.im01), self.mean_host,
-                                            None, st), "prepare_image_pair")
+        self._prepare_image_pair(im1, im2, self.im01, planes=False)
         A.photometric(self.im01, augment, out=self.x0, mean=CHANNEL_MEAN)
         self._input_planes()
 
@@ -1163,9 +1129,7 @@ class FlowNetEngine:
         from . import augment as A
         B, H, W = self.B, self.H, self.W
         if mask_gt is not None:
-            mask_gt = torch.as_tensor(mask_gt).to(device=self.dev, dtype=torch.float32).contiguous()
-            if tuple(mask_gt.shape) != (B, H, W, 1):
-                raise ValueError("set_input: mask_gt must be [%d,%d,%d,1], got %s" % (B, H, W, tuple(mask_gt.shape)))
+            mask_gt = self._device_mask_gt(mask_gt)
             if mask_gt.data_ptr() == self.mask_gt.data_ptr():
                 mask_gt = mask_gt.clone()         # the kernel gathers: it cannot read the buffer it writes
         if flow_gt.data_ptr() == self.flow_gt.data_ptr():
@@ -1186,15 +1150,42 @@ class FlowNetEngine:
             raise ValueError("set_input: the inference engine takes neither augmentation draws nor a target")
         if self.sequence:
             raise RuntimeError("set_input: a sequence engine takes frames, not pairs: set_frames(frames, carry)")
+        im1, im2 = self._device_pair(im1, im2)
+        self._prepare_image_pair(im1, im2, None, planes=True)
+
+    def _device_pair(self, im1, im2):
+        """The kernels take raw device pointers: bring whatever the input pipeline delivers (numpy batches of core/input.py,
+        host tensors, strided views) to contiguous fp32 on this engine's device — a no-op for a conforming tensor — and check
+        the shape."""
         B, H, W = self.B, self.H, self.W
         im1 = torch.as_tensor(im1).to(device=self.dev, dtype=torch.float32).contiguous()
         im2 = torch.as_tensor(im2).to(device=self.dev, dtype=torch.float32).contiguous()
         if tuple(im1.shape) != (B, H, W, 3) or tuple(im2.shape) != (B, H, W, 3):
             raise ValueError("set_input: expected two [%d,%d,%d,3] batches, got %s and %s"
                              % (B, H, W, tuple(im1.shape), tuple(im2.shape)))
-        pl = self.X0.pl if (self.X0.pl is not None and self.stages[0].is_c) else None
-        check(_lib.lib().unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(B * H * W), ptr(self.x0), ptr(None), self.mean_host,
-                                                   _lib.planes_of(pl), self.stream()), "prepare_image_pair")
+        return im1, im2
+
+    def _device_mask_gt(self, mask_gt):
+        """_device_pair for the validity mask of a supervised target."""
+        B, H, W = self.B, self.H, self.W
+        mask_gt = torch.as_tensor(mask_gt).to(device=self.dev, dtype=torch.float32).contiguous()
+        if tuple(mask_gt.shape) != (B, H, W, 1):
+            raise ValueError("set_input: mask_gt must be [%d,%d,%d,1], got %s" % (B, H, W, tuple(mask_gt.shape)))
+        return mask_gt
+
+    def network_input_planes(self, r0=0):
+        """Operand planes of the network input from row r0 on — what conv1 of a first-stage FlowNetC reads — or None (no planes
+        in this math mode, or a FlowNetS first: its stages build theirs after stack_input)."""
+        if self.X0.pl is None or not self.stages[0].is_c:
+            return None
+        return self.X0.pl[:, r0:]
+
+    def _prepare_image_pair(self, im1, im2, im01, planes):
+        """One launch: both frames -> the mean-free network input, the [0,1] images im01 of the losses (None: not wanted) and,
+        with planes, conv1's operand planes (without: the caller augments x0 first and calls _input_planes)."""
+        pl = self.network_input_planes() if planes else None
+        check(_lib.lib().unflow_prepare_image_pair(ptr(im1), ptr(im2), cl(self.B * self.H * self.W), ptr(self.x0), ptr(im01),
+                                                   self.mean_host, _lib.planes_of(pl), self.stream()), "prepare_image_pair")
 
     # ------------------------------------------------------------------ sequence engine: rows [1, F) and the carried row 0
     def carry_list(self):
@@ -1202,21 +1193,13 @@ class FlowNetEngine:
         a first-stage FlowNetC, conv3's output and the conv2 segment of cat2 — each as fp32 and as every operand plane.  (c1 is
         read by conv2 alone, on rows [1, F): its row 0 is never read.)  fp16 mode: the correlation's bf16 x 3 side planes are
         re-split from all F fp32 rows of c3 by every forward pass, after the carry."""
-        bufs = []
-
-        def add(t, pl, lo, n, r=0):
-            """channels [lo, lo + n) of the fp32 tensor t [F, h, w, C] and of its planes pl [P, F, h, w, Cp]; r: the row that
-            holds the tower's row 0 (bidirectional sequence engine: cat2 keeps the tower behind the backward block)"""
-            px = t.shape[1] * t.shape[2]
-            bufs.append(_lib.CarryBuf(t[r, 0, 0, lo:].data_ptr(), px, n * 4, t.stride(2) * 4))
-            for p in ([] if pl is None else range(pl.shape[0])):
-                bufs.append(_lib.CarryBuf(pl[p, r, 0, 0, lo:].data_ptr(), px, min(n, pl.shape[-1] - lo) * 2, pl.stride(3) * 2))
-        add(self.x0, None, 0, 4)
+        bufs = _carry_bufs(self.x0, None, 0, 4)
         st = self.stages[0]
         if st.is_c:
             for name, seg in (('c3', 'conv3'), ('cat2', 'conv2')):
                 lo, n = st.bufs[name][1][seg]
-                add(st.A[name].t, st.A[name].pl, lo, pad4(n), st.row0.get(name, 0))
+                # (the row that holds the tower's row 0: the bidirectional sequence engine keeps cat2's behind the backward block)
+                bufs += _carry_bufs(st.A[name].t, st.A[name].pl, lo, pad4(n), st.row0.get(name, 0))
         return bufs
 
     def sequence_carry(self, src_dev):
@@ -1232,9 +1215,9 @@ class FlowNetEngine:
         conv1's operand planes for a first-stage FlowNetC)."""
         if not self.sequence:
             raise RuntimeError("sequence_input: not a sequence engine (FlowNetEngine(..., inference=True, sequence=True))")
-        pl = self.X0.pl[:, 1:] if (self.X0.pl is not None and self.stages[0].is_c) else None
         check(_lib.lib().unflow_inference_input_frames(ptr(frames), ptr(desc), self.B, Hmax, Wmax, self.H, self.W, ptr(self.x0[1:]),
-                                                       self.mean_host, _lib.planes_of(pl), self.stream()), "inference_input_frames")
+                                                       self.mean_host, _lib.planes_of(self.network_input_planes(1)), self.stream()),
+              "inference_input_frames")
 
     def set_frames(self, frames, carry=0):
         """The eager form of one replay's input (tests, tools): carry > 0 first moves row `carry` to row 0, then frames
@@ -1263,8 +1246,9 @@ class FlowNetEngine:
 
     def _input_planes(self):
         """Operand planes of the network input for conv1 of a FlowNetC (FlowNetS stages build theirs after stack_input)."""
-        if self.X0.pl is not None and self.stages[0].is_c:
-            L.planes_from_f32(self.x0, self.X0.pl, C=4)
+        pl = self.network_input_planes()
+        if pl is not None:
+            L.planes_from_f32(self.x0, pl, C=4)
 
     def forward_net(self):
         """flownet(im1, im2, spec, backward_flow=True) (flownet.py:14-81): every stage in order; a refinement stage
@@ -1287,11 +1271,8 @@ class FlowNetEngine:
         st = self.stream()
         N, B = self.N, self.B
         P = self.params
-        wt = lambda k: float(P.get(k + '_weight') or 0.0)
+        wt, occl, use_border, levels, need_fbwarp, need_fwarp, need_mask_terms = self._loss_config()
         check(lib.unflow_zero(ptr(self.loss_acc), _lib.csz(4), st), "zero")
-        occl = {'': 0, None: 0, 'fb': 1, 'disocc': 2}[P.get('mask_occlusion', '')]
-        use_border = bool(P.get('border_mask'))
-        levels = self.lv if P.get('pyramid_loss') else self.lv[:1]
         # image pyramid: downsample(im, 4) then successive downsample(., 2) (unsupervised.py:99-100,145-146); with
         # full_res level 0 is the image itself (unsupervised.py:92-93)
         scales = self._image_and_mask_pyramid_scales()
@@ -1306,9 +1287,6 @@ class FlowNetEngine:
                 if sc != 1:
                     check(lib.unflow_downsample_fwd(ptr(prev_im), ptr(lv['im']), N, ph, pw, 3, sc, st), "downsample")
                 prev_im, ph, pw = lv['im'], lv['h'], lv['w']
-        need_fbwarp = bool(wt('fb')) or occl == 1
-        need_fwarp = bool(wt('sym')) or occl == 2
-        need_mask_terms = need_fbwarp or need_fwarp or bool(wt('occ')) or not use_border
         # the default terms (config.ini [train]: ternary + second-order, border mask): the whole pyramid in four launches
         if (not need_mask_terms and wt('ternary') and wt('smooth_2nd')
                 and not any(wt(k) for k in ('smooth_1st', 'photo', 'grad')) and self.fused_pyramid):
@@ -1341,17 +1319,7 @@ class FlowNetEngine:
             mask, n_mask = lv['mask'], lv['n_mask']
             if need_mask_terms:
                 self._level_extra(lv)
-                warped = fwm = None
-                if need_fbwarp:     # image_warp(flow_other, flow_own) (losses.py:38-39); scaling is linear, applied later
-                    warped = lv['fwarped']
-                    check(lib.unflow_image_warp_fwd(ptr(flow), 2, ptr(flow), cf(fs), ptr(warped), ptr(None), B, N, h, w,
-                                                    2, st), "image_warp(flow)")
-                if need_fwarp:      # forward_warp(flow*scale) (losses.py:28-29), deterministic accumulation
-                    check(lib.unflow_scale(ptr(flow), cf(fs), ptr(lv['fscaled']), cl(flow.numel()), st), "scale")
-                    fwm = lv['fwmap']
-                    ws = lv['fwws']      # this engine's own scratch (see _level_extra), never the shared grow-only one
-                    check(lib.unflow_forward_warp_fwd(ptr(lv['fscaled']), ptr(fwm), N, h, w, 1, ptr(ws),
-                                                      _lib.csz(ws.numel() * 4), st), "forward_warp")
+                warped, fwm = self._mask_inputs(lv, lv, need_fbwarp, need_fwarp)
                 a = acc() if (with_grad and wt('fb')) else 0
                 check(lib.unflow_mask_terms(ptr(flow), ptr(warped), ptr(fwm), ptr(lv['mask'] if use_border else None),
                                             lv['n_mask'],
@@ -1369,8 +1337,7 @@ class FlowNetEngine:
             # ---- data terms
             if wt('ternary'):
                 D = lv['pd']
-                check(lib.unflow_gray_pair(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(lv['gray1']), ptr(lv['gray2w']), B, N, h,
-                                           w, st), "gray_pair")
+                self._gray_pair(lv, lv)
                 check(lib.unflow_ternary_fwd(ptr(lv['gray1']), ptr(lv['gray2w']), ptr(mask), n_mask, ptr(lv['dist']),
                                              ptr(self.loss_acc), cf(lw * wt('ternary')), cf(n1), D, N, h, w, st), "ternary")
                 if with_grad:
@@ -1383,8 +1350,7 @@ class FlowNetEngine:
                                                      w, st), "photometric")
             if wt('grad'):
                 self._level_extra(lv)
-                check(lib.unflow_image_warp_fwd(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(lv['imw']), ptr(None), B, N, h, w,
-                                                3, st), "image_warp(im)")
+                self._warp_image(lv, lv)
                 check(lib.unflow_gradient_loss_fwd(ptr(lv['im']), 3, ptr(lv['imw']), ptr(mask), n_mask, ptr(lv['gdiff']),
                                                    ptr(self.loss_acc), cf(lw * wt('grad')), cf(n1 * 6), N, h, w, st),
                       "gradient_loss")
@@ -1395,10 +1361,13 @@ class FlowNetEngine:
         if with_grad and not P.get('pyramid_loss'):
             for lv in self.lv[1:]:
                 check(lib.unflow_zero(ptr(lv['gflow']), _lib.csz(lv['gflow'].numel() * 4), st), "zero")
-        # regularisation term (value only; its gradient is fused into adam_step)
         if not self.defer_l2:
-            check(lib.unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(self.loss_acc), st), "l2_loss")
+            self._l2_term(self.loss_acc)
         return self.loss_acc
+
+    def _l2_term(self, acc):
+        """Regularisation term (value only; its gradient is fused into adam_step), added to the device float acc."""
+        check(_lib.lib().unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(acc), self.stream()), "l2_loss")
 
     def _forward_loss_supervised(self, with_grad=True):
         """supervised.py:46-62: the last network's final flow (every network's with train_all, weight 1 / 2^i counted from
@@ -1421,7 +1390,7 @@ class FlowNetEngine:
                         g = stg.grad['flow%d' % other]
                         check(lib.unflow_zero(ptr(g), _lib.csz(g.numel() * 4), st), "zero")
         if not self.defer_l2:
-            check(lib.unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(self.loss_acc), st), "l2_loss")
+            self._l2_term(self.loss_acc)
         return self.loss_acc
 
     def _pyramid_levels(self, levels, wt):
@@ -1447,18 +1416,8 @@ class FlowNetEngine:
 
     def _level_extra(self, lv):
         """Buffers only the non-default loss terms need (allocated on first use, before any graph capture)."""
-        if 'maskN' in lv:
-            return
-        N, h, w = self.N, lv['h'], lv['w']
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)
-        lv.update(maskN=z(N, h, w), fwarped=z(N, h, w, 2), gwarped=z(N, h, w, 2), dimtmp=z(N, h, w, 2),
-                  fscaled=z(N, h, w, 2), fwmap=z(N, h, w), imw=z(N, h, w, 3), gdiff=z(N, h, w, 6), dimw=z(N, h, w, 3))
-        # forward_warp's scratch is owned by the engine (sized here, before any capture): the module-global grow-only
-        # workspace of ops.py is shared by every engine of the process — a second, larger engine (Trainer.eval's 1 x 384 x
-        # 1280 one beside a small-crop training engine) would re-allocate it under this engine's captured graphs (ADVICE r5)
-        lib = _lib.lib()
-        lib.unflow_forward_warp_workspace_bytes.restype = _lib.ctypes.c_size_t
-        lv['fwws'] = torch.empty(int(lib.unflow_forward_warp_workspace_bytes(N, h, w, 1)) // 4 + 64, dtype=torch.float32, device=self.dev)
+        if 'maskN' not in lv:
+            lv.update(self._loss_scratch(lv, with_grad=True))
 
     def _terms_scratch(self, lv):
         """loss_terms()'s own buffers of a level (allocated on first use, outside any capture): what forward_loss keeps in
@@ -1466,13 +1425,65 @@ class FlowNetEngine:
         if 'terms' not in lv:
             N, h, w = self.N, lv['h'], lv['w']
             z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)
-            lib = _lib.lib()
-            lib.unflow_forward_warp_workspace_bytes.restype = _lib.ctypes.c_size_t
-            lv['terms'] = dict(gray1=z(N, h, w), gray2w=z(N, h, w), dist=z(N, h, w), maskN=z(N, h, w), fwarped=z(N, h, w, 2),
-                               fscaled=z(N, h, w, 2), fwmap=z(N, h, w), imw=z(N, h, w, 3), gdiff=z(N, h, w, 6),
-                               fwws=torch.empty(int(lib.unflow_forward_warp_workspace_bytes(N, h, w, 1)) // 4 + 64,
-                                                dtype=torch.float32, device=self.dev))
+            lv['terms'] = dict(self._loss_scratch(lv, with_grad=False), gray1=z(N, h, w), gray2w=z(N, h, w), dist=z(N, h, w))
         return lv['terms']
+
+    def _loss_scratch(self, lv, with_grad):
+        """A fresh set of the buffers of a level that the non-default loss terms write; with_grad: and their gradients."""
+        N, h, w = self.N, lv['h'], lv['w']
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)
+        T = dict(maskN=z(N, h, w), fwarped=z(N, h, w, 2), fscaled=z(N, h, w, 2), fwmap=z(N, h, w), imw=z(N, h, w, 3),
+                 gdiff=z(N, h, w, 6))
+        if with_grad:
+            T.update(gwarped=z(N, h, w, 2), dimtmp=z(N, h, w, 2), dimw=z(N, h, w, 3))
+        # forward_warp's scratch is owned by the engine (sized here, before any capture): the module-global grow-only
+        # workspace of ops.py is shared by every engine of the process — a second, larger engine (Trainer.eval's 1 x 384 x
+        # 1280 one beside a small-crop training engine) would re-allocate it under this engine's captured graphs (ADVICE r5)
+        lib = _lib.lib()
+        lib.unflow_forward_warp_workspace_bytes.restype = _lib.ctypes.c_size_t
+        T['fwws'] = torch.empty(int(lib.unflow_forward_warp_workspace_bytes(N, h, w, 1)) // 4 + 64, dtype=torch.float32, device=self.dev)
+        return T
+
+    def _loss_config(self):
+        """What params asks of the loss, for forward_loss and loss_terms alike: (wt, occl, use_border, levels, need_fbwarp,
+        need_fwarp, need_mask_terms) — wt(term): its weight (0.0: off); occl: 0 none, 1 'fb', 2 'disocc'; levels: the pyramid
+        levels that count; need_*: which inputs of unflow_mask_terms are read, and whether it has to run at all."""
+        P = self.params
+        wt = lambda k: float(P.get(k + '_weight') or 0.0)
+        occl = {'': 0, None: 0, 'fb': 1, 'disocc': 2}[P.get('mask_occlusion', '')]
+        use_border = bool(P.get('border_mask'))
+        levels = self.lv if P.get('pyramid_loss') else self.lv[:1]
+        need_fbwarp = bool(wt('fb')) or occl == 1
+        need_fwarp = bool(wt('sym')) or occl == 2
+        need_mask_terms = need_fbwarp or need_fwarp or bool(wt('occ')) or not use_border
+        return wt, occl, use_border, levels, need_fbwarp, need_fwarp, need_mask_terms
+
+    # The forward-only launches of a level that forward_loss and loss_terms share; T: the buffer set they write (the level's own
+    # for the step, _terms_scratch for loss_terms).
+    def _mask_inputs(self, lv, T, need_fbwarp, need_fwarp):
+        """(warped, fwm) of unflow_mask_terms, None where not needed."""
+        lib, st = _lib.lib(), self.stream()
+        N, B, h, w, fs, flow = self.N, self.B, lv['h'], lv['w'], lv['fs'], lv['flow']
+        warped = fwm = None
+        if need_fbwarp:     # image_warp(flow_other, flow_own) (losses.py:38-39); scaling is linear, applied later
+            warped = T['fwarped']
+            check(lib.unflow_image_warp_fwd(ptr(flow), 2, ptr(flow), cf(fs), ptr(warped), ptr(None), B, N, h, w, 2, st),
+                  "image_warp(flow)")
+        if need_fwarp:      # forward_warp(flow*scale) (losses.py:28-29), deterministic accumulation
+            check(lib.unflow_scale(ptr(flow), cf(fs), ptr(T['fscaled']), cl(flow.numel()), st), "scale")
+            fwm = T['fwmap']
+            ws = T['fwws']      # this engine's own scratch (see _loss_scratch), never the shared grow-only one
+            check(lib.unflow_forward_warp_fwd(ptr(T['fscaled']), ptr(fwm), N, h, w, 1, ptr(ws), _lib.csz(ws.numel() * 4), st),
+                  "forward_warp")
+        return warped, fwm
+
+    def _gray_pair(self, lv, T):
+        check(_lib.lib().unflow_gray_pair(ptr(lv['im']), 3, ptr(lv['flow']), cf(lv['fs']), ptr(T['gray1']), ptr(T['gray2w']), self.B,
+                                          self.N, lv['h'], lv['w'], self.stream()), "gray_pair")
+
+    def _warp_image(self, lv, T):
+        check(_lib.lib().unflow_image_warp_fwd(ptr(lv['im']), 3, ptr(lv['flow']), cf(lv['fs']), ptr(T['imw']), ptr(None), self.B,
+                                               self.N, lv['h'], lv['w'], 3, self.stream()), "image_warp(im)")
 
     def loss_terms(self):
         """The terms of the loss that forward_loss (alone, or inside a training step) has just summed, one value each
@@ -1496,15 +1507,8 @@ class FlowNetEngine:
         lib = _lib.lib()
         st = self.stream()
         N, B = self.N, self.B
-        P = self.params
-        wt = lambda k: float(P.get(k + '_weight') or 0.0)
+        wt, occl, use_border, levels, need_fbwarp, need_fwarp, need_mask_terms = self._loss_config()
         on = [k for k in LOSSES if wt(k)]
-        occl = {'': 0, None: 0, 'fb': 1, 'disocc': 2}[P.get('mask_occlusion', '')]
-        use_border = bool(P.get('border_mask'))
-        levels = self.lv if P.get('pyramid_loss') else self.lv[:1]
-        need_fbwarp = bool(wt('fb')) or occl == 1
-        need_fwarp = bool(wt('sym')) or occl == 2
-        need_mask_terms = need_fbwarp or need_fwarp or bool(wt('occ')) or not use_border
         null = ptr(None)
         with torch.cuda.device(self.dev):
             acc = getattr(self, '_terms_acc', None)
@@ -1524,16 +1528,7 @@ class FlowNetEngine:
                                                         N, h, w, st), "smooth_1st")
                 mask, n_mask = lv['mask'], lv['n_mask']
                 if need_mask_terms:
-                    warped = fwm = None
-                    if need_fbwarp:
-                        warped = T['fwarped']
-                        check(lib.unflow_image_warp_fwd(ptr(flow), 2, ptr(flow), cf(fs), ptr(warped), null, B, N, h, w, 2, st),
-                              "image_warp(flow)")
-                    if need_fwarp:
-                        check(lib.unflow_scale(ptr(flow), cf(fs), ptr(T['fscaled']), cl(flow.numel()), st), "scale")
-                        fwm = T['fwmap']
-                        check(lib.unflow_forward_warp_fwd(ptr(T['fscaled']), ptr(fwm), N, h, w, 1, ptr(T['fwws']),
-                                                          _lib.csz(T['fwws'].numel() * 4), st), "forward_warp")
+                    warped, fwm = self._mask_inputs(lv, T, need_fbwarp, need_fwarp)
                     # the mask of the data terms once (no weight), then one launch per enabled term, one weight at a time
                     for k in [None] + [k for k in ('fb', 'occ', 'sym') if wt(k)]:
                         check(lib.unflow_mask_terms(ptr(flow), ptr(warped), ptr(fwm), ptr(lv['mask'] if use_border else None),
@@ -1542,19 +1537,17 @@ class FlowNetEngine:
                                                     cf(k == 'sym'), B, B, N, h, w, st), "mask_terms")
                     mask, n_mask = T['maskN'], N
                 if wt('ternary'):
-                    check(lib.unflow_gray_pair(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(T['gray1']), ptr(T['gray2w']), B, N, h, w,
-                                               st), "gray_pair")
+                    self._gray_pair(lv, T)
                     check(lib.unflow_ternary_fwd(ptr(T['gray1']), ptr(T['gray2w']), ptr(mask), n_mask, ptr(T['dist']),
                                                  slot('ternary'), cf(1.0), cf(n1), lv['pd'], N, h, w, st), "ternary")
                 if wt('photo'):
                     check(lib.unflow_photometric_fwd_bwd(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(mask), n_mask, slot('photo'),
                                                          null, 0, cf(1.0), cf(n1 * 3), B, N, h, w, st), "photometric")
                 if wt('grad'):
-                    check(lib.unflow_image_warp_fwd(ptr(lv['im']), 3, ptr(flow), cf(fs), ptr(T['imw']), null, B, N, h, w, 3, st),
-                          "image_warp(im)")
+                    self._warp_image(lv, T)
                     check(lib.unflow_gradient_loss_fwd(ptr(lv['im']), 3, ptr(T['imw']), ptr(mask), n_mask, ptr(T['gdiff']),
                                                        slot('grad'), cf(1.0), cf(n1 * 6), N, h, w, st), "gradient_loss")
-            check(lib.unflow_l2_loss(ptr(self.P), cl(self.n_weights), cf(L2_SCALE), ptr(acc[len(self.lv), 0]), st), "l2_loss")
+            self._l2_term(acc[len(self.lv), 0])
             host = acc.cpu().double().numpy()
         out_levels = [{k: float(host[i, LOSSES.index(k)]) for k in on} for i in range(len(levels))]
         combined = {k: float(sum(lv['lw'] * host[i, LOSSES.index(k)] for i, lv in enumerate(levels))) if k in on else 0.0
@@ -1583,12 +1576,13 @@ class FlowNetEngine:
         network's coarser flows do not reach the loss directly (only flows[-1] enters it, unsupervised.py:82-83).
         Supervised engine: d flow2 of the previous network already holds its own loss term (the loss launch wrote it, and
         zeroed the other levels); the stage-input gradient is added to it."""
-        if self.supervised:
+        if st.pairs is not None:
             B = self.B
+            (a, b, o), = st.pairs         # (the supervised engine's one block; the engines of several blocks are forward only)
             g2, pf, dx = prev.grad['flow2'], prev.act['flow2'], st.grad['x0s']
-            check(_lib.lib().unflow_stack_input_pair_bwd(ptr(dx), dx.stride(2), ptr(self.x0[:B]), ptr(self.x0[B:]), ptr(pf),
-                                                         ptr(g2), B, self.H, self.W, pf.shape[1], pf.shape[2],
-                                                         cf(4 * FLOW_SCALE), self.stream()), "stack_input_pair_bwd")
+            check(_lib.lib().unflow_stack_input_pair_bwd(ptr(dx[o:o + B]), dx.stride(2), ptr(self.x0[a:]), ptr(self.x0[b:]),
+                                                         ptr(pf[o:o + B]), ptr(g2[o:o + B]), B, self.H, self.W, pf.shape[1],
+                                                         pf.shape[2], cf(4 * FLOW_SCALE), self.stream()), "stack_input_pair_bwd")
             return
         for lvl in prev.flow_levels:
             gz = prev.grad['flow%d' % lvl]
@@ -1637,12 +1631,13 @@ class FlowNetEngine:
         applies the L2 term to them."""
         if self.train_all:
             return []
-        out = []
-        for stg in self.stages[:-1]:
-            lo = min(l.dw.data_ptr() for l in stg.layers) - self.G.data_ptr()
-            hi = max(l.dw.data_ptr() + l.dw.numel() * 4 for l in stg.layers) - self.G.data_ptr()
-            out.append((lo // 4, hi // 4))
-        return out
+        return [self.weight_range(stg.layers) for stg in self.stages[:-1]]
+
+    def weight_range(self, layers):
+        """The flat range of self.G (and P, M, V) that spans the weights of `layers`."""
+        lo = min(l.dw.data_ptr() for l in layers) - self.G.data_ptr()
+        hi = max(l.dw.data_ptr() + l.dw.numel() * 4 for l in layers) - self.G.data_ptr()
+        return lo // 4, hi // 4
 
     def grad_buckets(self):
         """(early, late) flat ranges for the default two-part cut (kept for callers of the two-part API)."""
@@ -1679,8 +1674,8 @@ class FlowNetEngine:
         adam_range() calls (bucketed update: each flat range as soon as its reduced gradient has landed)."""
         self.step_count += 1
         t = self.step_count
-        self._wplanes_version = None
-        return lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+        self._wplanes_version = None       # the parameters change behind torch's back: their operand planes are stale
+        return lr *math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
 
     def adam_range(self, lo, hi, lr_t, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-8):
         """The fused L2 + Adam update of flat range [lo, hi) on the CURRENT stream (weights first in the flat layout: the
@@ -1689,7 +1684,7 @@ class FlowNetEngine:
             return
         nreg = max(0, min(hi, self.n_weights) - lo)
         sl = lambda t: ptr(t[lo:hi])                                        # noqa: E731
-        if self.defer_l2:
+        if self.defer_l2:   # the loss of THIS step gets its regularisation term from the pre-update parameters here
             check(_lib.lib().unflow_adam_step_regloss(sl(self.P), sl(self.G), sl(self.M), sl(self.V), cl(hi - lo), cl(nreg),
                                                       cf(grad_scale), cf(L2_SCALE), cf(lr_t), cf(beta1), cf(beta2), cf(eps),
                                                       ptr(self.loss_acc), self.stream()), "adam")
@@ -1750,23 +1745,12 @@ class FlowNetEngine:
         """tf.train.AdamOptimizer(beta1=0.9, beta2=0.999) update (train.py:151-152), TF formulation, with the
         slim.l2_regularizer(0.0004) gradient added for the weight tensors (biases are not regularised)."""
         self._no_training("adam_step")
-        self.step_count += 1
-        t = self.step_count
-        lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
-        self._wplanes_version = None       # the parameters change behind torch's back: their operand planes are stale
+        lr_t = self.adam_begin(lr, beta1, beta2)
         if self.fused_adam and self.dev.type == 'cuda':
             self.adam_ranges_fused([(0, self.n_params)], lr_t, grad_scale, beta1, beta2, eps)
-            self._wplanes_version = self.P._version        # ... and were re-split by the same launch
+            self._wplanes_version = self.P._version        # the planes were re-split by the same launch
             return
-        if self.defer_l2:   # the loss of THIS step gets its regularisation term from the pre-update parameters here
-            check(_lib.lib().unflow_adam_step_regloss(ptr(self.P), ptr(self.G), ptr(self.M), ptr(self.V),
-                                                      cl(self.n_params), cl(self.n_weights), cf(grad_scale), cf(L2_SCALE),
-                                                      cf(lr_t), cf(beta1), cf(beta2), cf(eps), ptr(self.loss_acc),
-                                                      self.stream()), "adam")
-            return
-        check(_lib.lib().unflow_adam_step(ptr(self.P), ptr(self.G), ptr(self.M), ptr(self.V), cl(self.n_params),
-                                          cl(self.n_weights), cf(grad_scale), cf(L2_SCALE), cf(lr_t), cf(beta1),
-                                          cf(beta2), cf(eps), self.stream()), "adam")
+        self.adam_range(0, self.n_params, lr_t, grad_scale, beta1, beta2, eps)
 
     def check_device_faults(self, world_sync=False):
         """Sticky device-side fault counters of the library, read (and cleared) with a host sync: the bounded spins of the

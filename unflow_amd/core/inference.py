@@ -439,7 +439,7 @@ class FlowEstimator:
                 self.vis_max = z(3 * B, dtype=torch.int32)           # bit patterns of max |flow|, max |gt * mask|; B tickets
         last = e.stages[-1]
         self.flow_src = last.act['flow0'] if e.full_res else last.act['flow2']     # bidirectional: rows [0, B) fw, [B, 2B) bw
-        self.in_planes = e.X0.pl if (e.X0.pl is not None and e.stages[0].is_c) else None
+        self.in_planes = e.network_input_planes()
         self.slots = None
         self.graph = None
         self.global_step = None
