@@ -761,6 +761,57 @@ int unflow_sequence_visual(const void* frames, const int* tab, int B, int Hmax, 
                            const float* flow_bw, const unsigned char* occ_fw, float* shown, unsigned* max_bits,
                            unsigned char* out_u8, float* out_f32, unflow_stream_t stream);
 
+/* In-between frames along a clip (FlowEstimator(..., sequence=True | 'bidirectional', interpolate=n); csrc/interpolate.hip,
+ * DESIGN 7.16): n frames, 1 <= n <= 7, between the two frames of every valid pair of one sequence replay, motion-compensated:
+ * the colours of frame 0 are splatted forward along the forward flow and, with both directions, those of frame 1 along the
+ * backward flow; the sums are normalised by the splatted weight.  This definition is part of the ABI; tests/mid_ref.py mirrors it
+ * step by step and the kernels are held to equality.
+ * Setting.  tab: the DEVICE int32 tables of the replay (sequence_tables), read on the device, so a captured graph keeps addresses
+ * only: frame table [B][8] at word 0, pair table [B][8] at word 8B (a slot with h = 0, or with h > Hmax or w > Wmax, is not a
+ * pair; neither is slot 0 while the carry source is 0), the carry source at word 16B.  frames [B][Hmax][Wmax][3]: the up to B NEW
+ * staged frames, uint8 or fp32 in [0, 255] per the tables' u8 field, taken as fp32 — the staged frames, not the resampled "shown"
+ * ones.  Pair slot i of size (h, w), rows Wmax apart: im0 = staged frame i - 1 (slot 0: prev), im1 = staged frame i, fw =
+ * flow_fw[i] ([B][Hmax][Wmax][2], unflow_inference_output).  Both directions: bw = flow_bw[i] and occ_fw / occ_bw [B][Hmax][Wmax]
+ * uint8, the two masks of unflow_inference_occlusion; flow_bw, occ_fw, occ_bw are all given or all NULL.  In-between frame j =
+ * 1..n is at t = (float)j / (float)(n + 1), with s = (float)(n + 1 - j) / (float)(n + 1), both fp32.
+ * Arithmetic.  Every fp32 product and sum is rounded on its own (the library is built with -ffp-contract=off); all weights and all
+ * sums are integers.
+ * Pass A, for every pixel (x, y) of frame 0:
+ *   (u, v) = fw(x, y); a component that is not finite, or of magnitude >= 1e6, contributes nothing — tested before any conversion
+ *     to an integer, as unflow_sequence_track does;
+ *   c1 = image_warp(im1, fw)(x, y): csrc/image_warp.h's taps, clamped to (h, w), tap order ((wa*a + wb*b) + wc*c) + wd*d;
+ *   c = im0(x, y) where occ_fw(x, y) != 0 (both directions only; c1 is then not read), otherwise c = s * im0(x, y) + t * c1;
+ *   cq = (long)rintf(min(max(c, 0), 255) * 256) per channel;
+ *   px = (float)x + t * u, ix = (int)floorf(px), qx = (int)((px - floorf(px)) * 64), a 6-bit fraction; likewise in y;
+ *   the four targets (ix + dx, iy + dy) get the tap weight W = wx * wy * a, wx = 64 - qx for dx = 0 and qx for dx = 1, wy
+ *     likewise, a = n + 1 - j; a target outside [0, w) x [0, h), or of weight 0, is dropped — not clamped;
+ *   each kept target adds W * cq to its three colour sums and W to its weight sum, 64-bit integers.
+ * Pass B, both directions only, for every pixel of frame 1, the roles swapped: (u, v) = bw(x, y); c0 = image_warp(im0, bw)(x, y);
+ *   c = im1(x, y) where occ_bw != 0, otherwise s * c0 + t * im1(x, y); position (float)x + s * u; direction weight a = j.
+ * Normalise, per target pixel with weight sum Sw and colour sums Sc:
+ *   Sw >= 1024: out = (Sc + Sw * 128) / (Sw * 256) by integer division, per channel;
+ *   Sw < 1024, a HOLE (less than a quarter of one source pixel's weight in the weaker direction): the temporal blend
+ *     ((n + 1 - j) * q(im0) + j * q(im1) + (n + 1) * 128) / ((n + 1) * 256), q the quantisation of cq; it is counted.
+ * Outputs: out_mid [n][B][Hmax][Wmax][3] uint8, frame j of pair slot i at [j - 1][i]; out_holes [n][B] int32, the exact number of
+ * holes.  Nothing is written for slots that are not pairs, nor outside (h, w).
+ * prev [Hmax][Wmax][3] in the staged dtype (Hmax * Wmax * 12 bytes hold either), kept by the caller from one replay of a clip to
+ * the next: the host overwrites frames before each replay, so a launch of its own, BEHIND the splat and the normalisation, copies
+ * the (h, w) corner of the last frame-table slot with h > 0 into prev.  The copy depends on frames and tab alone, so an estimator's
+ * first replay ever, which runs the entry twice (the eager pass, then the captured graph's first replay), gives what one run
+ * gives.  prev is never read while the carry source is 0, and needs no initialisation.
+ * workspace: unflow_sequence_interpolate_workspace_bytes(n, B, Hmax, Wmax) bytes (0 for arguments the entry refuses), 16-byte
+ * aligned: the sums, four 64-bit integers per pixel of out_mid.  Zero on entry and left zero by every launch — the normalisation
+ * cleans what it reads, graph replays included, no memset node (the convention of the stream-K flags and max_bits).
+ * Deterministic: integer atomics only, no float atomics; the order of arrival cannot change a bit.
+ * Known limits: a foreground and a background that collide in a target are averaged, there is no depth order; holes are filled by
+ * the temporal blend, not inpainted.
+ * UNFLOW_ERR_SHAPE, and nothing is launched, for n outside 1..7, B < 1, Hmax or Wmax < 1, Hmax * Wmax above 2^31 - 1, or flow_bw /
+ * occ_fw / occ_bw neither all given nor all NULL. */
+size_t unflow_sequence_interpolate_workspace_bytes(int n, int B, int Hmax, int Wmax);
+int unflow_sequence_interpolate(const void* frames, const int* tab, int B, int Hmax, int Wmax, int n, const float* flow_fw,
+                                const float* flow_bw, const unsigned char* occ_fw, const unsigned char* occ_bw, void* prev,
+                                void* workspace, unsigned char* out_mid, int* out_holes, unflow_stream_t stream);
+
 /* ===================================================================== */
 /* PNG decode on the device (csrc/png_decode.hip, core/png_device.py)      */
 /* ===================================================================== */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track]
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
 of the replayed graph of FlowEstimator(..., sequence=True) in its steady state (a carried frame and B new frames: B pairs per
@@ -25,7 +25,13 @@ tracking estimator, of the same estimator without tracks, and of the host altern
 launches and B adds outside it (no visibility) — the three taken in turn, `--rounds` times, in one process; the flow heads are
 scaled down so that the tracks stay alive and the kernel does its whole work in every replay (the share alive is reported).  Beside
 them the track kernel alone (device events around 50 launches) with the bytes it must move, and the parent commit's recorded
-lines for the same estimators without tracks (profiles/sequence_bench_line.json, profiles/sequence_bidir_bench_line.json)."""
+lines for the same estimators without tracks (profiles/sequence_bench_line.json, profiles/sequence_bidir_bench_line.json).
+
+--interpolate N: FlowNetC at B = 4, both sequence modes, N in-between frames per pair: ms per pair of the replayed
+graph of the interpolating estimator against the same run's estimator without the option (the two take turns), and alone — device
+events around 50 launches — unflow_sequence_interpolate and the replay's output kernels (unflow_inference_output, with both
+directions twice and unflow_inference_occlusion), with the atomic bytes the splat issues.  Recorded, one line per N, in
+profiles/sequence_interpolate_bench_line.json."""
 import argparse
 import csv
 import glob
@@ -50,7 +56,7 @@ def _frames(n):
     return [np.roll(a, 2 * i, 1) for i in range(n)]
 
 
-def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None):
+def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
     pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
@@ -64,6 +70,8 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False
     kw = dict(visual='sequence' if sequence else True) if visual else {}
     if track is not False:
         kw['track'] = track
+    if interpolate:
+        kw['interpolate'] = interpolate
     est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
@@ -405,6 +413,75 @@ def track_case(seq, iters, warmup, rounds, B=4):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --interpolate
+def _launches_us(fn, dev, n=50, warm=10):
+    """us per call of fn: device events around n back-to-back calls, launch gaps included."""
+    import torch
+    with torch.cuda.device(dev):
+        for _ in range(warm):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        b.synchronize()
+    return a.elapsed_time(b) * 1e3 / n
+
+
+def interpolate_case(seq, n, iters, warmup, rounds, B=4):
+    import gc
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    plain, _ = _estimator('C', B, seq)
+    mid, mem = _estimator('C', B, seq, interpolate=n)
+    mid.interpolate_sequence(_frames(3 * B))               # the tables of the last replay: a carried frame, B pairs
+    runs = {'plain': plain.graph.replay, 'interpolate': mid.graph.replay}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence=seq if seq is True else str(seq), n=n, rounds=rounds)
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['interpolate']['estimator_MB'] = round(mem / 1e6, 1)
+    out['interpolate_over_plain'] = round(out['interpolate']['ms_per_pair'] / out['plain']['ms_per_pair'], 4)
+    out['interpolate_added_us_per_replay'] = round((out['interpolate']['ms_per_pair'] - out['plain']['ms_per_pair']) * B * 1e3, 2)
+    L, e = _lib.lib(), mid
+    bw, ofw, obw = (e.out_flow_bw, e.occ[0], e.occ[1]) if e.seq_bidir else (None, None, None)
+
+    def kernel():
+        check(L.unflow_sequence_interpolate(ptr(e.frames), ptr(e.tab), B, e.Hmax, e.Wmax, n, ptr(e.out_flow), ptr(bw), ptr(ofw),
+                                            ptr(obw), ptr(e.mid_prev), ptr(e.mid_sums), ptr(e.out_mid), ptr(e.out_mid_holes),
+                                            e.engine.stream()), "sequence_interpolate")
+
+    def outputs():
+        pairs = e.tab[8 * B:]
+        if e.seq_bidir:
+            fw_rows, bw_rows = e.engine.fw_bw(e.flow_src)
+            e._output(fw_rows, pairs, e.out_flow, e.out_u16)
+            e._output(bw_rows, pairs, e.out_flow_bw, e.out_u16_bw)
+            e._occlusion(pairs)
+        else:
+            e._output(e.flow_src, pairs, e.out_flow, e.out_u16)
+    us, us_out = _launches_us(kernel, e.dev), _launches_us(outputs, e.dev)
+    px, dirs = FRAME[0] * FRAME[1] * B, 2 if e.seq_bidir else 1
+    atomic_bytes = px * n * dirs * 128                     # 4 targets x 4 sums x 8 bytes per source pixel, j and direction, at most
+    out['kernel'] = dict(us=round(us, 2), launches=3, atomic_MB=round(atomic_bytes / 1e6, 1),
+                         atomic_TBps_if_all_of_it=round(atomic_bytes / us / 1e6, 3),
+                         how='device events around 50 back-to-back calls of the entry (three launches each), launch gaps included')
+    out['output_kernels'] = dict(us=round(us_out, 2), how='the same, unflow_inference_output (x 2 and unflow_inference_occlusion with '
+                                                          'both directions)')
+    out['kernel_over_output_kernels'] = round(us / us_out, 3)
+    out['holes_share'] = round(float(e.out_mid_holes.float().sum().item()) / (px * n), 5)
+    del plain, mid
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -420,8 +497,19 @@ def main():
     ap.add_argument('--track', action='store_true',
                     help='the tracking estimator against the same one without tracks and against image_warp launches behind '
                          'the graph, FlowNetC at B = 4, both sequence modes (DESIGN 7.15)')
-    ap.add_argument('--rounds', type=int, default=3, help='--track: how often the compared estimators take turns')
+    ap.add_argument('--rounds', type=int, default=3, help='--track, --interpolate: how often the compared estimators take turns')
+    ap.add_argument('--interpolate', type=int, default=None, metavar='N',
+                    help='the estimator with N in-between frames per pair against the same one without, FlowNetC at B = 4, both '
+                         'sequence modes, and the kernels alone (DESIGN 7.16)')
     a = ap.parse_args()
+    if a.interpolate is not None:
+        res = dict(metric='sequence_interpolate_ms_per_pair_over_the_same_estimator_without_it', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup, n=a.interpolate,
+                   expected='no ratio was predicted: the rate of 64-bit integer global atomics on this part was unmeasured when the '
+                            'kernel was written',
+                   cases=[interpolate_case(seq, a.interpolate, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
+        print(json.dumps(res))
+        return
     if a.track:
         res = dict(metric='sequence_track_ms_per_pair_over_the_same_estimator_without_tracks', shape=[H, W],
                    frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup,

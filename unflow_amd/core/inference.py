@@ -59,6 +59,15 @@ occlusion) kernels either sequence graph runs
 
 (push_tracks, track_sequence, export_sequence(tracks=True)); the grid stride and the number of tracks travel in the tables.
 
+sequence=True | 'bidirectional' with interpolate=n: n in-between frames per pair.  Behind the output (and occlusion,
+and track) kernels either sequence graph runs
+
+    unflow_sequence_interpolate    the staged frames, the forward flow (bidirectional: and the backward flow and both occlusion
+                                   masks) -> per pair n motion-compensated frames, an integer splat normalised by its weight, and
+                                   the count of the holes; the clip's last staged frame stays on the device for the next replay
+
+(push_interpolated, interpolate_sequence, export_sequence(interpolate=True)).
+
 The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
 _submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
 leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
@@ -111,6 +120,9 @@ def sequence_visual_files(n, bidirectional):
 # its displacement from the anchor, and alive bool, still in the frame and never occluded — [gh, gw, 2] and [gh, gw] for the dense
 # grid, [N, 2] and [N] for sparse anchors
 Track = collections.namedtuple('Track', ('disp', 'alive'))
+# What push_interpolated returns per pair (n, n + 1): frames uint8 [n_mid, h, w, 3], the in-between frames j = 1..n_mid at time
+# j / (n_mid + 1), and holes int [n_mid], the pixels of each that no source reached (filled with the temporal blend)
+Interpolated = collections.namedtuple('Interpolated', ('frames', 'holes'))
 TRACK_DEAD = 1e10          # a dead track in %06d_track.flo: the .flo unknown-flow convention (read back as mask = 0)
 
 
@@ -145,7 +157,17 @@ def track_grid(shape, stride):
     return (-(-int(shape[0]) // int(stride)), -(-int(shape[1]) // int(stride)))
 
 
-def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False):
+def interpolate_option(interpolate):
+    """FlowEstimator's interpolate option -> the number of in-between frames per pair: 0 (None or False: none) or an int n in
+    1..7.  Anything else: ValueError."""
+    if interpolate is None or interpolate is False:
+        return 0
+    if isinstance(interpolate, bool) or not isinstance(interpolate, (int, np.integer)) or not 1 <= int(interpolate) <= 7:
+        raise ValueError("FlowEstimator: interpolate=n is an int, 1 to 7 in-between frames per pair, got %r" % (interpolate,))
+    return int(interpolate)
+
+
+def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False, mid=0):
     """The files export / export_sequence write for pair n, in the order they are written — _10, _01, _10_occ, then the pictures
     (visual_files' or sequence_visual_files' list) in their file order: [(file name, source)].  A source is
 
@@ -154,6 +176,9 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False
         ('flo', attribute)    a .flo file of row i of that pinned flow of the slot: 'flow', 'flow_bw';
         ('track', attribute)  track: the dense tracks of row i on their grid, %06d_track.flo (FlowEstimator._track_flo), last.
 
+    mid: the in-between frames j = 1..mid of the pair, %06d_mid%d.png (pair, j), PNGs of image (j - 1) * B + i of the surface
+    'mid', behind the pictures.
+
     Both back ends of FlowEstimator._write_files and the entries of the replay's unflow_png_filter launch (filter_entries) come
     from this one list, so the span order and the file order cannot drift apart."""
     flows = [('10', 'u16', 'flow')] + ([('01', 'u16_bw', 'flow_bw')] if backward else [])
@@ -161,6 +186,7 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False
     if occlusion:
         out.append(('%06d_10_occ.png' % n, ('png', 'occ', 0)))
     return out + [(name, ('png', 'vis', k)) for k, name in pictures] + \
+        [('%06d_mid%d.png' % (n, j), ('png', 'mid', j - 1)) for j in range(1, int(mid) + 1)] + \
         ([('%06d_track.flo' % n, ('track', 'track_disp'))] if track else [])
 
 
@@ -270,10 +296,11 @@ def chunks(it, n):
         yield buf
 
 
-def output_buffers(B, Hm, Wm, Ncap=0):
+def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0):
     """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
     and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
-    estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator."""
+    estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator; n_mid: the
+    in-between frames per pair of an interpolating one."""
     return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
             ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
             ('sums', 'sums', (B, 2, 2), torch.float64, None),
@@ -284,7 +311,9 @@ def output_buffers(B, Hm, Wm, Ncap=0):
             ('occ_counts', 'occ_counts', (B, 3), torch.int32, 'bidirectional'),
             ('vis', 'vis', (len(VISUAL_IMAGES), B, Hm, Wm, 3), torch.uint8, 'visual'),
             ('track_disp', 'out_track_disp', (B, Ncap, 2), torch.float32, 'track'),
-            ('track_alive', 'out_track_alive', (B, Ncap), torch.uint8, 'track'))
+            ('track_alive', 'out_track_alive', (B, Ncap), torch.uint8, 'track'),
+            ('mid', 'out_mid', (n_mid, B, Hm, Wm, 3), torch.uint8, 'interpolate'),
+            ('mid_holes', 'out_mid_holes', (n_mid, B), torch.int32, 'interpolate'))
 
 
 class _Slot:
@@ -298,7 +327,7 @@ class _Slot:
         self.desc = pin(B, 8, dtype=torch.int32)
         self.tab = pin(16 * B + 4, dtype=torch.int32) if est.sequence else None   # sequence_tables
         self.gt_flow = self.gt_mask = None
-        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap):
+        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate):
             setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
         self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
@@ -339,6 +368,8 @@ class _Encoder:
             named += [('u16_bw', est.out_u16_bw, B, 3, _lib.PNG_U16BE), ('occ', est.occ[0], B, 1, _lib.PNG_U8X255)]
         if est.visual:
             named += [('vis', est.vis, len(VISUAL_IMAGES) * B, 3, _lib.PNG_U8)]
+        if est.interpolate:
+            named += [('mid', est.out_mid, est.interpolate * B, 3, _lib.PNG_U8)]
         self.index = {name: k for k, (name, *_) in enumerate(named)}
         self.surfaces = [PngSurface(t, images, Hm, Wm, ch, kind) for _, t, images, ch, kind in named]
         n_files = sum(s.images for s in self.surfaces)
@@ -371,10 +402,15 @@ class FlowEstimator:
     estimator also: never under the forward occlusion mask).  True: an anchor at every pixel; an int S >= 1: at every S-th pixel
     of every S-th row; an int array [N][2]: at those (x, y).  push_tracks / track_sequence return a Track(disp, alive) per pair,
     export_sequence(tracks=True) writes them; every other method returns what it returns without track.  reset() starts a new
-    anchor frame."""
+    anchor frame.
+    interpolate (with sequence): n in 1..7 in-between frames per pair of the clip, motion-compensated on the device from the
+    staged frames and the flows (both directions and the occlusion masks on a sequence='bidirectional' estimator).
+    push_interpolated / interpolate_sequence return an Interpolated(frames, holes) per pair, export_sequence(interpolate=True)
+    writes them; every other method returns what it returns without interpolate.  reset() starts a new clip: the frame kept
+    from the last one is not used."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
-                 visual=False, sequence=False, track=False):
+                 visual=False, sequence=False, track=False, interpolate=None):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -393,6 +429,10 @@ class FlowEstimator:
             raise ValueError("FlowEstimator: track follows the pixels of a clip's first frame; it needs sequence=True or "
                              "sequence='bidirectional'")
         self.track = self.track_spec is not None
+        self.interpolate = interpolate_option(interpolate)       # in-between frames per pair; 0: none
+        if self.interpolate and not sequence:
+            raise ValueError("FlowEstimator: interpolate makes the frames between the frames of a clip; it needs sequence=True or "
+                             "sequence='bidirectional'")
         self.sequence = bool(sequence)
         self.seq_bidir = sequence == 'bidirectional'
         self.params = dict(params)
@@ -424,7 +464,7 @@ class FlowEstimator:
             nb = int(L.unflow_inference_output_blocks(Hm, Wm))
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
-            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap):   # out_flow, out_u16, sums, counts, ...
+            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate):   # out_flow, out_u16, ...
                 setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
             self.track_anchors = self.track_disp = self.track_alive = None
             if self.track:
@@ -432,6 +472,13 @@ class FlowEstimator:
                 self.track_disp, self.track_alive = z(self.track_cap, 2), z(self.track_cap, dtype=torch.uint8)
                 if self.track_spec[0] == 'sparse':
                     self.track_anchors = torch.from_numpy(self.track_spec[1]).to(self.dev)
+            self.mid_prev = self.mid_sums = None
+            if self.interpolate:
+                # unflow_sequence_interpolate: the clip's last staged frame, kept from one replay to the next (fp32-sized), and the
+                # 64-bit sums, zero now and left zero by every launch
+                self.mid_prev = z(Hm * Wm * 3 * 4, dtype=torch.uint8)
+                self.mid_sums = z(int(L.unflow_sequence_interpolate_workspace_bytes(self.interpolate, B, Hm, Wm)) // 8,
+                                  dtype=torch.int64)
             self.vis_shown = self.vis_max = None
             if self.visual:
                 # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
@@ -496,8 +543,8 @@ class FlowEstimator:
     def _launch_sequence(self):
         """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds);
         sequence='bidirectional': the output kernel on either block of the engine's 2B rows, then the occlusion kernel, all
-        three over the pair table and without ground truth; track: then the tracks, through the pairs of the table; visual: then
-        the pictures, from the same tables."""
+        three over the pair table and without ground truth; track: then the tracks, through the pairs of the table; interpolate:
+        then the in-between frames of those pairs; visual: then the pictures, from the same tables."""
         e, B = self.engine, self.B
         L = _lib.lib()
         e.sequence_carry(self.tab[16 * B:])
@@ -516,6 +563,12 @@ class FlowEstimator:
                                           self.Hmax, self.Wmax, ptr(self.track_anchors), self.track_cap, ptr(self.track_disp),
                                           ptr(self.track_alive), ptr(self.out_track_disp), ptr(self.out_track_alive),
                                           e.stream()), "sequence_track")
+        if self.interpolate:
+            bw, ofw, obw = (self.out_flow_bw, self.occ[0], self.occ[1]) if self.seq_bidir else (None, None, None)
+            check(L.unflow_sequence_interpolate(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate,
+                                                ptr(self.out_flow), ptr(bw), ptr(ofw), ptr(obw), ptr(self.mid_prev),
+                                                ptr(self.mid_sums), ptr(self.out_mid), ptr(self.out_mid_holes), e.stream()),
+                  "sequence_interpolate")
         if self.visual:
             bw, occ = (self.out_flow_bw, self.occ[0]) if self.seq_bidir else (None, None)
             check(L.unflow_sequence_visual(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.H, self.W,
@@ -709,7 +762,7 @@ class FlowEstimator:
         truth was staged, the occlusion counts only when it had two maps."""
         special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
         nv = self._num_pictures(nmaps)
-        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap):
+        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate):
             if special.get(name, name in want):
                 dst, src = getattr(slot, name), getattr(self, attr)
                 if name == 'vis':
@@ -751,7 +804,7 @@ class FlowEstimator:
         return self._one_ahead(self._submit(k, exs, staged, nmaps_of(exs), want, files=files) for k, exs in enumerate(batches))
 
     # ------------------------------------------------------------------------------------------ public API
-    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False):
+    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False):
         """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
         one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
         if not sequence:
@@ -774,6 +827,9 @@ class FlowEstimator:
             raise RuntimeError("%s: a sequence estimator without tracks; build it with FlowEstimator(..., sequence=%r, track=True) "
                                "(or track=S, a grid stride, or track=anchors, an int array [N][2] of (x, y))"
                                % (what, 'bidirectional' if self.seq_bidir else True))
+        if interpolate and not self.interpolate:
+            raise RuntimeError("%s: a sequence estimator without in-between frames; build it with FlowEstimator(..., sequence=%r, "
+                               "interpolate=n), n in 1..7" % (what, 'bidirectional' if self.seq_bidir else True))
 
     def _visual_spelling(self):
         """How to build this sequence estimator with pictures, for the messages that ask for it."""
@@ -1059,6 +1115,8 @@ class FlowEstimator:
                             write_png_gray8(path, slot.occ.numpy()[0, i, :h, :w] * np.uint8(255))
                         elif attr == 'vis':
                             write_png_rgb8(path, slot.vis.numpy()[k[0], i, :h, :w])
+                        elif attr == 'mid':
+                            write_png_rgb8(path, slot.mid.numpy()[k[0], i, :h, :w])
                         else:
                             write_kitti_flow_png(path, getattr(slot, attr).numpy()[i, :h, :w].view(np.uint16))
                         paths.append(path)
@@ -1240,6 +1298,30 @@ class FlowEstimator:
             out += self._tracks_of(slot, rows)
         return out
 
+    # in-between frames
+    @staticmethod
+    def _interpolated_of(slot, rows):
+        """The rows of a finished interpolating replay as Interpolated tuples (copies)."""
+        m, hl = slot.mid.numpy(), slot.mid_holes.numpy()
+        return [Interpolated(m[:, i, :h, :w].copy(), hl[:, i].astype(np.int64)) for i, h, w in rows]
+
+    def push_interpolated(self, frames):
+        """push's frames on an estimator built with interpolate=n: one Interpolated(frames, holes) per new pair (the count is
+        push's).  For the pair (k, k + 1), frames is uint8 [n, h, w, 3], in-between frame j = 1..n at time j / (n + 1) between the
+        two staged frames — frame k's colours splatted along the forward flow and, on a sequence='bidirectional' estimator, frame
+        k + 1's along the backward flow, occluded pixels unblended (unflow_sequence_interpolate) — and holes int [n], the pixels of
+        each that no source reached and the temporal blend of the two frames fills.  Bit-reproducible from run to run."""
+        self._mode('push_interpolated', sequence=True, interpolate=True)
+        return self._interpolated_of(*self._push(frames, ('mid', 'mid_holes')))
+
+    def interpolate_sequence(self, frames):
+        """In-between frames along a clip: T >= 2 frames -> T - 1 Interpolated tuples (push_interpolated's)."""
+        self._mode('interpolate_sequence', sequence=True, interpolate=True)
+        out = []
+        for slot, rows, _ in self._pipeline_sequence(frames, ('mid', 'mid_holes')):
+            out += self._interpolated_of(slot, rows)
+        return out
+
     def _pipeline_sequence(self, frames, want, files=None, max_flow=None):
         """reset, then _one_ahead over pushes of B frames."""
         self.reset()
@@ -1263,7 +1345,7 @@ class FlowEstimator:
         return out
 
     def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False,
-                        visual=False, max_flow=None, tracks=False):
+                        visual=False, max_flow=None, tracks=False, interpolate=False):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
         writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
@@ -1278,7 +1360,9 @@ class FlowEstimator:
         tracks (an estimator built with track): the tracks of push_tracks.  Dense: after a pair's other files %06d_track.flo,
         the displacement from frame 0 to frame n + 1 on the gh x gw anchor grid, a dead track written as (1e10, 1e10) — the
         .flo unknown-flow value, read back as mask = 0 — through the same writer as the other .flo files.  Sparse anchors: one
-        tracks.npz behind the last pair's files, with anchors [N, 2] int32, disp [T - 1, N, 2] float32, alive [T - 1, N] bool."""
+        tracks.npz behind the last pair's files, with anchors [N, 2] int32, disp [T - 1, N, 2] float32, alive [T - 1, N] bool.
+        interpolate (an estimator built with interpolate=n): the in-between frames of push_interpolated, %06d_mid%d.png (pair, j =
+        1..n), 8-bit RGB, behind a pair's pictures — through either writer, the same pixels."""
         from .png_device import check_deflate_mode
         self._mode('export_sequence', sequence=True)
         if tracks and not self.track:
@@ -1291,12 +1375,15 @@ class FlowEstimator:
             raise ValueError("export_sequence: backward / occlusion files need FlowEstimator(..., sequence='bidirectional')")
         if visual and not self.visual:
             raise ValueError("export_sequence: the pictures need %s" % self._visual_spelling())
+        if interpolate and not self.interpolate:
+            raise ValueError("export_sequence: the in-between frames need FlowEstimator(..., sequence=%r, interpolate=n)"
+                             % ('bidirectional' if self.seq_bidir else True))
         if max_flow is not None and not visual:
             raise ValueError("export_sequence: max_flow scales the flow colours of the pictures; it needs visual=True")
 
         def plan(n, nmaps):
             return pair_files(n, fmt, backward, occlusion, sequence_visual_files(n, self.seq_bidir) if visual else (),
-                              track=dense)
+                              track=dense, mid=self.interpolate if interpolate else 0)
         dense = bool(tracks) and self.track_spec[0] == 'dense'
         sparse = [] if tracks and not dense else None      # sparse anchors: the Track of every pair, for tracks.npz
 

@@ -3,7 +3,7 @@ once (core/inference.FlowEstimator(..., sequence=True)).
 
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
                                   [--output_backward] [--occlusion] [--visual] [--max_flow F]
-                                  [--track] [--track_stride S] [--track_points FILE]
+                                  [--track] [--track_stride S] [--track_points FILE] [--interpolate N]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -16,7 +16,10 @@ the default and --host_encode: the host's writers.  --output_backward adds the b
 whole clip with one scale instead of every pair with its own maximum.  --track follows every pixel of the first frame along the
 clip and adds %06d_track.flo per pair: the displacement from frame 0 to frame n + 1, (1e10, 1e10) where the track
 has left the frame or — where both directions run — was occluded; --track_stride S: every S-th pixel of every S-th row instead;
---track_points FILE: the pixels listed in FILE, `x y` per line, written as one tracks.npz (anchors, disp, alive)."""
+--track_points FILE: the pixels listed in FILE, `x y` per line, written as one tracks.npz (anchors, disp, alive).
+--interpolate N (1..7) adds N in-between frames per pair, %06d_mid%d.png (pair, j = 1..N): frame j is at time
+j / (N + 1) between the pair's frames, motion-compensated along the flow (along both flows, occluded pixels unblended, where both
+directions run)."""
 import argparse
 import os
 import sys
@@ -141,6 +144,8 @@ def parser():
                     help='like --track, for every S-th pixel of every S-th row (files of ceil(h / S) x ceil(w / S) pixels)')
     ap.add_argument('--track_points', default=None, metavar='FILE',
                     help='follow the pixels listed in FILE (`x y` per line) instead: one tracks.npz with anchors, disp and alive')
+    ap.add_argument('--interpolate', type=int, default=None, metavar='N',
+                    help='also N in-between frames per pair (1..7), motion-compensated: %%06d_mid%%d.png (pair, j = 1..N)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -160,6 +165,8 @@ def parse_args(argv=None):
         ap.error("--max_flow scales the flow colours of the pictures: it needs --visual")
     if a.max_flow is not None and not a.max_flow > 0:
         ap.error("--max_flow must be positive")
+    if a.interpolate is not None and not 1 <= a.interpolate <= 7:
+        ap.error("--interpolate makes 1 to 7 in-between frames per pair")
     if a.track_stride is not None and a.track_stride < 1:
         ap.error("--track_stride must be at least 1")
     if a.track_points is not None and (a.track or a.track_stride is not None):
@@ -203,7 +210,8 @@ def main(argv=None):
     params.update(config.get('train_kitti', {}))
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
                                         sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
-                                        visual='sequence' if a.visual else False, track=a.track_option)
+                                        visual='sequence' if a.visual else False, track=a.track_option,
+                                        interpolate=a.interpolate)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
@@ -211,7 +219,8 @@ def main(argv=None):
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
                                     deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion, visual=a.visual,
-                                    max_flow=a.max_flow, tracks=a.track_option is not False)
+                                    max_flow=a.max_flow, tracks=a.track_option is not False,
+                                    interpolate=a.interpolate is not None)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))
