@@ -5,13 +5,18 @@ max-norm tolerances of tests/test_planes_gpu.py see a 1e-6 wobble.  tests/test_e
 
 The shapes are the case tables of tests/test_planes_gpu.py (correlation: those with C a power of two); the kernel path
 is selected with lib_option like there and named in the test id (path-case-regime).  The CPU side of every test asserts the
-regime's condition (sum |a b| + |bias| <= 2^21 granules) before the GPU is asked anything."""
+regime's condition (sum |a b| + |bias| <= 2^21 granules) before the GPU is asked anything.
+
+The accumulating call of every data gradient (run_dgrad) applies a REAL leaky-ReLU derivative on [0, hi) — the activation field, the
+np.float32 model and the comparators of tests/dgrad_epilogue.py — once from the fp32 activation and, on the operand-plane entries, once
+from the activation's first plane."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import dgrad_epilogue as D
 import exact_inputs as E
 from test_planes_gpu import (CONV_CASES, CORR_BWD_CASES, CORR_PL_CASES, DECONV_CASES, SPLITK_CASES, STREAMK_CASES, WGRAD_CASES,
                              lib_option, make_pt, planes_value, weight_planes)  # noqa: F401  (lib_option: fixture)
@@ -138,33 +143,62 @@ def run_dgrad(regime, case, dev, P, deconv=False, entry='pl', scale=0.0):
     assert_gpu_planes(DZ, dz, regime, 0)
     g = E.gen('base', regime, case)
     base = E.ints((B, H, W, Cin), g, -3, 3) * E.GRANULE[regime]
-    DX = L.PT.alloc((B, H, W, Cin + 4), dev, P)
-    DX.t.fill_(3.0)
-    DX2 = L.PT.alloc((B, H, W, Cin + 4), dev, P)
-    DX2.t.fill_(3.0)
-    DX2.t[..., :Cin] = base.float().to(dev)
-    v, v2 = DX.sl(0, Cin), DX2.sl(0, Cin)
     hi = Cin // 2 // 4 * 4
-    ones = torch.ones(B, H, W, Cin, device=dev)
+    s = base + ref                                                            # |base + ref| stays below 2^22 granules: exact
+    # a real derivative (tests/dgrad_epilogue.py): about half of the activations negative, the specials planted in channels 0, hi - 1, hi
+    act, _, special = D.act_field((B, H, W, Cin), 0, hi, (regime, case))
+    D.assert_conditions(act, s, 0, hi, "%s %s" % (regime, case))
+    want = D.expected(s, D.slope_f32(act), 0, hi)                             # inside [0, hi): fl32((base + ref) * slope), one fp32 multiply
+    A = make_pt(torch.from_numpy(act), dev, P) if entry == 'pl' else L.PT(torch.from_numpy(act).to(dev))
+
+    def dest(fill):
+        d = L.PT.alloc((B, H, W, Cin + 4), dev, P)
+        d.t.fill_(3.0)
+        d.pl.fill_(D.SENTINEL)                                                # planes: 'untouched' is not 'wrote zero'
+        if fill:
+            d.t[..., :Cin] = base.float().to(dev)
+        return d, d.sl(0, Cin)
+    (DX, v), (DX2, v2) = dest(False), dest(True)
     if entry == 'pl' and deconv:
-        L.deconv_bwd_data(DZ, wd, w_tr, v, accumulate=False)
-        L.deconv_bwd_data(DZ, wd, w_tr, v2, accumulate=True, act_src=ones, act_lo=0, act_hi=hi)
+        call = lambda d, **kw: L.deconv_bwd_data(DZ, wd, w_tr, d, **kw)                     # noqa: E731
     elif entry == 'pl':
-        L.conv_bwd_data(DZ, wd, w_dir, v, stride, accumulate=False)
-        L.conv_bwd_data(DZ, wd, w_dir, v2, stride, accumulate=True, act_src=ones, act_lo=0, act_hi=hi)
+        call = lambda d, **kw: L.conv_bwd_data(DZ, wd, w_dir, d, stride, **kw)              # noqa: E731
     elif deconv:
-        L.conv2d_transpose_bwd_data(DZ.t, wd, v.t, accumulate=False)
-        L.conv2d_transpose_bwd_data(DZ.t, wd, v2.t, accumulate=True)
+        call = lambda d, **kw: L.conv2d_transpose_bwd_data(DZ.t, wd, d.t, **kw)             # noqa: E731
     else:
-        L.conv2d_bwd_data(DZ.t, wd, v.t, stride, accumulate=False)
-        L.conv2d_bwd_data(DZ.t, wd, v2.t, stride, accumulate=True)
+        call = lambda d, **kw: L.conv2d_bwd_data(DZ.t, wd, d.t, stride, **kw)               # noqa: E731
+    tiny = deconv and Cin == 2 and Cout == 2                                  # the 2 -> 2 conv_transpose refuses a derivative
+    call(v, accumulate=False)
+    call(v2, accumulate=True, **({} if tiny else dict(act_src=A.t, act_lo=0, act_hi=hi)))
     assert_exact(v.t, ref, "data gradient %s" % regime)
-    assert_exact(v2.t, base + ref, "accumulating data gradient %s" % regime)  # |base + ref| stays below 2^22 granules: exact
-    assert torch.all(DX.t[..., Cin:] == 3.0) and torch.all(DX2.t[..., Cin:] == 3.0)
-    if entry == 'pl' and P == 3 and hi:                                       # planes only for the activated range, the exact split
-        pl2 = planes_value(DX2.pl.cpu())
-        assert torch.equal(pl2[..., :hi], (base + ref)[..., :hi])
-        assert torch.all(pl2[..., hi:] == 0)
+    D.assert_output(DX2.t, D.f32_exact(s) if tiny else want, Cin, 3.0, "accumulating data gradient %s, fp32 derivative" % regime)
+    assert torch.all(DX.t[..., Cin:] == 3.0)
+    if entry != 'pl':
+        return
+    # planes only for the activated range (final after this call): the exact split / the fp16 cast of the product
+    D.assert_planes(DX2.pl, D.expected_planes(want, P), 0, hi, "accumulating data gradient %s, fp32 derivative" % regime)
+    # the derivative from the first operand plane of an activation that has no fp32 copy: the reference is slope_bits of the plane bits
+    # the kernel reads
+    DX3, v3 = dest(True)
+    if not deconv and k == 1 and stride == 1 and Cout == 32 and hi:           # the pointwise kernel of conv_igemm.hip reads no planes
+        with pytest.raises(_lib_error()) as e:
+            call(v3, accumulate=True, act_src=A, act_lo=0, act_hi=hi, act_planes=True)
+        assert e.value.status == -7                                           # UNFLOW_ERR_UNSUPPORTED, nothing launched
+        D.assert_output(DX3.t, D.f32_exact(base), Cin, 3.0, "refused call")
+        return
+    call(v3, accumulate=True, act_src=A, act_lo=0, act_hi=hi, act_planes=True)
+    bits = A.pl[0, ..., :Cin].cpu().numpy()
+    want3 = D.expected(s, D.slope_bits(bits), 0, hi)
+    what = "accumulating data gradient %s, plane derivative" % regime
+    D.assert_output(DX3.t, want3, Cin, 3.0, what)
+    D.assert_planes(DX3.pl, D.expected_planes(want3, P), 0, hi, what)
+    same = ~torch.from_numpy(special).to(dev)
+    assert torch.equal(DX3.t[..., :Cin][same], DX2.t[..., :Cin][same]), "plane source != fp32 source away from the specials"
+
+
+def _lib_error():
+    from unflow_amd._lib import UnflowError
+    return UnflowError
 
 
 def run_wgrad(regime, case, dev, P, entry='pl', scale=0.0):

@@ -102,6 +102,21 @@ __device__ __forceinline__ void mfma_terms(const s16x8 (&av)[NPL], const s16x8 (
 }
 
 // sign test on a 16-bit plane element (bf16 hi plane or fp16): the value is > 0 (tf.maximum(0.1 x, x) took the x branch)
+// Against leaky_grad_from_out (y > 0 in fp32), measured on an MI355X with planes from unflow_planes_from_f32 (the conversions keep
+// denormals and round ties to even; tests/test_dgrad_epilogue_gpu.py prints this table, DESIGN.md 4.1.1 has all of it) — a positive
+// value that VANISHES in the plane gets 0.1 here where the fp32 source gives 1.0; everything else agrees:
+//   activation           fp32   bf16 hi bits -> slope   fp16 bits -> slope
+//   +0 / -0              0.1    0x0000 / 0x8000  0.1    0x0000 / 0x8000  0.1
+//   +2^-149              1.0    0x0000           0.1    0x0000           0.1
+//   2^-134 (a tie)       1.0    0x0000           0.1    0x0000           0.1
+//   2^-134 (1 + 2^-10)   1.0    0x0001           1.0    0x0000           0.1
+//   +2^-133              1.0    0x0001           1.0    0x0000           0.1
+//   +2^-126, +1e-30      1.0    0x0080, 0x0da2   1.0    0x0000           0.1
+//   2^-25 (a tie)        1.0    0x3300           1.0    0x0000           0.1
+//   2^-25 (1 + 2^-10)    1.0    0x3300           1.0    0x0001           1.0
+//   +2^-24               1.0    0x3380           1.0    0x0001           1.0
+//   65504, 1e5, 3e38     1.0    0x4780 ..        1.0    0x7bff, 0x7c00   1.0   (fp16 infinity is still positive and non-zero)
+//   every negative value 0.1    sign bit set     0.1    sign bit set     0.1
 __device__ __forceinline__ float leaky_grad_from_bits(unsigned h) { return ((h & 0x8000u) == 0u && (h & 0x7fffu) != 0u) ? 1.f : 0.1f; }
 
 // bias / leaky-ReLU / accumulate / leaky derivative of four consecutive output channels; stores the fp32 result when the
