@@ -665,6 +665,38 @@ int unflow_sequence_track(const float* flow_fw, const unsigned char* occ_fw, con
                           const int* anchors, int Ncap, float* disp, unsigned char* alive, float* out_disp,
                           unsigned char* out_alive, unflow_stream_t stream);
 
+/* Ground truth along a clip (FlowEstimator(..., sequence=..., track=..., ground_truth=True); csrc/track_score.hip):
+ * chain the ground-truth flow of the replay's valid pairs into ground-truth tracks, and score this replay's tracks against them,
+ * per pair slot, one launch behind unflow_sequence_track.  gt_flow [2][B][Hmax][Wmax][2] fp32 and gt_mask [2][B][Hmax][Wmax] fp32:
+ * the staged ground truth of unflow_inference_output, map-major, pair slot i's at [.][i], at the origin.  tab, anchors, Ncap and
+ * the track numbering: unflow_sequence_track's; word 4 of a pair's table row is m = nmaps, its number of maps (above 2: 2).
+ * out_disp [B][Ncap][2], out_alive [B][Ncap]: what unflow_sequence_track wrote for this replay (read only).
+ * State, kept by the caller along a clip and updated in place: gt_disp [Ncap][2] fp32, gt_alive [Ncap] uint8.  Carry source 0
+ * starts every ground-truth track from disp = 0, alive = 1, whatever the state holds (unflow_sequence_track's rule).
+ * One step, for valid pair slot i, is unflow_sequence_track's step — anchor test, image_warp's taps, any tap of non-zero weight,
+ * the fp32 adds rounded one by one, the integer in-frame test, the 1e6 / non-finite rule — with
+ *   flow = gt_flow[0][i] (map 0 is the full flow; map 1 is zero under occlusions and is never read);
+ *   a tap is "occluded" iff gt_mask[m - 1][i][tap] == 0: with two maps invalid or occluded, with one map invalid;
+ *   m < 1 on a valid pair ends every live ground-truth track at that slot (nothing is read).
+ * After every valid slot i: out_gt_disp[i][n], out_gt_alive[i][n] ([B][Ncap][2] fp32, [B][Ncap] uint8) for n < N, and the slot's
+ * score over the tracks n < N, with (du, dv) = out_disp[i][n] - gt disp (fp32 subtractions) and d2 = du*du + dv*dv, the products
+ * and the sum rounded separately; the predicted displacement is used as it is (frozen where that track is dead), a NaN compares
+ * false.  scores [B][16] int32, T = {1, 4, 16, 64, 256}:
+ *   0 n_gt (ground-truth track alive)   1 n_pred (out_alive)   2 n_both
+ *   3..7 within_gt[k]: gt alive and d2 < T[k]            8..12 within_both[k]: both alive and d2 < T[k]
+ *   13 n_agree: out_alive == gt alive                    14 N as used (after the clamp to Ncap)        15 0
+ * err [B] fp64: the sum over the both-alive tracks of (double)sqrtf(d2), reduced in a fixed order (per-wave cells, per-block
+ * partials, the last block found by an integer ticket, a fixed lane-to-partial assignment and a fixed tree; no float atomics):
+ * two launches of one grid on the same inputs give the same bytes.  Slots that are not pairs and rows n >= N are not written.
+ * workspace: unflow_sequence_track_score_workspace_bytes(B, Ncap) bytes (0 for arguments the entry refuses), 8-byte aligned, ZERO
+ * on entry of the first launch; every launch leaves it zero.  UNFLOW_ERR_NULL for a NULL pointer other than anchors;
+ * UNFLOW_ERR_SHAPE, and nothing is launched, for what unflow_sequence_track refuses and for B above 512 (the block's LDS). */
+size_t unflow_sequence_track_score_workspace_bytes(int B, int Ncap);
+int unflow_sequence_track_score(const float* gt_flow, const float* gt_mask, const int* tab, int B, int Hmax, int Wmax,
+                                const int* anchors, int Ncap, const float* out_disp, const unsigned char* out_alive,
+                                float* gt_disp, unsigned char* gt_alive, float* out_gt_disp, unsigned char* out_gt_alive,
+                                int* scores, double* err, void* workspace, unflow_stream_t stream);
+
 /* flow [B][fh][fw][2] (the last network's flow2, or flow0 at (H, W) with full_res) -> for every sample b with desc h > 0 and
  * every frame pixel (y < h, x < w):
  *   f = resize_tf1(resize_tf1(flow, H, W) * flow_scale, h, w) (full_res: resize_tf1(flow * flow_scale, h, w)),
@@ -689,7 +721,7 @@ int unflow_inference_output(const float* flow, int fh, int fw, float flow_scale,
  * (b, y, x); nothing else is written.  gt_mask [2][B][Hmax][Wmax] (may be NULL), staged as for unflow_inference_output (map 0:
  * occ, map 1: noc): for a sample with desc nmaps = 2, counts[b] = {TP, FP, FN} of occ_fw over the pixels with mask_occ = 1,
  * positive where mask_noc = 0 (this project's KITTI occlusion scores).  counts [B][3] int32 (required with gt_mask) is zeroed
- * on the stream first; exact integer sums. */
+ * on the stream first (by a one-block launch: no memset node in a captured graph); exact integer sums. */
 int unflow_inference_occlusion(const float* flow_fw, const float* flow_bw, const int* desc, int B, int Hmax, int Wmax,
                                const float* gt_mask, unsigned char* occ_fw, unsigned char* occ_bw, int* counts,
                                unflow_stream_t stream);

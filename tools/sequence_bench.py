@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N]
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N |
+                                    --ground_truth [--track]]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
 of the replayed graph of FlowEstimator(..., sequence=True) in its steady state (a carried frame and B new frames: B pairs per
@@ -31,7 +32,14 @@ lines for the same estimators without tracks (profiles/sequence_bench_line.json,
 graph of the interpolating estimator against the same run's estimator without the option (the two take turns), and alone — device
 events around 50 launches — unflow_sequence_interpolate and the replay's output kernels (unflow_inference_output, with both
 directions twice and unflow_inference_occlusion), with the atomic bytes the splat issues.  Recorded, one line per N, in
-profiles/sequence_interpolate_bench_line.json."""
+profiles/sequence_interpolate_bench_line.json.
+
+--ground_truth [--track]: FlowNetC at B = 4, both sequence modes: ms per pair of the replayed graph of the scoring
+estimator (two-map ground truth staged, every pair scored; with --track dense tracks of stride 1 and unflow_sequence_track_score)
+against the SAME RUN's estimator without ground_truth (with --track: the plain tracking estimator), the two taking turns; with
+--track the new kernel alone (device events around 50 launches) with the bytes it must move; and the wall time per pair of
+evaluate_sequence against pair-mode evaluate on the same synthetic clip from host arrays.  Recorded in
+profiles/sequence_gt_bench_line.json."""
 import argparse
 import csv
 import glob
@@ -56,7 +64,8 @@ def _frames(n):
     return [np.roll(a, 2 * i, 1) for i in range(n)]
 
 
-def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None):
+def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None,
+               ground_truth=False):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
     pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
@@ -72,6 +81,8 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False
         kw['track'] = track
     if interpolate:
         kw['interpolate'] = interpolate
+    if ground_truth:
+        kw['ground_truth'] = True
     est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
@@ -482,6 +493,95 @@ def interpolate_case(seq, n, iters, warmup, rounds, B=4):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --ground_truth
+def _clip_gts(n):
+    """A two-map ground truth per pair at FRAME: a flow of a hundredth of a pixel and masks of ones, so that every ground-truth
+    track stays alive and the scoring kernel does its whole work in every replay."""
+    import numpy as np
+    flow = np.full(FRAME + (2,), 0.01, np.float32)
+    ones = np.ones(FRAME, np.float32)
+    return [(flow, ones, flow, ones)] * n
+
+
+def track_score_bytes(B=4):
+    """Compulsory bytes of unflow_sequence_track_score per replay, dense stride 1 on FRAME: per track the state read and written
+    (9 + 9) and per pair the ground-truth flow and mask read once (8 + 4; tap re-reads go through the caches), the predicted track
+    read (9) and the ground-truth track written (9)."""
+    px = FRAME[0] * FRAME[1]
+    per = 18 + B * 30
+    return per, px * per
+
+
+def gt_case(seq, track, iters, warmup, rounds, B=4):
+    import gc
+    import time
+    import numpy as np
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    from unflow_amd.core.input import resize_image_with_crop_or_pad
+    tr = True if track else False
+    plain, _ = _estimator('C', B, seq, track=tr, head_scale=TRACK_HEAD_SCALE)
+    scored, mem = _estimator('C', B, seq, track=tr, head_scale=TRACK_HEAD_SCALE, ground_truth=True)
+    frames = _frames(3 * B + 1)
+    gts = _clip_gts(3 * B)
+    if track:
+        plain.track_sequence(frames[:3 * B])               # the tables of the last replay: a carried frame, B pairs, S = 1, N
+    res = scored.evaluate_sequence([(frames[:3 * B], gts[:3 * B - 1])])       # ... and their nmaps words, the maps staged
+    runs = {'plain': plain.graph.replay, 'ground_truth': scored.graph.replay}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence=seq if seq is True else str(seq), track=bool(track), rounds=rounds)
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['ground_truth']['estimator_MB'] = round(mem / 1e6, 1)
+    out['ground_truth_over_plain'] = round(out['ground_truth']['ms_per_pair'] / out['plain']['ms_per_pair'], 4)
+    out['ground_truth_added_us_per_replay'] = round((out['ground_truth']['ms_per_pair'] - out['plain']['ms_per_pair']) * B * 1e3, 2)
+    if track:
+        L, e = _lib.lib(), scored
+
+        def kernel():
+            check(L.unflow_sequence_track_score(ptr(e.gt_flow), ptr(e.gt_mask), ptr(e.tab), B, e.Hmax, e.Wmax, ptr(e.track_anchors),
+                                                e.track_cap, ptr(e.out_track_disp), ptr(e.out_track_alive), ptr(e.gt_track_disp),
+                                                ptr(e.gt_track_alive), ptr(e.out_gt_track_disp), ptr(e.out_gt_track_alive),
+                                                ptr(e.out_track_scores), ptr(e.out_track_err), ptr(e.track_score_ws),
+                                                e.engine.stream()), "sequence_track_score")
+        us = _launches_us(kernel, e.dev)
+        per, nbytes = track_score_bytes(B)
+        out['kernel'] = dict(us=round(us, 2), B_per_track=per, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / us / 1e6, 3),
+                             how='device events around 50 back-to-back launches, launch gaps included')
+        out['gt_alive_share'] = round(float(e.gt_track_alive[:FRAME[0] * FRAME[1]].float().mean().item()), 4)
+        out['track_scores_last_pair'] = [int(v) for v in e.out_track_scores[B - 1].cpu()]
+    # evaluate_sequence against pair-mode evaluate on the same clip from host arrays: wall time per pair, the second of two passes
+    n_pairs = 3 * B
+    pair, _ = _estimator('C', B, False, bidirectional=seq == 'bidirectional', head_scale=TRACK_HEAD_SCALE)
+    pad = lambda a: resize_image_with_crop_or_pad(a, H, W).reshape((H, W) + a.shape[2:])         # noqa: E731
+    fp = [pad(f.astype(np.float32)) for f in frames]
+    gp = [tuple(pad(a if a.ndim == 3 else a[..., None]) for a in g) for g in gts]
+    shape = np.asarray(FRAME + (3,), np.int32)
+    batches = [tuple(np.stack(c) for c in zip(*[(fp[i], fp[i + 1], shape) + gp[i] for i in range(b0, min(b0 + B, n_pairs))]))
+               for b0 in range(0, n_pairs, B)]
+    wall = {}
+    for name, fn in (('evaluate_sequence', lambda: scored.evaluate_sequence([(frames, gts)])),
+                     ('pair_evaluate', lambda: pair.evaluate(iter(batches)))):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        wall[name] = dict(ms_per_pair=round((time.perf_counter() - t0) * 1e3 / n_pairs, 3), pairs=r['num_examples'])
+    wall['evaluate_sequence_over_pair_evaluate'] = round(wall['evaluate_sequence']['ms_per_pair'] / wall['pair_evaluate']['ms_per_pair'], 4)
+    out['wall'] = wall
+    out['names'] = res['names']
+    del plain, scored, pair
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -501,7 +601,19 @@ def main():
     ap.add_argument('--interpolate', type=int, default=None, metavar='N',
                     help='the estimator with N in-between frames per pair against the same one without, FlowNetC at B = 4, both '
                          'sequence modes, and the kernels alone (DESIGN 7.16)')
+    ap.add_argument('--ground_truth', action='store_true',
+                    help='the scoring estimator against the same one without ground_truth (with --track: both tracking), FlowNetC at '
+                         'B = 4, both sequence modes, and evaluate_sequence against pair-mode evaluate (DESIGN 7.17)')
     a = ap.parse_args()
+    if a.ground_truth:
+        res = dict(metric='sequence_ground_truth_ms_per_pair_over_the_same_estimator_without_it', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup, track=bool(a.track),
+                   expected='no ratio was predicted: nobody had measured the scoring kernel; the track kernel of 7.15 (17.5 / 23.2 us '
+                            'alone) is the yardstick beside it',
+                   note='one run on one box; box to box +- 3 %',
+                   cases=[gt_case(seq, a.track, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
+        print(json.dumps(res))
+        return
     if a.interpolate is not None:
         res = dict(metric='sequence_interpolate_ms_per_pair_over_the_same_estimator_without_it', shape=[H, W],
                    frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup, n=a.interpolate,

@@ -68,6 +68,17 @@ and track) kernels either sequence graph runs
 
 (push_interpolated, interpolate_sequence, export_sequence(interpolate=True)).
 
+sequence=True | 'bidirectional' with ground_truth=True: scores along a clip.  The ground truth of every pair is staged
+per pair slot, the pair table carries its number of maps, the output kernel on the forward rows scores it (the occlusion kernel
+counts TP / FP / FN with two maps), and with track the graph runs, behind unflow_sequence_track,
+
+    unflow_sequence_track_score    the staged ground-truth flow and masks of the replay's pairs -> ground-truth tracks, chained as
+                                   the tracks are and ended at invalid (two maps: or occluded) pixels, and per pair the integer
+                                   counts and the fp64 error sum of this replay's tracks against them; the ground-truth state stays
+                                   on the device from one replay of the clip to the next
+
+(push_scored, evaluate_sequence).
+
 The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
 _submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
 leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
@@ -123,7 +134,29 @@ Track = collections.namedtuple('Track', ('disp', 'alive'))
 # What push_interpolated returns per pair (n, n + 1): frames uint8 [n_mid, h, w, 3], the in-between frames j = 1..n_mid at time
 # j / (n_mid + 1), and holes int [n_mid], the pixels of each that no source reached (filled with the temporal blend)
 Interpolated = collections.namedtuple('Interpolated', ('frames', 'holes'))
-TRACK_DEAD = 1e10          # a dead track in %06d_track.flo: the .flo unknown-flow convention (read back as mask = 0)
+# What push_scored returns per pair: the flow, then per map of the ground truth aee, outliers (%) and mask_sum (the scored pixels);
+# occ_counts [tp, fp, fn] (both directions and two maps) or None; track a TrackScore (an estimator with track) or None
+PairScore = collections.namedtuple('PairScore', ('flow', 'aee', 'outliers', 'mask_sum', 'occ_counts', 'track'))
+# A pair's tracks against the chained ground truth (unflow_sequence_track_score): the counts of live ground-truth, predicted and
+# both-alive tracks; epe, the mean distance over the both-alive ones; per threshold 1, 2, 4, 8, 16 px pos_acc (ground-truth-alive
+# tracks within it, a dead prediction's frozen position counting) and jaccard (both alive and within it, over either alive);
+# occ_acc, the tracks whose alive flag agrees; the ground-truth tracks themselves, shaped as Track's
+TrackScore = collections.namedtuple('TrackScore', ('n_gt', 'n_pred', 'n_both', 'epe', 'pos_acc', 'jaccard', 'occ_acc', 'gt_disp',
+                                                   'gt_alive'))
+TRACK_SCORE_THRESHOLDS = (1.0, 2.0, 4.0, 8.0, 16.0)      # px; the kernel compares the squared distance with their squares
+
+
+def track_score(words, err, gt_disp, gt_alive):
+    """The 16 integer words and the error sum of unflow_sequence_track_score (one slot, or several summed) as a TrackScore; a
+    ratio whose denominator is 0 is nan."""
+    w = [int(v) for v in words]
+    ratio = lambda a, b: a / b if b else float('nan')          # noqa: E731
+    n_gt, n_pred, n_both = w[:3]
+    return TrackScore(n_gt, n_pred, n_both, ratio(float(err), n_both), [ratio(w[3 + k], n_gt) for k in range(5)],
+                      [ratio(w[8 + k], n_gt + n_pred - w[8 + k]) for k in range(5)], ratio(w[13], w[14]), gt_disp, gt_alive)
+
+
+TRACK_DEAD = 1e10         # a dead track in %06d_track.flo: the .flo unknown-flow convention (read back as mask = 0)
 
 
 def track_option(track):
@@ -228,15 +261,16 @@ def pack_desc(shapes, batch, staged=None, nmaps=0, u8=False):
     return d
 
 
-def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None):
+def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None, nmaps=0):
     """The device tables of one sequence replay, one int32 array [16 * batch + 4]: the frame table [batch][8] (pack_desc: the k
     new frames of size `shape` in rows 1 .. k of the engine, slots [0, k)), the pair table [batch][8] (slot i = rows i, i + 1:
     valid when both hold frames of this clip — slot 0 needs a carried frame, slot i >= 1 needs i + 1 <= k), the carry source
     (row of the previous replay's last frame; 0: a clip's first replay, nothing carried) and, behind it, the max_flow of the
     clip's flow colours (unflow_sequence_visual): 0 for None, every pair coloured with its own maximum, else the bit pattern of
     float32 max(max_flow, 1) (flow_util.py:31-32); behind that, the two words of unflow_sequence_track: track = (S, N), the grid
-    stride (0 with sparse anchors) and the number of tracks; None: both 0, as in every table without tracks.  Returns (table,
-    slots of the valid pairs in order, the next replay's carry source = k)."""
+    stride (0 with sparse anchors) and the number of tracks; None: both 0, as in every table without tracks.  nmaps: the maps of
+    the staged ground truth of every valid pair (word 4 of its row; 0: none, the pair is not scored).  Returns (table, slots of
+    the valid pairs in order, the next replay's carry source = k)."""
     batch, k, carry = int(batch), int(k), int(carry)
     if not 1 <= k <= batch:
         raise ValueError("a sequence replay takes 1 to %d new frames, got %d" % (batch, k))
@@ -247,7 +281,7 @@ def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None)
     valid = [i for i in range(batch) if i + 1 <= k and (i > 0 or carry > 0)]
     pair = np.zeros((batch, 8), dtype=np.int32)
     for i in valid:
-        pair[i] = (int(shape[0]), int(shape[1]), 0, 0, 0, int(bool(u8)), 0, 0)
+        pair[i] = (int(shape[0]), int(shape[1]), 0, 0, int(nmaps), int(bool(u8)), 0, 0)
     tab[8 * batch:16 * batch] = pair.reshape(-1)
     tab[16 * batch] = carry
     if max_flow is not None:
@@ -296,11 +330,18 @@ def chunks(it, n):
         yield buf
 
 
-def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0):
+def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False):
     """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
     and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
     estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator; n_mid: the
-    in-between frames per pair of an interpolating one."""
+    in-between frames per pair of an interpolating one.  ground_truth: also the rows of unflow_sequence_track_score,
+    behind the others; their flag, track_gt, needs track and ground_truth both."""
+    scored = ()
+    if ground_truth:
+        scored = (('track_scores', 'out_track_scores', (B, 16), torch.int32, 'track_gt'),
+                  ('track_err', 'out_track_err', (B,), torch.float64, 'track_gt'),
+                  ('gt_track_disp', 'out_gt_track_disp', (B, Ncap, 2), torch.float32, 'track_gt'),
+                  ('gt_track_alive', 'out_gt_track_alive', (B, Ncap), torch.uint8, 'track_gt'))
     return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
             ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
             ('sums', 'sums', (B, 2, 2), torch.float64, None),
@@ -313,7 +354,7 @@ def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0):
             ('track_disp', 'out_track_disp', (B, Ncap, 2), torch.float32, 'track'),
             ('track_alive', 'out_track_alive', (B, Ncap), torch.uint8, 'track'),
             ('mid', 'out_mid', (n_mid, B, Hm, Wm, 3), torch.uint8, 'interpolate'),
-            ('mid_holes', 'out_mid_holes', (n_mid, B), torch.int32, 'interpolate'))
+            ('mid_holes', 'out_mid_holes', (n_mid, B), torch.int32, 'interpolate')) + scored
 
 
 class _Slot:
@@ -327,7 +368,7 @@ class _Slot:
         self.desc = pin(B, 8, dtype=torch.int32)
         self.tab = pin(16 * B + 4, dtype=torch.int32) if est.sequence else None   # sequence_tables
         self.gt_flow = self.gt_mask = None
-        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate):
+        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate, True):
             setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
         self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
@@ -407,10 +448,14 @@ class FlowEstimator:
     staged frames and the flows (both directions and the occlusion masks on a sequence='bidirectional' estimator).
     push_interpolated / interpolate_sequence return an Interpolated(frames, holes) per pair, export_sequence(interpolate=True)
     writes them; every other method returns what it returns without interpolate.  reset() starts a new clip: the frame kept
-    from the last one is not used."""
+    from the last one is not used.
+    ground_truth (with sequence): the pairs of a clip are scored against ground truth given with the frames — push_scored returns
+    a PairScore per pair (AEE and outliers per map; the occlusion counts with both directions and two maps; with track a
+    TrackScore against the chained ground-truth flow), evaluate_sequence the averages over clips; every other method returns
+    what it returns without ground_truth."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
-                 visual=False, sequence=False, track=False, interpolate=None):
+                 visual=False, sequence=False, track=False, interpolate=None, ground_truth=False):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -433,6 +478,11 @@ class FlowEstimator:
         if self.interpolate and not sequence:
             raise ValueError("FlowEstimator: interpolate makes the frames between the frames of a clip; it needs sequence=True or "
                              "sequence='bidirectional'")
+        self.ground_truth = bool(ground_truth)                   # sequence: the clip's pairs are scored
+        if self.ground_truth and not sequence:
+            raise ValueError("FlowEstimator: ground_truth scores the pairs of a clip; it needs sequence=True or "
+                             "sequence='bidirectional' (a pair estimator scores already: evaluate)")
+        self.track_gt = self.track and self.ground_truth
         self.sequence = bool(sequence)
         self.seq_bidir = sequence == 'bidirectional'
         self.params = dict(params)
@@ -458,13 +508,14 @@ class FlowEstimator:
             z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.dev)   # noqa: E731
             self.frames = z((1 if self.sequence else 2) * B * Hm * Wm * 3 * 4, dtype=torch.uint8)
             self.desc = z(B, 8, dtype=torch.int32)
-            # sequence: frame table, pair table and carry source in one buffer (sequence_tables); no ground truth
+            # sequence: frame table, pair table and carry source in one buffer (sequence_tables); ground truth only on request
             self.tab = z(16 * B + 4, dtype=torch.int32) if self.sequence else None
-            self.gt_flow, self.gt_mask = (None, None) if self.sequence else (z(2, B, Hm, Wm, 2), z(2, B, Hm, Wm))
+            scored = self.ground_truth or not self.sequence
+            self.gt_flow, self.gt_mask = (z(2, B, Hm, Wm, 2), z(2, B, Hm, Wm)) if scored else (None, None)
             nb = int(L.unflow_inference_output_blocks(Hm, Wm))
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
-            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate):   # out_flow, out_u16, ...
+            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate, True):     # out_flow, out_u16, ...
                 setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
             self.track_anchors = self.track_disp = self.track_alive = None
             if self.track:
@@ -472,6 +523,13 @@ class FlowEstimator:
                 self.track_disp, self.track_alive = z(self.track_cap, 2), z(self.track_cap, dtype=torch.uint8)
                 if self.track_spec[0] == 'sparse':
                     self.track_anchors = torch.from_numpy(self.track_spec[1]).to(self.dev)
+            self.gt_track_disp = self.gt_track_alive = self.track_score_ws = None
+            if self.track_gt:
+                # the state of unflow_sequence_track_score, kept along a clip like the tracks', and its scratch: zero now and
+                # left zero by every launch
+                self.gt_track_disp, self.gt_track_alive = z(self.track_cap, 2), z(self.track_cap, dtype=torch.uint8)
+                self.track_score_ws = z(int(L.unflow_sequence_track_score_workspace_bytes(B, self.track_cap)) // 8,
+                                        dtype=torch.int64)
             self.mid_prev = self.mid_sums = None
             if self.interpolate:
                 # unflow_sequence_interpolate: the clip's last staged frame, kept from one replay to the next (fp32-sized), and the
@@ -496,6 +554,7 @@ class FlowEstimator:
         self._seq_k = 0               # sequence: replays submitted (the pinned slot alternates)
         self._max_flow = _UNSET       # sequence: the clip's max_flow of the flow colours (None: per pair), set by its first push
         self._enc = None              # _Encoder, built by the first export through the device encode path
+        self._clip_nmaps = 0          # sequence with ground_truth: the maps per pair of the clip, set by its first scored pair
 
     # ------------------------------------------------------------------------------------------ parameters
     @classmethod
@@ -553,16 +612,23 @@ class FlowEstimator:
         pairs = self.tab[8 * B:]
         if self.seq_bidir:
             fw, bw = e.fw_bw(self.flow_src)
-            self._output(fw, pairs, self.out_flow, self.out_u16)
+            self._output(fw, pairs, self.out_flow, self.out_u16, gt=self.ground_truth)
             self._output(bw, pairs, self.out_flow_bw, self.out_u16_bw)
-            self._occlusion(pairs)
+            self._occlusion(pairs, self.gt_mask if self.ground_truth else None)
         else:
-            self._output(self.flow_src, pairs, self.out_flow, self.out_u16)
+            self._output(self.flow_src, pairs, self.out_flow, self.out_u16, gt=self.ground_truth)
         if self.track:
             check(L.unflow_sequence_track(ptr(self.out_flow), ptr(self.occ[0]) if self.seq_bidir else None, ptr(self.tab), B,
                                           self.Hmax, self.Wmax, ptr(self.track_anchors), self.track_cap, ptr(self.track_disp),
                                           ptr(self.track_alive), ptr(self.out_track_disp), ptr(self.out_track_alive),
                                           e.stream()), "sequence_track")
+        if self.track_gt:
+            check(L.unflow_sequence_track_score(ptr(self.gt_flow), ptr(self.gt_mask), ptr(self.tab), B, self.Hmax, self.Wmax,
+                                                ptr(self.track_anchors), self.track_cap, ptr(self.out_track_disp),
+                                                ptr(self.out_track_alive), ptr(self.gt_track_disp), ptr(self.gt_track_alive),
+                                                ptr(self.out_gt_track_disp), ptr(self.out_gt_track_alive),
+                                                ptr(self.out_track_scores), ptr(self.out_track_err), ptr(self.track_score_ws),
+                                                e.stream()), "sequence_track_score")
         if self.interpolate:
             bw, ofw, obw = (self.out_flow_bw, self.occ[0], self.occ[1]) if self.seq_bidir else (None, None, None)
             check(L.unflow_sequence_interpolate(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate,
@@ -755,14 +821,16 @@ class FlowEstimator:
     def _num_pictures(self, nmaps):
         """How many of the pictures a replay draws: the last two exist only with ground truth (pair mode) or with both
         directions (sequence mode)."""
-        return len(VISUAL_IMAGES) if nmaps or self.seq_bidir else len(FlowVisual._fields)
+        if self.sequence:
+            return len(VISUAL_IMAGES) if self.seq_bidir else len(FlowVisual._fields)
+        return len(VISUAL_IMAGES) if nmaps else len(FlowVisual._fields)
 
     def _copy_back(self, slot, want, nmaps):
         """Queue the copies of the outputs named in `want` into the slot's pinned buffers.  The scores come back whenever ground
         truth was staged, the occlusion counts only when it had two maps."""
         special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
         nv = self._num_pictures(nmaps)
-        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate):
+        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate, True):
             if special.get(name, name in want):
                 dst, src = getattr(slot, name), getattr(self, attr)
                 if name == 'vis':
@@ -804,7 +872,7 @@ class FlowEstimator:
         return self._one_ahead(self._submit(k, exs, staged, nmaps_of(exs), want, files=files) for k, exs in enumerate(batches))
 
     # ------------------------------------------------------------------------------------------ public API
-    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False):
+    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False, ground_truth=False):
         """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
         one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
         if not sequence:
@@ -830,6 +898,9 @@ class FlowEstimator:
         if interpolate and not self.interpolate:
             raise RuntimeError("%s: a sequence estimator without in-between frames; build it with FlowEstimator(..., sequence=%r, "
                                "interpolate=n), n in 1..7" % (what, 'bidirectional' if self.seq_bidir else True))
+        if ground_truth and not self.ground_truth:
+            raise RuntimeError("%s: a sequence estimator without ground truth; build it with FlowEstimator(..., sequence=%r, "
+                               "ground_truth=True)" % (what, 'bidirectional' if self.seq_bidir else True))
 
     def _visual_spelling(self):
         """How to build this sequence estimator with pictures, for the messages that ask for it."""
@@ -1129,6 +1200,7 @@ class FlowEstimator:
         self._mode('reset', sequence=True)
         self._carry, self._clip = 0, None
         self._max_flow = _UNSET
+        self._clip_nmaps = 0
 
     def _clip_max_flow(self, max_flow, what):
         """The max_flow of the clip's flow colours: taken from the call that starts the clip (None: a maximum per pair); a later
@@ -1172,16 +1244,92 @@ class FlowEstimator:
             out.append(a)
         return out
 
-    def _submit_sequence(self, frames, want=('flow',), files=None, max_flow=None):
+    def _clip_gts(self, gts, n_frames, what):
+        """The ground truth of a scored push, checked before anything is staged: gts[i] belongs to the pair that ends at the
+        i-th new frame — None for a clip's first frame only, else (flow, mask) or (flow_occ, mask_occ, flow_noc, mask_noc), one
+        map count per clip.  Returns [None | [(flow [h, w, 2], mask [h, w]), ...]] with host arrays as float32 numpy, tensors on
+        this device left where they are."""
+        gts = list(gts)
+        if len(gts) != n_frames:
+            raise ValueError("%s: %d frames, %d ground truths (one per frame; None for a clip's first frame)"
+                             % (what, n_frames, len(gts)))
+        h, w, _ = self._clip
+        out = []
+        for i, g in enumerate(gts):
+            first = self._carry == 0 and i == 0
+            if g is None:
+                if not first:
+                    raise ValueError("%s: frame %d has no ground truth; only a clip's first frame ends no pair" % (what, i))
+                out.append(None)
+                continue
+            if len(g) not in (2, 4):
+                raise ValueError("%s: the ground truth of frame %d is (flow, mask) or (flow_occ, mask_occ, flow_noc, mask_noc), "
+                                 "got %d arrays" % (what, i, len(g)))
+            if first:                             # the pair that would end here does not exist: nothing to score
+                out.append(None)
+                continue
+            nmaps = len(g) // 2
+            if self._clip_nmaps == 0:
+                self._clip_nmaps = nmaps
+            elif nmaps != self._clip_nmaps:
+                raise ValueError("%s: the ground truth of frame %d has %d map(s), the clip's has %d; reset() starts a new clip"
+                                 % (what, i, nmaps, self._clip_nmaps))
+            maps = []
+            for m in range(nmaps):
+                f, msk = g[2 * m], g[2 * m + 1]
+                if not (isinstance(f, torch.Tensor) and self._on_device((f,))):
+                    f = np.asarray(f.cpu().numpy() if isinstance(f, torch.Tensor) else f, dtype=np.float32)
+                if not (isinstance(msk, torch.Tensor) and self._on_device((msk,))):
+                    msk = np.asarray(msk.cpu().numpy() if isinstance(msk, torch.Tensor) else msk, dtype=np.float32)
+                if tuple(f.shape) != (h, w, 2) or tuple(msk.shape) not in ((h, w), (h, w, 1)):
+                    raise ValueError("%s: the ground truth of frame %d is a [%d, %d, 2] flow and a [%d, %d] mask, got %s and %s"
+                                     % (what, i, h, w, h, w, tuple(f.shape), tuple(msk.shape)))
+                maps.append((f, msk.reshape(h, w)))
+            out.append(maps)
+        return out
+
+    def _stage_gts(self, slot, gts, h, w):
+        """Ground truth of pair slot i = gts[i], at the origin of its row, zero outside (h, w): host arrays through the slot's
+        pinned buffers and one upload, tensors of this device by device copies behind it (as _submit_sequence's frames)."""
+        nmaps = self._clip_nmaps
+        gf, gm = slot.gt(self)
+        host = False
+        for i, maps in enumerate(gts):
+            for m, (f, msk) in enumerate(maps or ()):
+                if isinstance(f, torch.Tensor) and isinstance(msk, torch.Tensor):
+                    continue
+                host = True
+                for dst, src in ((gf[m, i].numpy(), f), (gm[m, i].numpy(), msk)):
+                    if not isinstance(src, torch.Tensor):
+                        dst[:h, :w] = src
+                        dst[h:] = 0
+                        dst[:h, w:] = 0
+        with torch.cuda.device(self.dev):
+            if host:
+                self.gt_flow[:nmaps].copy_(gf[:nmaps], non_blocking=True)
+                self.gt_mask[:nmaps].copy_(gm[:nmaps], non_blocking=True)
+            for i, maps in enumerate(gts):
+                for m, (f, msk) in enumerate(maps or ()):
+                    for dst, src in ((self.gt_flow[m, i], f), (self.gt_mask[m, i], msk)):
+                        if isinstance(src, torch.Tensor):
+                            dst[:h, :w].copy_(src.float(), non_blocking=True)
+                            dst[h:].zero_()
+                            dst[:h, w:].zero_()
+
+    def _submit_sequence(self, frames, want=('flow',), files=None, max_flow=None, gts=None):
         """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns the slot, its
         rows the valid pair slots.  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ';
-        visual: 'vis'); files: _replay's.  max_flow: the clip's (_clip_max_flow)."""
+        visual: 'vis'); files: _replay's.  max_flow: the clip's (_clip_max_flow).  gts (an estimator with ground_truth): the
+        ground truth per new frame (_clip_gts); the pairs are then scored and slot.pending carries their map count."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
         max_flow = self._clip_max_flow(max_flow, 'push')
         frames = self._clip_frames(frames, 'push')
         h, w, u8 = self._clip
+        if gts is not None:
+            gts = self._clip_gts(gts, len(frames), 'push_scored')
+        nmaps = self._clip_nmaps if gts is not None else 0
         slot = self._slot(self._seq_k)
         self._seq_k += 1
         slot.wait()
@@ -1191,8 +1339,11 @@ class FlowEstimator:
         for i, a in enumerate(frames):
             if not isinstance(a, torch.Tensor):
                 fr[i, :h, :w] = a
-        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow, self._track_words(h, w))
+        tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow, self._track_words(h, w),
+                                                  nmaps=nmaps)
         slot.tab.numpy()[:] = tab
+        if nmaps:
+            self._stage_gts(slot, gts, h, w)
         with torch.cuda.device(self.dev):
             self.tab.copy_(slot.tab, non_blocking=True)
             if len(on_dev) < len(frames):
@@ -1201,7 +1352,7 @@ class FlowEstimator:
                 dv = self.frames[:nbytes].view(torch.uint8 if u8 else torch.float32).view(B, Hm, Wm, 3)
                 for i, a in on_dev:
                     dv[i, :h, :w].copy_(a, non_blocking=True)
-            return self._replay(slot, [(i, h, w) for i in valid], 0, want, files)
+            return self._replay(slot, [(i, h, w) for i in valid], nmaps, want, files)
 
     def _push(self, frames, want, max_flow=None):
         """One replay on its own: (slot, rows) once it has finished."""
@@ -1322,14 +1473,108 @@ class FlowEstimator:
             out += self._interpolated_of(slot, rows)
         return out
 
-    def _pipeline_sequence(self, frames, want, files=None, max_flow=None):
-        """reset, then _one_ahead over pushes of B frames."""
+    # ground truth along a clip
+    def _scored_want(self):
+        """What a scored replay copies back besides the scores themselves (sums and counts come with nmaps)."""
+        want = ('flow',) + (('occ_counts',) if self.seq_bidir else ())
+        if self.track:
+            want += ('track_scores', 'track_err', 'gt_track_disp', 'gt_track_alive')
+        return want
+
+    def _scores_of(self, slot, rows, nmaps):
+        """The rows of a finished scored replay as PairScore tuples (copies)."""
+        sums, counts = slot.sums.numpy(), slot.counts.numpy()
+        out = []
+        for (i, h, w), flow in zip(rows, self._flows_of(slot, rows)):
+            msum = [float(sums[i, m, 1]) for m in range(nmaps)]
+            aee = [float(sums[i, m, 0]) / msum[m] if msum[m] else float('nan') for m in range(nmaps)]
+            outl = [100.0 * float(counts[i, m]) / msum[m] if msum[m] else float('nan') for m in range(nmaps)]
+            occ = [int(v) for v in slot.occ_counts.numpy()[i]] if self.seq_bidir and nmaps == 2 else None
+            track = None
+            if self.track:
+                shape = self._track_shape(h, w)
+                n = int(np.prod(shape))
+                track = track_score(slot.track_scores.numpy()[i], float(slot.track_err.numpy()[i]),
+                                    slot.gt_track_disp.numpy()[i, :n].reshape(shape + (2,)).copy(),
+                                    slot.gt_track_alive.numpy()[i, :n].reshape(shape).astype(bool))
+            out.append(PairScore(flow, aee, outl, msum, occ, track))
+        return out
+
+    def push_scored(self, frames, gts):
+        """push's frames on an estimator built with ground_truth=True, with the ground truth of the pairs they end: gts[i] is
+        that of the pair ending at frames[i] — (flow [h, w, 2], mask [h, w] or [h, w, 1]), or the two-map (flow_occ, mask_occ,
+        flow_noc, mask_noc) — at the frames' own size, host arrays or tensors of this device; None only for a clip's first
+        frame.  One map count per clip.  Returns one PairScore(flow, aee, outliers, mask_sum, occ_counts, track) per new pair
+        (the count is push's): aee and outliers (%) per map as evaluate forms them, occ_counts [tp, fp, fn] on a
+        sequence='bidirectional' estimator with two maps (else None), track a TrackScore on an estimator with track (else
+        None): the tracks of push_tracks against the chained ground-truth flow, ended at its invalid (two maps: or occluded)
+        pixels."""
+        self._mode('push_scored', sequence=True, ground_truth=True)
+        slot = self._submit_sequence(list(frames), self._scored_want(), gts=list(gts))
+        slot.wait()
+        return self._scores_of(slot, *slot.pending)
+
+    def evaluate_sequence(self, clips, num=None):
+        """Scores along clips: `clips` yields (frames, gts) per clip, gts[i] the ground truth (push_scored's forms) of the pair
+        (frames[i], frames[i + 1]), len(gts) == len(frames) - 1.  reset() between clips; every frame is uploaded and encoded
+        once.  num: at most that many pairs.  Returns evaluate's dictionary — the per-pair averages of AEE/<map> and
+        outliers/<map>, num_examples, per_example, names; with both directions and two maps the pooled occ/precision, occ/recall,
+        occ/F1 and occ_counts — and per_clip, the number of pairs of every clip.  With track also track/epe, track/delta_avg (the
+        mean of pos_acc), track/AJ (the mean of jaccard) and track/occ_acc, pooled over all pairs from the summed integer words,
+        and per_example_track (the TrackScore of every pair, without its arrays)."""
+        self._mode('evaluate_sequence', sequence=True, ground_truth=True)
+        names, rows, occ_rows, per_clip, tracks = None, [], [], [], []
+        words, err = np.zeros(16, np.int64), 0.0
+        for frames, gts in clips:
+            if num is not None and len(rows) >= int(num):
+                break
+            frames, gts = list(frames), list(gts)
+            if len(gts) != len(frames) - 1:
+                raise ValueError("evaluate_sequence: a clip of %d frames has %d pairs, got %d ground truths"
+                                 % (len(frames), max(len(frames) - 1, 0), len(gts)))
+            n0 = len(rows)
+            for slot, pairs, nmaps in self._pipeline_sequence(frames, self._scored_want(), gts=[None] + gts):
+                for i, sc in zip((p[0] for p in pairs), self._scores_of(slot, pairs, nmaps)):
+                    if num is not None and len(rows) >= int(num):
+                        break
+                    if names is None:
+                        names = [n for m in MAP_NAMES[nmaps] for n in ('AEE/' + m, 'outliers/' + m)]
+                    elif len(names) != 2 * nmaps:
+                        raise ValueError("evaluate_sequence: the clips' ground truth changed its number of maps")
+                    rows.append([v for m in range(nmaps) for v in (sc.aee[m], sc.outliers[m])])
+                    if sc.occ_counts is not None:
+                        occ_rows.append(sc.occ_counts)
+                    if sc.track is not None:
+                        tracks.append(sc.track._replace(gt_disp=None, gt_alive=None))
+                        words += slot.track_scores.numpy()[i].astype(np.int64)
+                        err += float(slot.track_err.numpy()[i])
+            per_clip.append(len(rows) - n0)
+        if not rows:
+            raise ValueError("evaluate_sequence: the input yielded no pairs")
+        avg = np.mean(np.asarray(rows, dtype=np.float64), axis=0)
+        out = {k: float(v) for k, v in zip(names, avg)}
+        out.update(num_examples=len(rows), per_example=rows, names=names, per_clip=per_clip)
+        if occ_rows and len(occ_rows) == len(rows):
+            out.update(occlusion_scores(occ_rows))
+            out['occ_counts'] = occ_rows
+        if tracks:
+            pooled = track_score(words, err, None, None)
+            out.update({'track/epe': pooled.epe, 'track/delta_avg': float(np.mean(pooled.pos_acc)),
+                        'track/AJ': float(np.mean(pooled.jaccard)), 'track/occ_acc': pooled.occ_acc,
+                        'per_example_track': tracks})
+        return out
+
+    def _pipeline_sequence(self, frames, want, files=None, max_flow=None, gts=None):
+        """reset, then _one_ahead over pushes of B frames (gts: the ground truth per frame, chunked alongside)."""
         self.reset()
 
         def replays():
             total = 0
             for chunk in chunks(frames, self.B):
                 total += len(chunk)
+                if gts is not None:
+                    yield self._submit_sequence(chunk, want, files, max_flow, gts=gts[total - len(chunk):total])
+                    continue
                 yield self._submit_sequence(chunk, want, files, max_flow)
             if total < 2:                         # raised before the only replay, which holds no pair, would be handed out
                 raise ValueError("a clip needs at least two frames, got %d" % total)

@@ -213,6 +213,55 @@ def _sintel_gt(raw_dev, n_raw, dec_dev, n_dec, table_dev, n, H, W, flow, mask, s
                                       ptr(flow), ptr(mask), _stream_ptr(stream)), "sintel_gt")
 
 
+def sintel_gt_device(triples, device=None):
+    """Sintel's two-map ground truth of n pairs at the files' OWN size, composed on the device: triples = [(.flo, invalid PNG,
+    occlusions PNG), ...], all of one size (h, w) -> (flow [2, n, h, w, 2], mask [2, n, h, w]) fp32 device tensors, map 0 =
+    (flow, 1 - invalid), map 1 = (flow * (1 - occ), (1 - invalid) * (1 - occ)) — unflow_sintel_gt over the full-size window
+    (origin 0, no crop, no padding), on the current stream, the bits of SintelInput.read_gt_full.  A file of another size, or a
+    mask whose size differs from its .flo's, raises ValueError naming it.  (Synchronous host reads: the ground truth of a clip's
+    replay, B files of each kind; evaluate_flo --sequence.)"""
+    dev = _device(device)
+    n = len(triples)
+    if n == 0:
+        raise ValueError("sintel_gt_device: no files")
+    h, w = flo_header(triples[0][0])
+    parts, rows, src, dst = [], [], 0, 0
+    for col in range(3):
+        for t in triples:
+            path = t[col]
+            if col == 0:
+                if flo_header(path) != (h, w):
+                    raise ValueError("%s is %d x %d, the clip's first flow file %s %d x %d"
+                                     % ((path,) + flo_header(path) + (triples[0][0], h, w)))
+                pad = -src % FLO_ALIGN
+                parts.append(np.zeros(pad, np.uint8))
+                src += pad
+                with open(path, 'rb') as f:
+                    body = np.frombuffer(f.read()[FLO_HEADER_BYTES:], dtype=np.uint8)
+                rows.append((src, 0, h, w, 8, 4, 0, 0))
+                parts.append(body)
+                src += body.size
+            else:
+                with open(path, 'rb') as f:
+                    mh, mw, depth, ctype, raw = png_scanlines(f.read())
+                if (mh, mw) != (h, w):
+                    raise ValueError("%s is %d x %d, its flow file %s %d x %d" % (path, mh, mw, t[0], h, w))
+                n_in, n_out = mh * (mw * _bpp(depth, ctype) + 1), mh * mw * _bpp(depth, ctype)
+                rows.append(_table_row(src, dst, mh, mw, depth, ctype))
+                parts.append(np.frombuffer(raw, dtype=np.uint8, count=n_in))
+                src, dst = src + n_in, dst + n_out
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        raw_dev = torch.from_numpy(np.concatenate(parts)).to(dev)
+        table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        dec = torch.empty(max(dst, 1), dtype=torch.uint8, device=dev)
+        _unfilter(raw_dev, src, dec, dst, table[n:], 2 * n, stream)
+        flow = torch.empty(2, n, h, w, 2, dtype=torch.float32, device=dev)
+        mask = torch.empty(2, n, h, w, dtype=torch.float32, device=dev)
+        _sintel_gt(raw_dev, src, dec, dst, table, n, h, w, flow, mask, stream)
+    return flow, mask
+
+
 class PairPlanner:
     """The host-only half of DevicePairBatches: which files form the next batch and where they are cropped.  Walks the pair list
     as RawPairBatches does (in order, cyclically, `batch_size` examples per batch) and makes the same

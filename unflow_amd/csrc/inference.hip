@@ -283,6 +283,10 @@ __global__ __launch_bounds__(OCC_THREADS) void inference_occlusion_kernel(
   }
 }
 
+__global__ void zero_counts_kernel(int* __restrict__ counts, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) counts[i] = 0;
+}
+
 }  // namespace
 
 UNFLOW_API int unflow_inference_input(const void* frames, const int* desc, int B, int Hmax, int Wmax, int H, int W, float* net_in4,
@@ -352,7 +356,9 @@ UNFLOW_API int unflow_inference_occlusion(const float* flow_fw, const float* flo
   if (gt_mask && !counts) return UNFLOW_ERR_NULL;
   if (B <= 0 || Hmax <= 0 || Wmax <= 0 || (long)Hmax * Wmax > 0x7fffffffL) return UNFLOW_ERR_SHAPE;
   const hipStream_t st = as_stream(stream);
-  if (counts && hipMemsetAsync(counts, 0, sizeof(int) * 3 * (size_t)B, st) != hipSuccess) return UNFLOW_ERR_LAUNCH;
+  // zeroed by a launch, not by hipMemsetAsync: inside a replayed graph a memset node of a few bytes has left other words than
+  // zero in its target (DESIGN 7.4 met it at 24 bytes; 7.17 met it here, at B = 2, once the counts of a sequence graph were read)
+  if (counts) zero_counts_kernel<<<1, 64, 0, st>>>(counts, 3 * B);
   const dim3 grid(unflow_inference_output_blocks(Hmax, Wmax), B);
   inference_occlusion_kernel<<<grid, OCC_THREADS, 0, st>>>(flow_fw, flow_bw, desc, B, Hmax, Wmax, gt_mask, occ_fw, occ_bw, counts);
   return launch_status();

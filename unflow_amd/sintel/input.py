@@ -11,10 +11,12 @@ binary mask is followed.  The .flo size comes from the file's heade
 Host numpy batches, or — with a device — the same batches as device tensors, composed by unflow_sintel_gt
 (middlebury/input.py::FloInput, core/png_device.py).  input_train_gt (this project's addition, DESIGN 7.9) is the supervised
 training input: random crops with one of the two composed maps.  The dataset downloader (sintel/data.py) is out of scope."""
+import os
+
 import numpy as np
 
 from ..core.input import read_flo, read_png_image
-from ..middlebury.input import FloInput, listed, scene_pairs
+from ..middlebury.input import FloInput, listed, scene_files, scene_pairs
 
 
 def read_binary(path):
@@ -39,6 +41,42 @@ class SintelInput(FloInput):
         if len(pairs) != len(gt[0]):
             raise ValueError("sintel: %d frame pairs in %s but %d flow files" % (len(pairs), image_dir, len(gt[0])))
         return pairs, gt
+
+    def clips(self, variant='clean'):
+        """The scenes of sintel/training/<variant> as clips: a list of (scene name, frame files, [(flo, invalid,
+        occlusions), ...]), the triple of pair i = (frame i, frame i + 1) at position i — gt_files' three listings scene by
+        scene, with its length checks per scene: a scene of T frames has T - 1 flow files, T invalid maps (the last dropped) and
+        T - 1 occlusion maps."""
+        if variant not in ('clean', 'final'):
+            raise ValueError("variant must be 'clean' or 'final', got %r" % (variant,))
+        image_dir = 'sintel/training/' + variant
+        self.train_files(image_dir)                  # the listings' total lengths agree
+        names = sorted(os.listdir(self._dir(image_dir)))
+        frames = scene_files(self._dir(image_dir))
+        flow = scene_files(self._dir('sintel/training/flow'))
+        invalid = scene_files(self._dir('sintel/training/invalid'), drop_last=True)
+        occ = scene_files(self._dir('sintel/training/occlusions'))
+        if not len(frames) == len(flow) == len(invalid) == len(occ):
+            raise ValueError("sintel: %d scenes in %s, %d in flow, %d in invalid, %d in occlusions"
+                             % (len(frames), image_dir, len(flow), len(invalid), len(occ)))
+        out = []
+        for name, fr, fl, inv, oc in zip(names, frames, flow, invalid, occ):
+            if not len(fr) - 1 == len(fl) == len(inv) == len(oc):
+                raise ValueError("sintel: scene %s has %d frames (%d pairs) but %d flow files, %d invalid maps (its last dropped), "
+                                 "%d occlusion maps" % (name, len(fr), max(len(fr) - 1, 0), len(fl), len(inv), len(oc)))
+            out.append((name, fr, list(zip(fl, inv, oc))))
+        return out
+
+    def read_gt_full(self, f_flow, f_invalid, f_occ):
+        """_read_gt's composition at the files' own size, no crop and no padding: (flow_occ [h,w,2], mask_occ [h,w], flow_noc,
+        mask_noc) — what evaluate_flo --sequence scores a clip against (png_device.sintel_gt_device: the same bits)."""
+        flow = read_flo(f_flow)[0].numpy()
+        invalid, occ = read_binary(f_invalid), read_binary(f_occ)
+        for f, m in ((f_invalid, invalid), (f_occ, occ)):
+            if m.shape[:2] != flow.shape[:2]:
+                raise ValueError("%s is %d x %d, its flow file %s %d x %d" % ((f,) + m.shape[:2] + (f_flow,) + flow.shape[:2]))
+        mask_occ = 1 - invalid
+        return flow, mask_occ[:, :, 0], flow * (1 - occ), (mask_occ * (1 - occ))[:, :, 0]
 
     def _read_gt(self, f_flow, f_invalid, f_occ):
         flow = read_flo(f_flow)[0].numpy()
