@@ -844,6 +844,48 @@ int unflow_sequence_interpolate(const void* frames, const int* tab, int B, int H
                                 const float* flow_bw, const unsigned char* occ_fw, const unsigned char* occ_bw, void* prev,
                                 void* workspace, unsigned char* out_mid, int* out_holes, unflow_stream_t stream);
 
+/* Held-out scores of the in-between frames (FlowEstimator(..., sequence=..., interpolate=n, held_out=True);
+ * csrc/interpolate_score.hip): the frames that unflow_sequence_interpolate made, and two candidates that need no flow,
+ * against the frames that were left out of the clip, by squared error and by SSIM.  Launched behind unflow_sequence_interpolate.
+ * This definition is part of the ABI; tests/mid_score_ref.py mirrors it.
+ * Setting.  frames, tab, B, Hmax, Wmax, n: unflow_sequence_interpolate's.  out_mid [n][B][Hmax][Wmax][3] uint8: what that entry
+ * wrote (read only).  truth [n][B][Hmax][Wmax][3] in the staged dtype (the tables' u8 field): truth frame j of pair slot i at
+ * [j - 1][i], at the origin, rows Wmax apart.  A pair slot is scored iff it is a pair by unflow_sequence_interpolate's rule AND
+ * word 6 of its pair-table row, `held`, is non-zero.  For pair slot i of size (h, w): im0 = staged frame i - 1 (slot 0: this
+ * entry's own prev), im1 = staged frame i.
+ * Bytes.  q(c) = (long)rintf(min(max(c, 0), 255) * 256) is unflow_sequence_interpolate's quantisation (one definition,
+ * csrc/mid_common.h; fminf / fmaxf return their other operand for a NaN, so a NaN colour is 0).  The byte of a staged value is
+ * (q(c) + 128) / 256 by integer division — for a uint8 frame the byte itself.  T is the truth's byte.  Three candidates X per (j,
+ * slot), kind
+ *   0 interpolated  out_mid[j - 1][i];
+ *   1 blend         ((n + 1 - j) q(im0) + j q(im1) + 128 (n + 1)) / (256 (n + 1)): what unflow_sequence_interpolate gives a hole;
+ *   2 nearest       the byte of im0 where 2 j <= n + 1, else the byte of im1.
+ * Scores per (j, slot, kind):
+ *   sse   int64, the sum over the h w pixels and 3 channels of (X - T)^2, exact;
+ *   ssim  fp64, the sum over the channels and over every 8 x 8 window wholly inside (h, w) — (h - 7)(w - 7) positions, none and
+ *         the sum 0 if h < 8 or w < 8 — of the window's SSIM: with the integer window sums Sx, Sy, Sxx, Syy, Sxy (x the
+ *         candidate, y the truth), as 64-bit integers vx = 64 Sxx - Sx^2, vy = 64 Syy - Sy^2, cxy = 64 Sxy - Sx Sy, then
+ *           a1 = (double)(2 Sx Sy) + c1,  a2 = (double)(2 cxy) + c2,  b1 = (double)(Sx^2 + Sy^2) + c1,  b2 = (double)(vx + vy) + c2,
+ *           ssim = (a1 * a2) / (b1 * b2),   c1 = 26634.24 = 4096 (0.01 * 255)^2,  c2 = 239708.16 = 4096 (0.03 * 255)^2,
+ *         every fp64 operation rounded on its own (-ffp-contract=off); the integers are below 2^53, their conversions exact.
+ * Outputs: out_sse [n][B][3] int64, out_ssim [n][B][3] fp64, (j, slot, kind) at [j - 1][slot][kind].  Nothing is written for a
+ * slot that is not scored.  The pixel and window counts are the host's, from (h, w).
+ * The fp64 sums are reduced in a fixed order — a thread's terms, a tree per wave, the waves, the block's tiles, per-block partials,
+ * an integer ticket, the last block over the partials by a fixed lane assignment and a tree; no float atomics — so two launches and
+ * two graph replays give the same bytes.  The integer sums use integer atomics.
+ * prev [Hmax][Wmax][3] in the staged dtype (Hmax * Wmax * 12 bytes hold either), this entry's own (unflow_sequence_interpolate has
+ * overwritten its prev with this replay's last frame by now), kept by the caller along a clip: a launch behind the scoring one
+ * copies the (h, w) corner of the last frame-table slot with h > 0 into it.  It is never read while the carry source is 0 and
+ * needs no initialisation.
+ * workspace: unflow_sequence_interpolate_score_workspace_bytes(n, B, Hmax, Wmax) bytes (0 for arguments the entry refuses), 8-byte
+ * aligned, zero on entry and left zero by every launch (no memset node in a captured graph).
+ * UNFLOW_ERR_NULL for a NULL pointer; UNFLOW_ERR_SHAPE, and nothing is launched, for n outside 1..7, B < 1 or above 65535 (the
+ * grid's rows), Hmax or Wmax < 1, Hmax * Wmax above 2^31 - 1. */
+size_t unflow_sequence_interpolate_score_workspace_bytes(int n, int B, int Hmax, int Wmax);
+int unflow_sequence_interpolate_score(const void* frames, const int* tab, int B, int Hmax, int Wmax, int n,
+                                      const unsigned char* out_mid, const void* truth, void* prev, void* workspace,
+                                      long long* out_sse, double* out_ssim, unflow_stream_t stream);
+
 /* ===================================================================== */
 /* PNG decode on the device (csrc/png_decode.hip, core/png_device.py)      */
 /* ===================================================================== */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N |
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N [--held_out] |
                                     --ground_truth [--track]]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
@@ -34,6 +34,10 @@ events around 50 launches — unflow_sequence_interpolate and the replay's outpu
 directions twice and unflow_inference_occlusion), with the atomic bytes the splat issues.  Recorded, one line per N, in
 profiles/sequence_interpolate_bench_line.json.
 
+--interpolate N --held_out: the estimator that also scores its in-between frames against held-out frames, against
+the SAME RUN's interpolating estimator without the option, the two taking turns; and unflow_sequence_interpolate_score alone (device
+events around 50 back-to-back calls) beside the bytes it reads.  One line per N in profiles/sequence_mid_score_bench_line.json.
+
 --ground_truth [--track]: FlowNetC at B = 4, both sequence modes: ms per pair of the replayed graph of the scoring
 estimator (two-map ground truth staged, every pair scored; with --track dense tracks of stride 1 and unflow_sequence_track_score)
 against the SAME RUN's estimator without ground_truth (with --track: the plain tracking estimator), the two taking turns; with
@@ -65,7 +69,7 @@ def _frames(n):
 
 
 def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None,
-               ground_truth=False):
+               ground_truth=False, held_out=False):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
     pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
@@ -83,6 +87,8 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False
         kw['interpolate'] = interpolate
     if ground_truth:
         kw['ground_truth'] = True
+    if held_out:
+        kw['held_out'] = True
     est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
@@ -493,6 +499,53 @@ def interpolate_case(seq, n, iters, warmup, rounds, B=4):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --interpolate N --held_out (7.18)
+def held_out_case(seq, n, iters, warmup, rounds, B=4):
+    """The scoring estimator against the SAME RUN's interpolating estimator without the option, the two taking turns; and the
+    new entry alone, with the bytes it has to read."""
+    import gc
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    mid, _ = _estimator('C', B, seq, interpolate=n)
+    mid.interpolate_sequence(_frames(3 * B))
+    held, mem = _estimator('C', B, seq, interpolate=n, held_out=True)
+    scores = held.evaluate_interpolation([_frames((3 * B - 1) * (n + 1) + 1)])      # the last replay: a carried frame, B held pairs
+    runs = {'interpolate': mid.graph.replay, 'held_out': held.graph.replay}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence=seq if seq is True else str(seq), n=n, rounds=rounds)
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['held_out']['estimator_MB'] = round(mem / 1e6, 1)
+    out['held_out_over_interpolate'] = round(out['held_out']['ms_per_pair'] / out['interpolate']['ms_per_pair'], 4)
+    out['held_out_added_us_per_replay'] = round((out['held_out']['ms_per_pair'] - out['interpolate']['ms_per_pair']) * B * 1e3, 2)
+    L, e = _lib.lib(), held
+
+    def kernel():
+        check(L.unflow_sequence_interpolate_score(ptr(e.frames), ptr(e.tab), B, e.Hmax, e.Wmax, n, ptr(e.out_mid), ptr(e.mid_truth),
+                                                  ptr(e.mid_score_prev), ptr(e.mid_score_ws), ptr(e.out_mid_sse),
+                                                  ptr(e.out_mid_ssim), e.engine.stream()), "sequence_interpolate_score")
+    us = _launches_us(kernel, e.dev)
+    px = FRAME[0] * FRAME[1] * B
+    # uint8 frames: per pixel the two frames' 3 bytes once per slot, truth and out_mid 3 bytes each per j; the 39 x 23 halo region
+    # of a 32 x 16 tile reads 1.75 times the tile's own pixels
+    own = px * (6 + 6 * n)
+    out['kernel'] = dict(us=round(us, 2), launches=2, own_MB=round(own / 1e6, 2), with_halo_MB=round(own * 39 * 23 / 512 / 1e6, 2),
+                         own_TBps=round(own / us / 1e6, 4), with_halo_TBps=round(own * 39 * 23 / 512 / us / 1e6, 4),
+                         how='device events around 50 back-to-back calls of the entry (two launches each), launch gaps included')
+    out['scores'] = {k: round(v, 4) for k, v in scores.items() if k.startswith(('psnr/', 'ssim/'))}
+    out['holes_share'] = round(scores['holes'], 5)
+    assert not bool(e.mid_score_ws.any())
+    del mid, held
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- --ground_truth (DESIGN 7.17)
 def _clip_gts(n):
     """A two-map ground truth per pair at FRAME: a flow of a hundredth of a pixel and masks of ones, so that every ground-truth
@@ -601,6 +654,9 @@ def main():
     ap.add_argument('--interpolate', type=int, default=None, metavar='N',
                     help='the estimator with N in-between frames per pair against the same one without, FlowNetC at B = 4, both '
                          'sequence modes, and the kernels alone (DESIGN 7.16)')
+    ap.add_argument('--held_out', action='store_true',
+                    help='with --interpolate N: the estimator that scores its in-between frames against the same run\'s '
+                         'interpolating estimator without the option, and the scoring entry alone (DESIGN 7.18)')
     ap.add_argument('--ground_truth', action='store_true',
                     help='the scoring estimator against the same one without ground_truth (with --track: both tracking), FlowNetC at '
                          'B = 4, both sequence modes, and evaluate_sequence against pair-mode evaluate (DESIGN 7.17)')
@@ -612,6 +668,17 @@ def main():
                             'alone) is the yardstick beside it',
                    note='one run on one box; box to box +- 3 %',
                    cases=[gt_case(seq, a.track, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
+        print(json.dumps(res))
+        return
+    if a.held_out:
+        if a.interpolate is None:
+            ap.error("--held_out needs --interpolate N")
+        res = dict(metric='sequence_held_out_ms_per_pair_over_the_same_interpolating_estimator_without_it', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup, n=a.interpolate,
+                   expected='no time or ratio was predicted: nobody had measured this kernel; its bytes are about 12 B per pixel and j '
+                            'plus the halo',
+                   note='one run on one box; box to box +- 3 %',
+                   cases=[held_out_case(seq, a.interpolate, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
         print(json.dumps(res))
         return
     if a.interpolate is not None:

@@ -79,6 +79,16 @@ counts TP / FP / FN with two maps), and with track the graph runs, behind unflow
 
 (push_scored, evaluate_sequence).
 
+sequence=True | 'bidirectional' with interpolate=n and held_out=True: the in-between frames scored against held-out frames (DESIGN
+7.18).  The frames that were left out of the clip are staged per pair slot and j, the pair table says `held`, and behind
+unflow_sequence_interpolate the graph runs
+
+    unflow_sequence_interpolate_score   the staged frames, out_mid and the truth frames -> per pair, j and candidate (the interpolated
+                                   frame, the temporal blend, the nearest frame) the exact squared error and the sum of the 8 x 8
+                                   window SSIMs, reduced in a fixed order; its own copy of the clip's last frame stays on the device
+
+(push_held_out, evaluate_interpolation).
+
 The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
 _submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
 leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
@@ -88,6 +98,7 @@ output is a row of output_buffers, a new file kind a row of pair_files and a bra
 import collections
 import contextlib
 import itertools
+import math
 import os
 
 import numpy as np
@@ -134,6 +145,30 @@ Track = collections.namedtuple('Track', ('disp', 'alive'))
 # What push_interpolated returns per pair (n, n + 1): frames uint8 [n_mid, h, w, 3], the in-between frames j = 1..n_mid at time
 # j / (n_mid + 1), and holes int [n_mid], the pixels of each that no source reached (filled with the temporal blend)
 Interpolated = collections.namedtuple('Interpolated', ('frames', 'holes'))
+# What push_held_out returns per pair: Interpolated's frames and holes, then per in-between frame j and candidate kind (MID_KINDS:
+# the interpolated frame, the temporal blend, the nearest frame) against the held-out frame: sse int64 [n_mid, 3], the summed squared
+# byte error; psnr [n_mid, 3] = 10 log10(255^2 3 h w / sse), inf at sse = 0; ssim [n_mid, 3], the mean 8 x 8-window SSIM over the 3
+# (h - 7)(w - 7) windows, nan without a window
+HeldOut = collections.namedtuple('HeldOut', ('frames', 'holes', 'sse', 'psnr', 'ssim'))
+MID_KINDS = ('mid', 'blend', 'nearest')
+
+
+def mid_windows(h, w):
+    """The 8 x 8 window positions of an (h, w) frame times its 3 channels: what a pair's SSIM sum is divided by."""
+    return 3 * max(int(h) - 7, 0) * max(int(w) - 7, 0)
+
+
+def mid_psnr(sse, values):
+    """10 log10(255^2 values / sse) of integer squared-error sums over `values` byte values; inf where sse = 0."""
+    sse = np.asarray(sse, dtype=np.float64)
+    with np.errstate(divide='ignore'):
+        return 10.0 * np.log10(255.0 ** 2 * float(values) / sse)
+
+
+def mid_mean_ssim(ssim_sum, windows):
+    """SSIM sums over `windows` windows as means; nan without a window."""
+    ssim_sum = np.asarray(ssim_sum, dtype=np.float64)
+    return ssim_sum / float(windows) if windows else np.full(ssim_sum.shape, np.nan)
 # What push_scored returns per pair: the flow, then per map of the ground truth aee, outliers (%) and mask_sum (the scored pixels);
 # occ_counts [tp, fp, fn] (both directions and two maps) or None; track a TrackScore (an estimator with track) or None
 PairScore = collections.namedtuple('PairScore', ('flow', 'aee', 'outliers', 'mask_sum', 'occ_counts', 'track'))
@@ -261,7 +296,7 @@ def pack_desc(shapes, batch, staged=None, nmaps=0, u8=False):
     return d
 
 
-def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None, nmaps=0):
+def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None, nmaps=0, held=0):
     """The device tables of one sequence replay, one int32 array [16 * batch + 4]: the frame table [batch][8] (pack_desc: the k
     new frames of size `shape` in rows 1 .. k of the engine, slots [0, k)), the pair table [batch][8] (slot i = rows i, i + 1:
     valid when both hold frames of this clip — slot 0 needs a carried frame, slot i >= 1 needs i + 1 <= k), the carry source
@@ -269,7 +304,8 @@ def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None,
     clip's flow colours (unflow_sequence_visual): 0 for None, every pair coloured with its own maximum, else the bit pattern of
     float32 max(max_flow, 1) (flow_util.py:31-32); behind that, the two words of unflow_sequence_track: track = (S, N), the grid
     stride (0 with sparse anchors) and the number of tracks; None: both 0, as in every table without tracks.  nmaps: the maps of
-    the staged ground truth of every valid pair (word 4 of its row; 0: none, the pair is not scored).  Returns (table, slots of
+    the staged ground truth of every valid pair (word 4 of its row; 0: none, the pair is not scored).  held: non-zero when the
+    truth frames of every valid pair are staged (word 6 of its row; 0: unflow_sequence_interpolate_score skips the pair).  Returns (table, slots of
     the valid pairs in order, the next replay's carry source = k)."""
     batch, k, carry = int(batch), int(k), int(carry)
     if not 1 <= k <= batch:
@@ -281,7 +317,7 @@ def sequence_tables(shape, k, batch, carry, u8=False, max_flow=None, track=None,
     valid = [i for i in range(batch) if i + 1 <= k and (i > 0 or carry > 0)]
     pair = np.zeros((batch, 8), dtype=np.int32)
     for i in valid:
-        pair[i] = (int(shape[0]), int(shape[1]), 0, 0, int(nmaps), int(bool(u8)), 0, 0)
+        pair[i] = (int(shape[0]), int(shape[1]), 0, 0, int(nmaps), int(bool(u8)), int(held), 0)
     tab[8 * batch:16 * batch] = pair.reshape(-1)
     tab[16 * batch] = carry
     if max_flow is not None:
@@ -330,18 +366,22 @@ def chunks(it, n):
         yield buf
 
 
-def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False):
+def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=False):
     """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
     and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
     estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator; n_mid: the
     in-between frames per pair of an interpolating one.  ground_truth: also the rows of unflow_sequence_track_score,
-    behind the others; their flag, track_gt, needs track and ground_truth both."""
+    behind the others; their flag, track_gt, needs track and ground_truth both.  held_out: also the rows of
+    unflow_sequence_interpolate_score, behind everything else."""
     scored = ()
     if ground_truth:
         scored = (('track_scores', 'out_track_scores', (B, 16), torch.int32, 'track_gt'),
                   ('track_err', 'out_track_err', (B,), torch.float64, 'track_gt'),
                   ('gt_track_disp', 'out_gt_track_disp', (B, Ncap, 2), torch.float32, 'track_gt'),
                   ('gt_track_alive', 'out_gt_track_alive', (B, Ncap), torch.uint8, 'track_gt'))
+    if held_out:
+        scored += (('mid_sse', 'out_mid_sse', (n_mid, B, 3), torch.int64, 'held_out'),
+                   ('mid_ssim', 'out_mid_ssim', (n_mid, B, 3), torch.float64, 'held_out'))
     return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
             ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
             ('sums', 'sums', (B, 2, 2), torch.float64, None),
@@ -368,7 +408,9 @@ class _Slot:
         self.desc = pin(B, 8, dtype=torch.int32)
         self.tab = pin(16 * B + 4, dtype=torch.int32) if est.sequence else None   # sequence_tables
         self.gt_flow = self.gt_mask = None
-        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate, True):
+        # held_out: the truth frames of a replay's pairs, [n_mid][B][Hmax][Wmax][3], fp32-sized like the frames
+        self.truth = pin(est.interpolate * B * Hm * Wm * 3 * 4, dtype=torch.uint8) if est.held_out else None
+        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate, True, held_out=True):
             setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
         self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
@@ -452,10 +494,14 @@ class FlowEstimator:
     ground_truth (with sequence): the pairs of a clip are scored against ground truth given with the frames — push_scored returns
     a PairScore per pair (AEE and outliers per map; the occlusion counts with both directions and two maps; with track a
     TrackScore against the chained ground-truth flow), evaluate_sequence the averages over clips; every other method returns
-    what it returns without ground_truth."""
+    what it returns without ground_truth.
+    held_out (with interpolate): the in-between frames are scored against the frames that were left out of the clip, given with
+    the frames — push_held_out returns a HeldOut(frames, holes, sse, psnr, ssim) per pair, for the interpolated frame, the temporal
+    blend and the nearest frame; evaluate_interpolation subsamples full-rate clips and pools the scores; every other method
+    returns what it returns without held_out."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
-                 visual=False, sequence=False, track=False, interpolate=None, ground_truth=False):
+                 visual=False, sequence=False, track=False, interpolate=None, ground_truth=False, held_out=False):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -478,6 +524,10 @@ class FlowEstimator:
         if self.interpolate and not sequence:
             raise ValueError("FlowEstimator: interpolate makes the frames between the frames of a clip; it needs sequence=True or "
                              "sequence='bidirectional'")
+        self.held_out = bool(held_out)                           # the in-between frames are scored
+        if self.held_out and not self.interpolate:
+            raise ValueError("FlowEstimator: held_out scores the in-between frames against the frames left out of the clip; it "
+                             "needs interpolate=n (and sequence=True or sequence='bidirectional')")
         self.ground_truth = bool(ground_truth)                   # sequence: the clip's pairs are scored
         if self.ground_truth and not sequence:
             raise ValueError("FlowEstimator: ground_truth scores the pairs of a clip; it needs sequence=True or "
@@ -515,7 +565,8 @@ class FlowEstimator:
             nb = int(L.unflow_inference_output_blocks(Hm, Wm))
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
-            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate, True):     # out_flow, out_u16, ...
+            for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate, True,
+                                                              held_out=True):     # out_flow, out_u16, ...
                 setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
             self.track_anchors = self.track_disp = self.track_alive = None
             if self.track:
@@ -537,6 +588,14 @@ class FlowEstimator:
                 self.mid_prev = z(Hm * Wm * 3 * 4, dtype=torch.uint8)
                 self.mid_sums = z(int(L.unflow_sequence_interpolate_workspace_bytes(self.interpolate, B, Hm, Wm)) // 8,
                                   dtype=torch.int64)
+            self.mid_truth = self.mid_score_prev = self.mid_score_ws = None
+            if self.held_out:
+                # unflow_sequence_interpolate_score: the staged truth frames (fp32-sized), its own copy of the clip's last frame and
+                # its scratch, zero now and left zero by every launch
+                self.mid_truth = z(self.interpolate * B * Hm * Wm * 3 * 4, dtype=torch.uint8)
+                self.mid_score_prev = z(Hm * Wm * 3 * 4, dtype=torch.uint8)
+                self.mid_score_ws = z(int(L.unflow_sequence_interpolate_score_workspace_bytes(self.interpolate, B, Hm, Wm)) // 8,
+                                      dtype=torch.int64)
             self.vis_shown = self.vis_max = None
             if self.visual:
                 # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
@@ -603,7 +662,7 @@ class FlowEstimator:
         """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds);
         sequence='bidirectional': the output kernel on either block of the engine's 2B rows, then the occlusion kernel, all
         three over the pair table and without ground truth; track: then the tracks, through the pairs of the table; interpolate:
-        then the in-between frames of those pairs; visual: then the pictures, from the same tables."""
+        then the in-between frames of those pairs (held_out: and their scores where the table says held); visual: then the pictures, from the same tables."""
         e, B = self.engine, self.B
         L = _lib.lib()
         e.sequence_carry(self.tab[16 * B:])
@@ -635,6 +694,11 @@ class FlowEstimator:
                                                 ptr(self.out_flow), ptr(bw), ptr(ofw), ptr(obw), ptr(self.mid_prev),
                                                 ptr(self.mid_sums), ptr(self.out_mid), ptr(self.out_mid_holes), e.stream()),
                   "sequence_interpolate")
+        if self.held_out:
+            check(L.unflow_sequence_interpolate_score(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate,
+                                                      ptr(self.out_mid), ptr(self.mid_truth), ptr(self.mid_score_prev),
+                                                      ptr(self.mid_score_ws), ptr(self.out_mid_sse), ptr(self.out_mid_ssim),
+                                                      e.stream()), "sequence_interpolate_score")
         if self.visual:
             bw, occ = (self.out_flow_bw, self.occ[0]) if self.seq_bidir else (None, None)
             check(L.unflow_sequence_visual(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.H, self.W,
@@ -830,7 +894,7 @@ class FlowEstimator:
         truth was staged, the occlusion counts only when it had two maps."""
         special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
         nv = self._num_pictures(nmaps)
-        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate, True):
+        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate, True, held_out=True):
             if special.get(name, name in want):
                 dst, src = getattr(slot, name), getattr(self, attr)
                 if name == 'vis':
@@ -872,7 +936,8 @@ class FlowEstimator:
         return self._one_ahead(self._submit(k, exs, staged, nmaps_of(exs), want, files=files) for k, exs in enumerate(batches))
 
     # ------------------------------------------------------------------------------------------ public API
-    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False, ground_truth=False):
+    def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False, ground_truth=False,
+              held_out=False):
         """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
         one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
         if not sequence:
@@ -901,6 +966,9 @@ class FlowEstimator:
         if ground_truth and not self.ground_truth:
             raise RuntimeError("%s: a sequence estimator without ground truth; build it with FlowEstimator(..., sequence=%r, "
                                "ground_truth=True)" % (what, 'bidirectional' if self.seq_bidir else True))
+        if held_out and not self.held_out:
+            raise RuntimeError("%s: a sequence estimator without held-out frames; build it with FlowEstimator(..., sequence=%r, "
+                               "interpolate=n, held_out=True)" % (what, 'bidirectional' if self.seq_bidir else True))
 
     def _visual_spelling(self):
         """How to build this sequence estimator with pictures, for the messages that ask for it."""
@@ -1316,11 +1384,68 @@ class FlowEstimator:
                             dst[h:].zero_()
                             dst[:h, w:].zero_()
 
-    def _submit_sequence(self, frames, want=('flow',), files=None, max_flow=None, gts=None):
+    def _clip_truths(self, truths, n_frames, what):
+        """The held-out frames of a push, checked before anything is staged: truths[i] holds the n frames between the frame before
+        the i-th new frame and it — n [h, w, 3] arrays or one [n, h, w, 3], of the clip's size and dtype; None for a clip's first
+        frame only.  Returns [None | [n frames]], host arrays as numpy, tensors of this device left where they are."""
+        truths = list(truths)
+        if len(truths) != n_frames:
+            raise ValueError("%s: %d frames, %d sets of held-out frames (one per frame; None for a clip's first frame)"
+                             % (what, n_frames, len(truths)))
+        h, w, u8 = self._clip
+        n, out = self.interpolate, []
+        for i, t in enumerate(truths):
+            first = self._carry == 0 and i == 0
+            if t is None:
+                if not first:
+                    raise ValueError("%s: frame %d has no held-out frames; only a clip's first frame ends no pair" % (what, i))
+                out.append(None)
+                continue
+            if len(t) != n:
+                raise ValueError("%s: frame %d comes with %d held-out frames, the estimator interpolates %d per pair"
+                                 % (what, i, len(t), n))
+            got = []
+            for a in t:
+                if not (isinstance(a, torch.Tensor) and self._on_device((a,))):
+                    a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+                a_u8 = a.dtype == (torch.uint8 if isinstance(a, torch.Tensor) else np.uint8)
+                if tuple(a.shape) != (h, w, 3) or a_u8 != u8:
+                    raise ValueError("%s: the held-out frames of frame %d have the clip's size and type ([%d, %d, 3] %s), got %s %s"
+                                     % (what, i, h, w, 'uint8' if u8 else 'float32', tuple(a.shape), a.dtype))
+                if not u8:
+                    a = a.float() if isinstance(a, torch.Tensor) else a.astype(np.float32, copy=False)
+                got.append(a)
+            out.append(None if first else got)       # the pair that would end at a clip's first frame does not exist
+        return out
+
+    def _stage_truths(self, slot, truths, h, w, u8):
+        """Truth frame j of pair slot i = truths[i][j - 1] at [j - 1][i], at the origin: host arrays through the slot's pinned buffer
+        and one upload, tensors of this device by device copies behind it (as the frames)."""
+        n, B, Hm, Wm = self.interpolate, self.B, self.Hmax, self.Wmax
+        nbytes = n * B * Hm * Wm * 3 * (1 if u8 else 4)
+        pinned = slot.truth[:nbytes].numpy().view(np.uint8 if u8 else np.float32).reshape(n, B, Hm, Wm, 3)
+        on_dev, host = [], False
+        for i, t in enumerate(truths):
+            for j, a in enumerate(t or ()):
+                if isinstance(a, torch.Tensor):
+                    on_dev.append((j, i, a))
+                else:
+                    pinned[j, i, :h, :w] = a
+                    host = True
+        with torch.cuda.device(self.dev):
+            if host:
+                self.mid_truth[:nbytes].copy_(slot.truth[:nbytes], non_blocking=True)
+            dv = self.mid_truth[:nbytes].view(torch.uint8 if u8 else torch.float32).view(n, B, Hm, Wm, 3)
+            for j, i, a in on_dev:
+                dv[j, i, :h, :w].copy_(a, non_blocking=True)
+
+    def _submit_sequence(self, frames, want=('flow',), files=None, max_flow=None, gts=None, truths=None):
         """Stage 1..B new frames of the clip, copy them and the tables in, run, queue the copies back; returns the slot, its
         rows the valid pair slots.  want: the outputs to copy back ('flow', 'u16'; bidirectional: 'flow_bw', 'u16_bw', 'occ';
         visual: 'vis'); files: _replay's.  max_flow: the clip's (_clip_max_flow).  gts (an estimator with ground_truth): the
-        ground truth per new frame (_clip_gts); the pairs are then scored and slot.pending carries their map count."""
+        ground truth per new frame (_clip_gts); the pairs are then scored and slot.pending carries their map count.  truths (an
+        estimator with held_out): the held-out frames per new frame (_clip_truths); the tables then say held and the in-between
+        frames are scored."""
         B, Hm, Wm = self.B, self.Hmax, self.Wmax
         if not 1 <= len(frames) <= B:
             raise ValueError("push: 1 to %d new frames per replay, got %d" % (B, len(frames)))
@@ -1330,6 +1455,8 @@ class FlowEstimator:
         if gts is not None:
             gts = self._clip_gts(gts, len(frames), 'push_scored')
         nmaps = self._clip_nmaps if gts is not None else 0
+        if truths is not None:
+            truths = self._clip_truths(truths, len(frames), 'push_held_out')
         slot = self._slot(self._seq_k)
         self._seq_k += 1
         slot.wait()
@@ -1340,10 +1467,12 @@ class FlowEstimator:
             if not isinstance(a, torch.Tensor):
                 fr[i, :h, :w] = a
         tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow, self._track_words(h, w),
-                                                  nmaps=nmaps)
+                                                  nmaps=nmaps, held=int(truths is not None))
         slot.tab.numpy()[:] = tab
         if nmaps:
             self._stage_gts(slot, gts, h, w)
+        if truths is not None:
+            self._stage_truths(slot, truths, h, w, u8)
         with torch.cuda.device(self.dev):
             self.tab.copy_(slot.tab, non_blocking=True)
             if len(on_dev) < len(frames):
@@ -1473,6 +1602,80 @@ class FlowEstimator:
             out += self._interpolated_of(slot, rows)
         return out
 
+    # held-out scores of the in-between frames
+    HELD_WANT = ('mid', 'mid_holes', 'mid_sse', 'mid_ssim')
+
+    @staticmethod
+    def _held_out_of(slot, rows):
+        """The rows of a finished held-out replay as HeldOut tuples (copies)."""
+        sse, ssim = slot.mid_sse.numpy(), slot.mid_ssim.numpy()
+        out = []
+        for (i, h, w), m in zip(rows, FlowEstimator._interpolated_of(slot, rows)):
+            e = sse[:, i].astype(np.int64)
+            out.append(HeldOut(m.frames, m.holes, e, mid_psnr(e, 3 * h * w), mid_mean_ssim(ssim[:, i], mid_windows(h, w))))
+        return out
+
+    def push_held_out(self, frames, truths):
+        """push_interpolated's frames on an estimator built with held_out=True, with the frames that were left out of the clip:
+        truths[i] holds the n frames between the frame before frames[i] and it — a sequence of n [h, w, 3] arrays or one [n, h, w,
+        3], of the clip's size and dtype, host arrays or tensors of this device; None only for a clip's first frame.  Returns one
+        HeldOut(frames, holes, sse, psnr, ssim) per new pair (the count is push's): push_interpolated's frames and holes, and per
+        in-between frame j and kind (MID_KINDS: the interpolated frame, the temporal blend, the nearest frame) sse int64 [n, 3],
+        psnr [n, 3] = 10 log10(255^2 3 h w / sse) (inf at sse = 0) and ssim [n, 3], the mean SSIM over the 8 x 8 windows inside the
+        frame and the channels (nan without a window)."""
+        self._mode('push_held_out', sequence=True, interpolate=True, held_out=True)
+        slot = self._submit_sequence(list(frames), self.HELD_WANT, truths=list(truths))
+        slot.wait()
+        return self._held_out_of(slot, slot.pending[0])
+
+    def evaluate_interpolation(self, clips, num=None):
+        """The held-out protocol over full-rate clips: `clips` yields lists of frames; of each, frames 0, n + 1, 2 (n + 1), ... go
+        to the network, the n frames between two of them are the truths of that pair, and trailing frames that complete no pair
+        are dropped.  reset() between clips.  num: at most that many pairs.  Returns psnr/<kind> and ssim/<kind> for the kinds mid,
+        blend, nearest — PSNR from the summed integer squared errors (the pooled MSE), SSIM from the summed window sums and counts
+        — the same per position j as psnr_j/<kind> and ssim_j/<kind> (lists of n), holes (the share of interpolated pixels that no
+        source reached) and holes_j, num_examples, per_clip (the pairs of every clip) and per_frame: per pair a dict(sse, psnr,
+        ssim, holes, shape), so that a mean of per-frame PSNRs can be formed by the caller."""
+        self._mode('evaluate_interpolation', sequence=True, interpolate=True, held_out=True)
+        n = self.interpolate
+        sse, ssim = np.zeros((n, 3), np.int64), np.zeros((n, 3))
+        values = wins = 0
+        holes = np.zeros(n, np.int64)
+        per_clip, per_frame = [], []
+        for clip in clips:
+            if num is not None and len(per_frame) >= int(num):
+                break
+            clip = list(clip)
+            pairs = (len(clip) - 1) // (n + 1)
+            if pairs < 1:
+                raise ValueError("evaluate_interpolation: a clip of %d frames holds no pair with %d held-out frame(s)" % (len(clip), n))
+            net = clip[:pairs * (n + 1) + 1:n + 1]
+            truths = [None] + [clip[p * (n + 1) + 1:(p + 1) * (n + 1)] for p in range(pairs)]
+            n0 = len(per_frame)
+            for slot, rows, _ in self._pipeline_sequence(net, self.HELD_WANT, truths=truths):
+                raw = slot.mid_ssim.numpy()
+                for (i, h, w), sc in zip(rows, self._held_out_of(slot, rows)):
+                    if num is not None and len(per_frame) >= int(num):
+                        break
+                    sse += sc.sse
+                    ssim += raw[:, i]
+                    values += 3 * h * w
+                    wins += mid_windows(h, w)
+                    holes += sc.holes
+                    per_frame.append(dict(sse=sc.sse, psnr=sc.psnr, ssim=sc.ssim, holes=sc.holes, shape=(h, w)))
+            per_clip.append(len(per_frame) - n0)
+        if not per_frame:
+            raise ValueError("evaluate_interpolation: the input yielded no pairs")
+        out = {}
+        for k, kind in enumerate(MID_KINDS):
+            out['psnr/' + kind] = float(mid_psnr(sse[:, k].sum(), n * values))
+            out['ssim/' + kind] = float(mid_mean_ssim(math.fsum(ssim[:, k]), n * wins))
+            out['psnr_j/' + kind] = [float(v) for v in mid_psnr(sse[:, k], values)]
+            out['ssim_j/' + kind] = [float(v) for v in mid_mean_ssim(ssim[:, k], wins)]
+        out.update(holes=float(holes.sum()) / (n * values // 3), holes_j=[float(v) / (values // 3) for v in holes],
+                   num_examples=len(per_frame), per_clip=per_clip, per_frame=per_frame, sse=sse)
+        return out
+
     # ground truth along a clip (DESIGN 7.17)
     def _scored_want(self):
         """What a scored replay copies back besides the scores themselves (sums and counts come with nmaps)."""
@@ -1564,14 +1767,18 @@ class FlowEstimator:
                         'per_example_track': tracks})
         return out
 
-    def _pipeline_sequence(self, frames, want, files=None, max_flow=None, gts=None):
-        """reset, then _one_ahead over pushes of B frames (gts: the ground truth per frame, chunked alongside)."""
+    def _pipeline_sequence(self, frames, want, files=None, max_flow=None, gts=None, truths=None):
+        """reset, then _one_ahead over pushes of B frames (gts: the ground truth per frame, chunked alongside; truths: the held-out
+        frames per frame, likewise)."""
         self.reset()
 
         def replays():
             total = 0
             for chunk in chunks(frames, self.B):
                 total += len(chunk)
+                if truths is not None:
+                    yield self._submit_sequence(chunk, want, files, max_flow, truths=truths[total - len(chunk):total])
+                    continue
                 if gts is not None:
                     yield self._submit_sequence(chunk, want, files, max_flow, gts=gts[total - len(chunk):total])
                     continue

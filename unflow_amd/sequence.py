@@ -3,7 +3,7 @@ once (core/inference.FlowEstimator(..., sequence=True)).
 
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
                                   [--output_backward] [--occlusion] [--visual] [--max_flow F]
-                                  [--track] [--track_stride S] [--track_points FILE] [--interpolate N]
+                                  [--track] [--track_stride S] [--track_points FILE] [--interpolate N [--held_out]]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -19,7 +19,11 @@ has left the frame or — where both directions run — was occluded; --track_st
 --track_points FILE: the pixels listed in FILE, `x y` per line, written as one tracks.npz (anchors, disp, alive).
 --interpolate N (1..7) adds N in-between frames per pair, %06d_mid%d.png (pair, j = 1..N): frame j is at time
 j / (N + 1) between the pair's frames, motion-compensated along the flow (along both flows, occluded pixels unblended, where both
-directions run)."""
+directions run).  --held_out (with --interpolate N) scores them: DIR is then the FULL-RATE clip, frames 0, N + 1,
+2 (N + 1), ... go to the network, the N frames between two of them are held out, and trailing frames that complete no pair are
+dropped (their number is printed).  It prints PSNR and SSIM of the interpolated frames, of the temporal blend and of the nearest
+frame against the held-out frames, over the clip and per position j, and the share of hole pixels; the files are then those of the
+subsampled clip, pairs numbered along it."""
 import argparse
 import os
 import sys
@@ -146,6 +150,9 @@ def parser():
                     help='follow the pixels listed in FILE (`x y` per line) instead: one tracks.npz with anchors, disp and alive')
     ap.add_argument('--interpolate', type=int, default=None, metavar='N',
                     help='also N in-between frames per pair (1..7), motion-compensated: %%06d_mid%%d.png (pair, j = 1..N)')
+    ap.add_argument('--held_out', action='store_true',
+                    help='with --interpolate N: DIR is the full-rate clip; every (N + 1)-th frame goes to the network and the '
+                         'in-between frames are scored against the frames left out (PSNR, SSIM; also blend and nearest frame)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -167,6 +174,8 @@ def parse_args(argv=None):
         ap.error("--max_flow must be positive")
     if a.interpolate is not None and not 1 <= a.interpolate <= 7:
         ap.error("--interpolate makes 1 to 7 in-between frames per pair")
+    if a.held_out and a.interpolate is None:
+        ap.error("--held_out scores the in-between frames: it needs --interpolate N")
     if a.track_stride is not None and a.track_stride < 1:
         ap.error("--track_stride must be at least 1")
     if a.track_points is not None and (a.track or a.track_stride is not None):
@@ -195,7 +204,28 @@ def parse_args(argv=None):
         if s != sizes[0]:
             ap.error("%s: a %dx%d frame in a clip of %dx%d frames (%s)" % (p, s[0], s[1], sizes[0][0], sizes[0][1], a.files[0]))
     a.frame_size = sizes[0]
+    a.full_rate, a.dropped = None, 0
+    if a.held_out:                                # the full-rate clip: every (N + 1)-th frame is a network frame
+        pairs = (len(a.files) - 1) // (a.interpolate + 1)
+        if pairs < 1:
+            ap.error("--frames %s: --held_out with --interpolate %d needs at least %d frames, found %d"
+                     % (a.frames, a.interpolate, a.interpolate + 2, len(a.files)))
+        a.full_rate = a.files[:pairs * (a.interpolate + 1) + 1]
+        a.dropped = len(a.files) - len(a.full_rate)
+        a.files = a.full_rate[::a.interpolate + 1]
     return a
+
+
+def held_out_table(scores, n):
+    """evaluate_interpolation's dictionary as the lines the command prints: a row per kind, PSNR and SSIM over the clip and per j."""
+    from .core.inference import MID_KINDS
+    lines = ["%-8s %10s %10s  %s" % ("", "PSNR", "SSIM", "  ".join("j=%d PSNR / SSIM     " % j for j in range(1, n + 1)))]
+    for kind in MID_KINDS:
+        per_j = "  ".join("%8.4f / %8.6f" % (p, q) for p, q in zip(scores['psnr_j/' + kind], scores['ssim_j/' + kind]))
+        lines.append("%-8s %10.4f %10.6f  %s" % (kind, scores['psnr/' + kind], scores['ssim/' + kind], per_j))
+    lines.append("holes    %.4f %% of the interpolated pixels (%s)"
+                 % (100.0 * scores['holes'], "  ".join("j=%d %.4f %%" % (j + 1, 100.0 * v) for j, v in enumerate(scores['holes_j']))))
+    return lines
 
 
 def main(argv=None):
@@ -211,11 +241,19 @@ def main(argv=None):
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
                                         sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
                                         visual='sequence' if a.visual else False, track=a.track_option,
-                                        interpolate=a.interpolate)
+                                        interpolate=a.interpolate, held_out=a.held_out)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
     try:
+        if a.held_out:
+            if a.dropped:
+                print("dropped %d trailing frame(s) that complete no pair of %d held-out frame(s)" % (a.dropped, a.interpolate))
+            full = [read_frame(p) for p in a.full_rate] if a.host_decode else list(device_frames(a.full_rate, a.batch, est.dev))
+            scores = est.evaluate_interpolation([full])
+            print("held out: %d pair(s), %d frame(s) each" % (scores['num_examples'], a.interpolate))
+            print("\n".join(held_out_table(scores, a.interpolate)))
+            del full
         frames = (read_frame(p) for p in a.files) if a.host_decode else device_frames(a.files, a.batch, est.dev)
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
                                     deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion, visual=a.visual,
