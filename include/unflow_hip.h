@@ -844,6 +844,41 @@ int unflow_sequence_interpolate(const void* frames, const int* tab, int B, int H
                                 const float* flow_bw, const unsigned char* occ_fw, const unsigned char* occ_bw, void* prev,
                                 void* workspace, unsigned char* out_mid, int* out_holes, unflow_stream_t stream);
 
+/* In-between frames, consistency-ordered (FlowEstimator(..., interpolate=n, interpolate_order=k); csrc/interpolate.hip, DESIGN
+ * 7.19): unflow_sequence_interpolate's arguments, workspace (the same unflow_sequence_interpolate_workspace_bytes, zero on entry,
+ * left zero, no memset node), outputs and prev, plus order, 0..4.  order = 0 is unflow_sequence_interpolate, byte for byte.  For
+ * order = k >= 1 its definition changes in the places below and nowhere else; this text is part of the ABI,
+ * tests/mid_order_ref.py mirrors it step by step and the kernels are held to equality.
+ * Per source pixel, passes A and B alike.  here = the pixel's own colour (im0(x, y) in pass A, im1(x, y) in pass B); wp = the
+ *   other frame warped by the flow (c1 in pass A, c0 in pass B: the same image_warp taps and tap order);
+ *   e = fminf((|here.r - wp.r| + |here.g - wp.g|) + |here.b - wp.b|, 765.f), every fp32 difference, absolute value and sum rounded
+ *     on its own; a NaN gives 765, by fminf's rule;
+ *   d = min(((int)e) >> (6 - k), 6);  conf = 64 >> d: 64 where the two frames agree along the flow, 1 at the floor.  At k = 1
+ *     conf halves per 32 summed grey levels of disagreement, at k = 4 per 4.
+ *   A pixel whose occlusion mask is non-zero (both directions): conf = 1 and its own colour; as in unflow_sequence_interpolate its
+ *     warp taps are not read.  A pixel with d == 6: its own colour, unblended, as if it were masked.  Every other pixel: the blend
+ *     of unflow_sequence_interpolate (s * im0 + t * c1, or s * c0 + t * im1).
+ *   Tap weight W = wx * wy * a * conf, the same W into the three colour sums and the weight sum.  The targets, the dropping rule,
+ *     the flow test, the 8.8 quantisation and the 6-bit fractions are unflow_sequence_interpolate's.
+ * Normalise.  Sw and Sc are the sums of W and W * cq; Sw0 is the sum of the conf-less weights wx * wy * a of the same taps.  A
+ *   target is a HOLE iff Sw0 < 1024, so the set of holes is exactly unflow_sequence_interpolate's at every order: a hole is a
+ *   target that too little of the source lands on, however well that little agrees (with the test on Sw, which conf lifts up to
+ *   64-fold, a sliver of a consistent pixel would close a hole with its colour alone).  Not a hole: out = (Sc + Sw * 128) /
+ *   (Sw * 256), as there.  A hole with both directions: the temporal blend, as there.  A hole in one direction: the byte of the
+ *   LATER frame, (q(im1) + 128) / 256 — a pixel nothing lands on was uncovered by the motion, and im1 is where it is visible.
+ *   Holes are counted as there.
+ *   No fifth sum: the weight word of the workspace holds Sw in bits [0, 46) and Sw0 mod 2^18 above them, one atomic add of
+ *   W + ((wx * wy * a) << 46) per tap.  Sw0 <= Sw <= 64 Sw0, so Sw < 1024 is a hole and Sw >= 65536 is none whatever the top bits
+ *   say, and in between Sw0 <= Sw < 2^16 has not wrapped: the test is exact.  Sw < 2^24 taps * 4096 * 7 * 64 < 2^45.
+ * Range.  One tap adds at most 4096 * 7 * 64 * 65280 < 2^37 to a colour sum, and a target gets at most one tap per source pixel
+ *   and direction.  With order >= 1 the entry returns UNFLOW_ERR_SHAPE for Hmax * Wmax > 2^23 (tested first, before the NULL
+ *   checks): up to 2^26 taps fit a signed 64-bit sum, and a 3840 x 2160 frame passes.
+ * The ordered splat reads nothing unflow_sequence_interpolate's does not read.  Deterministic in the same way: integer atomics only.
+ * UNFLOW_ERR_SHAPE, and nothing is launched, for order outside 0..4 and for everything unflow_sequence_interpolate refuses. */
+int unflow_sequence_interpolate_ordered(const void* frames, const int* tab, int B, int Hmax, int Wmax, int n, const float* flow_fw,
+                                        const float* flow_bw, const unsigned char* occ_fw, const unsigned char* occ_bw, void* prev,
+                                        void* workspace, unsigned char* out_mid, int* out_holes, int order, unflow_stream_t stream);
+
 /* Held-out scores of the in-between frames (FlowEstimator(..., sequence=..., interpolate=n, held_out=True);
  * csrc/interpolate_score.hip): the frames that unflow_sequence_interpolate made, and two candidates that need no flow,
  * against the frames that were left out of the clip, by squared error and by SSIM.  Launched behind unflow_sequence_interpolate.

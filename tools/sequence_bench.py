@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N [--held_out] |
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N [--order K | --held_out] |
                                     --ground_truth [--track]]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
@@ -33,6 +33,10 @@ graph of the interpolating estimator against the same run's estimator without th
 events around 50 launches — unflow_sequence_interpolate and the replay's output kernels (unflow_inference_output, with both
 directions twice and unflow_inference_occlusion), with the atomic bytes the splat issues.  Recorded, one line per N, in
 profiles/sequence_interpolate_bench_line.json.
+
+--interpolate N --order K: the estimator with the consistency-ordered splat against the SAME RUN's unordered
+interpolating estimator, the two taking turns; and the two entries alone on one set of buffers (device events around 50 launches),
+taking turns as well.  One line per N in profiles/sequence_interpolate_order_bench_line.json.
 
 --interpolate N --held_out: the estimator that also scores its in-between frames against held-out frames, against
 the SAME RUN's interpolating estimator without the option, the two taking turns; and unflow_sequence_interpolate_score alone (device
@@ -69,7 +73,7 @@ def _frames(n):
 
 
 def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None,
-               ground_truth=False, held_out=False):
+               ground_truth=False, held_out=False, interpolate_order=None):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
     pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
@@ -85,6 +89,8 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False
         kw['track'] = track
     if interpolate:
         kw['interpolate'] = interpolate
+    if interpolate_order:
+        kw['interpolate_order'] = interpolate_order
     if ground_truth:
         kw['ground_truth'] = True
     if held_out:
@@ -499,6 +505,57 @@ def interpolate_case(seq, n, iters, warmup, rounds, B=4):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --interpolate N --order K (7.19)
+def order_case(seq, n, order, iters, warmup, rounds, B=4):
+    """The ordered estimator against the SAME RUN's unordered interpolating estimator, the two taking turns; and the two entries
+    alone on the ordered estimator's buffers, taking turns as well."""
+    import gc
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    mid, _ = _estimator('C', B, seq, interpolate=n)
+    mid.interpolate_sequence(_frames(3 * B))               # the tables of the last replay: a carried frame, B pairs
+    ordered, mem = _estimator('C', B, seq, interpolate=n, interpolate_order=order)
+    ordered.interpolate_sequence(_frames(3 * B))
+    runs = {'interpolate': mid.graph.replay, 'ordered': ordered.graph.replay}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence=seq if seq is True else str(seq), n=n, order=order, rounds=rounds)
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['ordered']['estimator_MB'] = round(mem / 1e6, 1)
+    out['ordered_over_interpolate'] = round(out['ordered']['ms_per_pair'] / out['interpolate']['ms_per_pair'], 4)
+    out['ordered_added_us_per_replay'] = round((out['ordered']['ms_per_pair'] - out['interpolate']['ms_per_pair']) * B * 1e3, 2)
+    L, e = _lib.lib(), ordered
+    bw, ofw, obw = (e.out_flow_bw, e.occ[0], e.occ[1]) if e.seq_bidir else (None, None, None)
+    args = (ptr(e.frames), ptr(e.tab), B, e.Hmax, e.Wmax, n, ptr(e.out_flow), ptr(bw), ptr(ofw), ptr(obw), ptr(e.mid_prev),
+            ptr(e.mid_sums), ptr(e.out_mid), ptr(e.out_mid_holes))
+    entries = {'interpolate': lambda: check(L.unflow_sequence_interpolate(*args, e.engine.stream()), "sequence_interpolate"),
+               'ordered': lambda: check(L.unflow_sequence_interpolate_ordered(*args, order, e.engine.stream()),
+                                        "sequence_interpolate_ordered")}
+    us = {k: [] for k in entries}
+    for _ in range(rounds):
+        for k, fn in entries.items():
+            us[k].append(_launches_us(fn, e.dev))
+    px, dirs = FRAME[0] * FRAME[1] * B, 2 if e.seq_bidir else 1
+    atomic_bytes = px * n * dirs * 128                     # 4 targets x 4 sums x 8 bytes per source pixel, j and direction, at most
+    out['kernel'] = {k: dict(us=round(statistics.mean(v), 2), rounds_us=[round(x, 2) for x in v],
+                             atomic_TBps_if_all_of_it=round(atomic_bytes / statistics.mean(v) / 1e6, 3)) for k, v in us.items()}
+    out['kernel']['atomic_MB'] = round(atomic_bytes / 1e6, 1)
+    out['kernel']['how'] = 'device events around 50 back-to-back calls of either entry (three launches each), launch gaps included'
+    out['kernel']['ordered_over_interpolate'] = round(statistics.mean(us['ordered']) / statistics.mean(us['interpolate']), 4)
+    entries['ordered']()                                   # the outputs of the ordered entry, for the hole share
+    out['holes_share'] = round(float(e.out_mid_holes.float().sum().item()) / (px * n), 5)
+    assert not bool(e.mid_sums.any())
+    del mid, ordered
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- --interpolate N --held_out (7.18)
 def held_out_case(seq, n, iters, warmup, rounds, B=4):
     """The scoring estimator against the SAME RUN's interpolating estimator without the option, the two taking turns; and the
@@ -654,6 +711,9 @@ def main():
     ap.add_argument('--interpolate', type=int, default=None, metavar='N',
                     help='the estimator with N in-between frames per pair against the same one without, FlowNetC at B = 4, both '
                          'sequence modes, and the kernels alone (DESIGN 7.16)')
+    ap.add_argument('--order', type=int, default=None, metavar='K',
+                    help='with --interpolate N: the estimator with the consistency-ordered splat of steepness K (1..4) against the '
+                         'same run\'s unordered interpolating estimator, and the two entries alone (DESIGN 7.19)')
     ap.add_argument('--held_out', action='store_true',
                     help='with --interpolate N: the estimator that scores its in-between frames against the same run\'s '
                          'interpolating estimator without the option, and the scoring entry alone (DESIGN 7.18)')
@@ -668,6 +728,17 @@ def main():
                             'alone) is the yardstick beside it',
                    note='one run on one box; box to box +- 3 %',
                    cases=[gt_case(seq, a.track, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
+        print(json.dumps(res))
+        return
+    if a.order is not None:
+        if a.interpolate is None or a.held_out or not 1 <= a.order <= 4:
+            ap.error("--order K, 1..4, needs --interpolate N (and no --held_out)")
+        res = dict(metric='sequence_interpolate_ordered_ms_per_pair_over_the_same_runs_unordered_interpolating_estimator', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup, n=a.interpolate, order=a.order,
+                   expected='from the code: the splat runs at the rate of its 64-bit atomics (0.33 - 0.39 TB/s, DESIGN 7.16) and the '
+                            'ordered one adds a few VALU operations per source pixel, so inside the +- 3 % box-to-box spread',
+                   note='one run on one box; box to box +- 3 %',
+                   cases=[order_case(seq, a.interpolate, a.order, a.iters, a.warmup, a.rounds) for seq in (True, 'bidirectional')])
         print(json.dumps(res))
         return
     if a.held_out:

@@ -60,6 +60,7 @@ def lib():
         _lib.unflow_sequence_track_score_workspace_bytes.restype = ctypes.c_size_t
         _lib.unflow_sequence_interpolate.restype = ctypes.c_int
         _lib.unflow_sequence_interpolate_workspace_bytes.restype = ctypes.c_size_t
+        _lib.unflow_sequence_interpolate_ordered.restype = ctypes.c_int
         _lib.unflow_sequence_interpolate_score.restype = ctypes.c_int
         _lib.unflow_sequence_interpolate_score_workspace_bytes.restype = ctypes.c_size_t
         for name in ('unflow_deflate_segment_bound', 'unflow_deflate_stream_bound', 'unflow_deflate_slot_bytes'):

@@ -66,7 +66,9 @@ and track) kernels either sequence graph runs
                                    masks) -> per pair n motion-compensated frames, an integer splat normalised by its weight, and
                                    the count of the holes; the clip's last staged frame stays on the device for the next replay
 
-(push_interpolated, interpolate_sequence, export_sequence(interpolate=True)).
+(push_interpolated, interpolate_sequence, export_sequence(interpolate=True)).  With interpolate_order=k the graph runs
+unflow_sequence_interpolate_ordered(..., k) in its place, on the same buffers: the splat weighted by how well the two frames agree
+along each pixel's flow.  Everything on top is unchanged.
 
 sequence=True | 'bidirectional' with ground_truth=True: scores along a clip.  The ground truth of every pair is staged
 per pair slot, the pair table carries its number of maps, the output kernel on the forward rows scores it (the occlusion kernel
@@ -233,6 +235,19 @@ def interpolate_option(interpolate):
     if isinstance(interpolate, bool) or not isinstance(interpolate, (int, np.integer)) or not 1 <= int(interpolate) <= 7:
         raise ValueError("FlowEstimator: interpolate=n is an int, 1 to 7 in-between frames per pair, got %r" % (interpolate,))
     return int(interpolate)
+
+
+def interpolate_order_option(interpolate_order, interpolate=1):
+    """FlowEstimator's interpolate_order option -> the order of unflow_sequence_interpolate_ordered: 0 (None or 0: the plain
+    entry) or an int k in 1..4, the steepness of the consistency weight.  Anything else, or a k without in-between
+    frames (interpolate: interpolate_option's number), is a ValueError."""
+    if interpolate_order is None:
+        return 0
+    if isinstance(interpolate_order, bool) or not isinstance(interpolate_order, (int, np.integer)) or not 0 <= int(interpolate_order) <= 4:
+        raise ValueError("FlowEstimator: interpolate_order=k is an int, 1 to 4 (None or 0: unordered), got %r" % (interpolate_order,))
+    if int(interpolate_order) and not interpolate:
+        raise ValueError("FlowEstimator: interpolate_order orders the splat of the in-between frames; it needs interpolate=n")
+    return int(interpolate_order)
 
 
 def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False, mid=0):
@@ -491,6 +506,10 @@ class FlowEstimator:
     push_interpolated / interpolate_sequence return an Interpolated(frames, holes) per pair, export_sequence(interpolate=True)
     writes them; every other method returns what it returns without interpolate.  reset() starts a new clip: the frame kept
     from the last one is not used.
+    interpolate_order (with interpolate): k in 1..4, the consistency-ordered splat — every splatted pixel is weighted
+    by how well the two frames agree along its flow (the weight halves per 64 >> k summed grey levels), pixels that disagree are
+    not blended, and on a one-direction estimator a hole takes the later frame's colour.  None or 0: the plain splat.  Nothing
+    else changes: the same methods, tuples and files.
     ground_truth (with sequence): the pairs of a clip are scored against ground truth given with the frames — push_scored returns
     a PairScore per pair (AEE and outliers per map; the occlusion counts with both directions and two maps; with track a
     TrackScore against the chained ground-truth flow), evaluate_sequence the averages over clips; every other method returns
@@ -501,7 +520,8 @@ class FlowEstimator:
     returns what it returns without held_out."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
-                 visual=False, sequence=False, track=False, interpolate=None, ground_truth=False, held_out=False):
+                 visual=False, sequence=False, track=False, interpolate=None, ground_truth=False, held_out=False,
+                 interpolate_order=None):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -524,6 +544,7 @@ class FlowEstimator:
         if self.interpolate and not sequence:
             raise ValueError("FlowEstimator: interpolate makes the frames between the frames of a clip; it needs sequence=True or "
                              "sequence='bidirectional'")
+        self.interpolate_order = interpolate_order_option(interpolate_order, self.interpolate)    # 0: the plain splat
         self.held_out = bool(held_out)                           # the in-between frames are scored
         if self.held_out and not self.interpolate:
             raise ValueError("FlowEstimator: held_out scores the in-between frames against the frames left out of the clip; it "
@@ -690,10 +711,12 @@ class FlowEstimator:
                                                 e.stream()), "sequence_track_score")
         if self.interpolate:
             bw, ofw, obw = (self.out_flow_bw, self.occ[0], self.occ[1]) if self.seq_bidir else (None, None, None)
-            check(L.unflow_sequence_interpolate(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate,
-                                                ptr(self.out_flow), ptr(bw), ptr(ofw), ptr(obw), ptr(self.mid_prev),
-                                                ptr(self.mid_sums), ptr(self.out_mid), ptr(self.out_mid_holes), e.stream()),
-                  "sequence_interpolate")
+            args = (ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate, ptr(self.out_flow), ptr(bw), ptr(ofw),
+                    ptr(obw), ptr(self.mid_prev), ptr(self.mid_sums), ptr(self.out_mid), ptr(self.out_mid_holes))
+            if self.interpolate_order:
+                check(L.unflow_sequence_interpolate_ordered(*args, self.interpolate_order, e.stream()), "sequence_interpolate_ordered")
+            else:
+                check(L.unflow_sequence_interpolate(*args, e.stream()), "sequence_interpolate")
         if self.held_out:
             check(L.unflow_sequence_interpolate_score(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate,
                                                       ptr(self.out_mid), ptr(self.mid_truth), ptr(self.mid_score_prev),

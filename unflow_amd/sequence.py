@@ -3,7 +3,7 @@ once (core/inference.FlowEstimator(..., sequence=True)).
 
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
                                   [--output_backward] [--occlusion] [--visual] [--max_flow F]
-                                  [--track] [--track_stride S] [--track_points FILE] [--interpolate N [--held_out]]
+                                  [--track] [--track_stride S] [--track_points FILE] [--interpolate N [--order K] [--held_out]]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -19,7 +19,9 @@ has left the frame or — where both directions run — was occluded; --track_st
 --track_points FILE: the pixels listed in FILE, `x y` per line, written as one tracks.npz (anchors, disp, alive).
 --interpolate N (1..7) adds N in-between frames per pair, %06d_mid%d.png (pair, j = 1..N): frame j is at time
 j / (N + 1) between the pair's frames, motion-compensated along the flow (along both flows, occluded pixels unblended, where both
-directions run).  --held_out (with --interpolate N) scores them: DIR is then the FULL-RATE clip, frames 0, N + 1,
+directions run).  --order K (1..4, with --interpolate N) orders that splat: every pixel is weighted by how well the
+two frames agree along its flow, the weight halving per 64 >> K summed grey levels, pixels that disagree are not blended, and in
+one direction a hole takes the later frame's colour; the files are the same.  --held_out (with --interpolate N) scores them: DIR is then the FULL-RATE clip, frames 0, N + 1,
 2 (N + 1), ... go to the network, the N frames between two of them are held out, and trailing frames that complete no pair are
 dropped (their number is printed).  It prints PSNR and SSIM of the interpolated frames, of the temporal blend and of the nearest
 frame against the held-out frames, over the clip and per position j, and the share of hole pixels; the files are then those of the
@@ -150,6 +152,8 @@ def parser():
                     help='follow the pixels listed in FILE (`x y` per line) instead: one tracks.npz with anchors, disp and alive')
     ap.add_argument('--interpolate', type=int, default=None, metavar='N',
                     help='also N in-between frames per pair (1..7), motion-compensated: %%06d_mid%%d.png (pair, j = 1..N)')
+    ap.add_argument('--order', type=int, default=None, metavar='K',
+                    help='with --interpolate N: the consistency-ordered splat of steepness K (1..4) in place of the plain one')
     ap.add_argument('--held_out', action='store_true',
                     help='with --interpolate N: DIR is the full-rate clip; every (N + 1)-th frame goes to the network and the '
                          'in-between frames are scored against the frames left out (PSNR, SSIM; also blend and nearest frame)')
@@ -174,6 +178,10 @@ def parse_args(argv=None):
         ap.error("--max_flow must be positive")
     if a.interpolate is not None and not 1 <= a.interpolate <= 7:
         ap.error("--interpolate makes 1 to 7 in-between frames per pair")
+    if a.order is not None and not 1 <= a.order <= 4:
+        ap.error("--order is the steepness of the ordered splat, 1 to 4")
+    if a.order is not None and a.interpolate is None:
+        ap.error("--order orders the splat of the in-between frames: it needs --interpolate N")
     if a.held_out and a.interpolate is None:
         ap.error("--held_out scores the in-between frames: it needs --interpolate N")
     if a.track_stride is not None and a.track_stride < 1:
@@ -241,7 +249,7 @@ def main(argv=None):
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
                                         sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
                                         visual='sequence' if a.visual else False, track=a.track_option,
-                                        interpolate=a.interpolate, held_out=a.held_out)
+                                        interpolate=a.interpolate, held_out=a.held_out, interpolate_order=a.order)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
