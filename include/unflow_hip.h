@@ -921,6 +921,58 @@ int unflow_sequence_interpolate_score(const void* frames, const int* tab, int B,
                                       const unsigned char* out_mid, const void* truth, void* prev, void* workspace,
                                       long long* out_sse, double* out_ssim, unflow_stream_t stream);
 
+/* Camera motion along a clip (csrc/stabilise.hip): per valid pair slot i of a sequence replay, of size (h, w), a robust
+ * affine fit to the forward flow, the residual of every pixel against it, the camera path composed along the clip and the pair's
+ * LATER frame (frame-table slot i of `frames`, uint8 or fp32 per word 5 of the pair row) resampled along that path.  tab: the
+ * device tables of the replay (frame table at word 0, pair table at word 8 B, carry source at word 16 B).  A pair slot with h <= 0,
+ * w <= 0, h > Hmax or w > Wmax — and slot 0 while the carry source is 0, unflow_sequence_interpolate's rule — is not a pair:
+ * nothing is written for it, and nothing outside (h, w) for any slot.
+ * Everything is integer but the solve; >> is an arithmetic shift of an int64.
+ *   Quantise.  (u, v) = flow_fw[i](x, y).  VALID: both components finite and of magnitude < 4096 (tested before any integer
+ *     conversion).  U = rintf(u * 64), V likewise.  X = 2 x - (w - 1), Y = 2 y - (h - 1): half pixels about the frame centre.
+ *     ELIGIBLE: valid, and occ_fw NULL or occ_fw[i](x, y) == 0.
+ *   Model.  P = {Tu, Lux, Luy, Tv, Lvx, Lvy} int64, T in 2^-16 px, L in 2^-24 per pixel.  pred_u = Tu + ((Lux X + Luy Y + 256) >>
+ *     9), r_u = (U << 10) - pred_u, v likewise; e = |r_u| + |r_v|, the L1 residual in 2^-16 px.
+ *   Fit.  P = 0, status = 1; iterations r = 0 .. iters (R).  The weight g of an eligible pixel is 1 for r = 0; for r >= 1, with e
+ *     under the current P, k_r = max(0, tol - (R - r)), d = min(e >> (17 - k_r), 6), g = d >= 6 ? 0 : 64 >> d.  Others weigh 0.
+ *     Thirteen int64 sums over the slot: g, gX, gY, gXX, gXY, gYY, gU, gXU, gYU, gV, gXV, gYV and n = #{g > 0}.  The solve, fp64,
+ *     every operation rounded on its own, A the symmetric matrix of the first six sums in the order (1, X, Y): degenerate if n <
+ *     16; a00 = A00 must be > 0; m1 = A10 / a00, m2 = A20 / a00; a11 = A11 - m1 A01, a12 = A12 - m1 A02, a22 = A22 - m2 A02; a11
+ *     must be > 0; m3 = a12 / a11, a22 = a22 - m3 a12; a22 must be > 0 (a comparison with a NaN is false: degenerate); per right-hand
+ *     side (b0, b1, b2) — the U sums, then the V sums — b1' = b1 - m1 b0, b2' = (b2 - m2 b0) - m3 b1', p2 = b2' / a22, p1 = (b1' -
+ *     a12 p2) / a11, p0 = ((b0 - A01 p1) - A02 p2) / a00; T = rint(p0 * 1024) clamped to +-2^28, L = rint(p1 * 2^19), rint(p2 *
+ *     2^19) clamped to +-2^23 (the clamp: not below the upper limit -> the upper limit, then below the lower -> the lower).  A
+ *     degenerate iteration ends the loop and keeps P; a successful one replaces P and sets status = 0.
+ *     out_motion[i] = {P[0..5], status | (successful iterations << 8), n of the last successful iteration}.
+ *   Path.  D(p) = c + Dt + Dl (p - c) maps stabilised to later-frame coordinates, Dt in 2^-16 px, Dl in 2^-24; the state path[8] =
+ *     {Dt_x, Dl_xx, Dl_xy, Dt_y, Dl_yx, Dl_yy, 0, 0} is kept by the caller along a clip and needs no initialisation: with carry
+ *     source 0 the clip starts from the identity (Dt = 0, Dl = 2^24 I) whatever it holds (unflow_sequence_track's rule).  Per valid
+ *     slot in order, Ml = 2^24 I + L: Dt' = T + ((Ml Dt + 2^23) >> 24), Dl' = (Ml Dl + 2^23) >> 24 (each entry the sum of two
+ *     products, then one rounding).  follow = s >= 1: per word, E = D' - identity, D = identity + E - (E >> s); s = 0: D = D' (lock
+ *     mode: every frame in the first frame's coordinates).  Dt is clamped to +-2^30, Dl to +-2^26.  out_path[i] = D; after the last
+ *     valid slot path = D; a replay without a valid pair leaves path alone.
+ *   Residual map.  Under the final P, out_resid = min(255, e >> 14), quarter pixels; an invalid pixel gives 255.
+ *   Stabilised frame.  Px = 2 (Dt_x + ((Dl_xx X + Dl_xy Y + 256) >> 9)) + ((w - 1) << 16) in 2^-17 px, Py likewise.  COVERED: 0 <=
+ *     Px <= (w - 1) << 17 and the same in y.  ix = Px >> 17, qx = (Px >> 9) & 255, the neighbour min(ix + 1, w - 1); colours in 8.8
+ *     fixed point (unflow_sequence_interpolate's rule); byte = (sum of (256 - qx | qx)(256 - qy | qy) colour + 2^23) >> 24.  An
+ *     uncovered pixel is (0, 0, 0).
+ *   out_counts[i] = {valid, valid but not eligible, eligible with min(e >> (17 - tol), 6) = 6 under the final P, uncovered}.
+ * Ranges.  Hmax, Wmax <= 4096: |X|, |Y| < 2^13, g <= 2^6, |U| <= 2^18, so a term is below 2^(6 + 13 + 18) = 2^37 and a sum over
+ * 2^24 pixels below 2^61.  |T| <= 2^28, |L| <= 2^23: |L X + L Y + 256| < 2^38, |pred| < 2^30, e < 2^32.  |Ml| < 2^25, |Dt| <= 2^30,
+ * |Dl| <= 2^26: a sum of two products is below 2^57.  |Dl X + Dl Y + 256| < 2^41, |Px| < 2^33; a tap sum is below 2^16 2^16 = 2^32.
+ * Outputs: out_motion, out_path [B][8] int64, out_resid [B][Hmax][Wmax], out_stab [B][Hmax][Wmax][3], out_counts [B][4].
+ * workspace: unflow_sequence_stabilise_workspace_bytes(B) bytes (0 for a B the entry refuses), zero on entry of the first launch
+ * and left zero by every launch (no memset node in a captured graph); workspace, path, out_motion, out_path and flow_fw 8-byte aligned
+ * (UNFLOW_ERR_UNSUPPORTED otherwise).  The sums use 64-bit integer atomics; no float atomics, no float reductions: two launches and
+ * two graph replays give the same bytes.  UNFLOW_ERR_NULL for a NULL pointer other than occ_fw; UNFLOW_ERR_SHAPE for B < 1 or
+ * above 65535 (the grid's rows), Hmax or Wmax outside 1..4096, tol or iters outside 0..4, follow outside 0..8.  A refused call
+ * launches and writes nothing. */
+size_t unflow_sequence_stabilise_workspace_bytes(int B);
+int unflow_sequence_stabilise(const void* frames, const int* tab, int B, int Hmax, int Wmax, const float* flow_fw,
+                              const unsigned char* occ_fw, int tol, int iters, int follow, long long* path, void* workspace,
+                              long long* out_motion, long long* out_path, unsigned char* out_resid, unsigned char* out_stab,
+                              int* out_counts, unflow_stream_t stream);
+
 /* ===================================================================== */
 /* PNG decode on the device (csrc/png_decode.hip, core/png_device.py)      */
 /* ===================================================================== */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --interpolate N [--order K | --held_out] |
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --stabilise | --interpolate N [--order K | --held_out] |
                                     --ground_truth [--track]]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
@@ -47,7 +47,12 @@ estimator (two-map ground truth staged, every pair scored; with --track dense tr
 against the SAME RUN's estimator without ground_truth (with --track: the plain tracking estimator), the two taking turns; with
 --track the new kernel alone (device events around 50 launches) with the bytes it must move; and the wall time per pair of
 evaluate_sequence against pair-mode evaluate on the same synthetic clip from host arrays.  Recorded in
-profiles/sequence_gt_bench_line.json."""
+profiles/sequence_gt_bench_line.json.
+
+--stabilise: FlowNetC at B = 4, both sequence modes: ms per pair of the replayed graph of the stabilising estimator
+(the defaults: tol 2, iters 3, follow 0) against the SAME RUN's plain estimator, the two taking turns; and
+unflow_sequence_stabilise alone (device events around 50 calls, nine launches each) with the bytes it must move.  One line per mode
+in profiles/sequence_stabilise_bench_line.json."""
 import argparse
 import csv
 import glob
@@ -73,7 +78,7 @@ def _frames(n):
 
 
 def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None,
-               ground_truth=False, held_out=False, interpolate_order=None):
+               ground_truth=False, held_out=False, interpolate_order=None, stabilise=None):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
     pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
@@ -95,6 +100,8 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False
         kw['ground_truth'] = True
     if held_out:
         kw['held_out'] = True
+    if stabilise:
+        kw['stabilise'] = stabilise
     est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
@@ -692,6 +699,95 @@ def gt_case(seq, track, iters, warmup, rounds, B=4):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --stabilise
+def stabilise_bytes(iters, B=4):
+    """Compulsory bytes of unflow_sequence_stabilise per replay on FRAME: the flow (8 bytes per pixel) is read iters + 2 times — once
+    per fit and once for the residual map — the uint8 frame (3 bytes) once, and four bytes are written per pixel."""
+    return FRAME[0] * FRAME[1] * B * (8 * (iters + 2) + 3 + 4)
+
+
+def stabilise_kernels_only(mode, iters, B=4):
+    """Child: unflow_sequence_stabilise alone on a set-up FlowNetC estimator, `iters` times (carry source B, every pair valid)."""
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    e, _ = _estimator('C', B, 'bidirectional' if mode == 'bidir' else True, stabilise=True)
+    e.stabilise_sequence(_frames(3 * B))
+    L, o = _lib.lib(), e.stabilise
+    torch.cuda.synchronize()
+    for _ in range(iters):
+        check(L.unflow_sequence_stabilise(ptr(e.frames), ptr(e.tab), B, e.Hmax, e.Wmax, ptr(e.out_flow),
+                                          ptr(e.occ[0]) if e.seq_bidir else None, o['tol'], o['iters'], o['follow'], ptr(e.stab_path),
+                                          ptr(e.stab_ws), ptr(e.out_stab_motion), ptr(e.out_stab_path), ptr(e.out_stab_resid),
+                                          ptr(e.out_stab), ptr(e.out_stab_counts), e.engine.stream()), "sequence_stabilise")
+    torch.cuda.synchronize()
+
+
+def stabilise_rocprof(seq, iters=50):
+    """Per-kernel times of the entry from a counters-free kernel-trace child: {kernel: calls, mean us}, and the sum of one entry's
+    nine launches (the estimator's own few replays are in the means too)."""
+    rows, err = _rocprof(['--stabilise-kernels-only', 'bidir' if seq == 'bidirectional' else 'fw', '--iters', str(iters)])
+    if err:
+        return err
+    out, R = {}, 3
+    per_entry = {'st_accumulate_kernel': R + 1, 'st_solve_kernel': R + 1, 'st_apply_kernel': 1}
+    for row in rows:
+        for name in per_entry:
+            if name in row['Name']:
+                out[name] = dict(calls=int(row['Calls']), us=round(float(row['AverageNs']) / 1e3, 2))
+    if len(out) == len(per_entry):
+        out['kernels_us_per_entry'] = round(sum(out[n]['us'] * k for n, k in per_entry.items()), 2)
+    return out
+
+
+def stabilise_case(seq, iters, warmup, rounds, B=4, rocprof=False):
+    """The stabilising estimator (defaults: tol 2, iters 3, follow 0) against the SAME RUN's plain estimator, the two taking turns;
+    and the new entry alone, with the bytes it has to move."""
+    import gc
+    import torch
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    plain, _ = _estimator('C', B, seq)
+    stab, mem = _estimator('C', B, seq, stabilise=True)
+    stab.stabilise_sequence(_frames(3 * B))                # the tables of the last replay: a carried frame, B pairs
+    runs = {'plain': plain.graph.replay, 'stabilise': stab.graph.replay}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence=seq if seq is True else str(seq), rounds=rounds, options=dict(stab.stabilise))
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['stabilise']['estimator_MB'] = round(mem / 1e6, 1)
+    out['stabilise_over_plain'] = round(out['stabilise']['ms_per_pair'] / out['plain']['ms_per_pair'], 4)
+    out['stabilise_added_us_per_replay'] = round((out['stabilise']['ms_per_pair'] - out['plain']['ms_per_pair']) * B * 1e3, 2)
+    L, e, o = _lib.lib(), stab, stab.stabilise
+
+    def kernel():
+        check(L.unflow_sequence_stabilise(ptr(e.frames), ptr(e.tab), B, e.Hmax, e.Wmax, ptr(e.out_flow),
+                                          ptr(e.occ[0]) if e.seq_bidir else None, o['tol'], o['iters'], o['follow'], ptr(e.stab_path),
+                                          ptr(e.stab_ws), ptr(e.out_stab_motion), ptr(e.out_stab_path), ptr(e.out_stab_resid),
+                                          ptr(e.out_stab), ptr(e.out_stab_counts), e.engine.stream()), "sequence_stabilise")
+    us = [_launches_us(kernel, e.dev) for _ in range(rounds)]
+    nbytes = stabilise_bytes(o['iters'], B)
+    launches = 2 * o['iters'] + 3
+    out['kernel'] = dict(us=round(statistics.mean(us), 2), rounds_us=[round(x, 2) for x in us], launches=launches,
+                         compulsory_MB=round(nbytes / 1e6, 2), TBps_of_compulsory=round(nbytes / statistics.mean(us) / 1e6, 3),
+                         us_per_launch=round(statistics.mean(us) / launches, 2),
+                         how='device events around 50 back-to-back calls of the entry (%d launches each), launch gaps included'
+                             % launches)
+    out['motion_last_pair'] = [int(v) for v in e.out_stab_motion[B - 1].cpu()]
+    out['counts_last_pair'] = [int(v) for v in e.out_stab_counts[B - 1].cpu()]
+    assert not bool(e.stab_ws.any())
+    if rocprof:
+        out['kernel']['rocprofv3'] = stabilise_rocprof(seq)
+    del plain, stab
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -720,7 +816,25 @@ def main():
     ap.add_argument('--ground_truth', action='store_true',
                     help='the scoring estimator against the same one without ground_truth (with --track: both tracking), FlowNetC at '
                          'B = 4, both sequence modes, and evaluate_sequence against pair-mode evaluate (DESIGN 7.17)')
+    ap.add_argument('--stabilise', action='store_true',
+                    help='the stabilising estimator against the same run\'s plain estimator, FlowNetC at B = 4, both sequence modes, '
+                         'and unflow_sequence_stabilise alone (DESIGN 7.20)')
+    ap.add_argument('--stabilise-kernels-only', choices=('fw', 'bidir'), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.stabilise_kernels_only:
+        return stabilise_kernels_only(a.stabilise_kernels_only, a.iters)
+    if a.stabilise:
+        for seq in (True, 'bidirectional'):              # one line per mode
+            res = dict(metric='sequence_stabilise_ms_per_pair_over_the_same_runs_plain_estimator', shape=[H, W],
+                       frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup,
+                       expected='no time or ratio was predicted: nobody had measured this entry.  From the bytes: the flow read '
+                                'iters + 2 times, the frame once, four bytes written per pixel — %.1f MB per replay at the '
+                                'defaults, microseconds at HBM rate; the entry is 2 iters + 3 dependent launches, so its launch '
+                                'gaps weigh as much' % (stabilise_bytes(3) / 1e6),
+                       note='one run on one box; box to box +- 3 %',
+                       cases=[stabilise_case(seq, a.iters, a.warmup, a.rounds, rocprof=a.rocprof)])
+            print(json.dumps(res), flush=True)
+        return
     if a.ground_truth:
         res = dict(metric='sequence_ground_truth_ms_per_pair_over_the_same_estimator_without_it', shape=[H, W],
                    frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup, track=bool(a.track),

@@ -91,6 +91,16 @@ unflow_sequence_interpolate the graph runs
 
 (push_held_out, evaluate_interpolation).
 
+sequence=True | 'bidirectional' with stabilise=True | dict(tol, iters, follow): camera motion along a clip.  Behind the
+track kernels and in front of the interpolation either sequence graph runs
+
+    unflow_sequence_stabilise      the forward flow of the replay's pairs (bidirectional: and the forward occlusion mask) -> per pair
+                                   a robust affine fit (integer sums, one fp64 solve per iteration on the device), every pixel's
+                                   residual against it, the camera path composed along the clip, and the staged later frame
+                                   resampled along that path; the path stays on the device from one replay of the clip to the next
+
+(push_stabilised, stabilise_sequence, export_sequence(stabilise=True)); tol, iters and follow travel by value.
+
 The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
 _submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
 leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
@@ -250,7 +260,51 @@ def interpolate_order_option(interpolate_order, interpolate=1):
     return int(interpolate_order)
 
 
-def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False, mid=0):
+# What push_stabilised returns per pair (n, n + 1) (unflow_sequence_stabilise): frame uint8 [h, w, 3], frame n + 1
+# resampled along the camera path (uncovered pixels black); residual uint8 [h, w], how far every pixel's flow is from the pair's
+# dominant motion, in quarter pixels of L1 distance (255: that or more, or no usable flow); motion int64 [8] = {Tu, Lux, Luy, Tv,
+# Lvx, Lvy, status | successful iterations << 8, pixels used}, the affine fit, T in 2^-16 px, L in 2^-24 per pixel; path int64 [8],
+# the path after the pair in the same units (its linear part includes the identity); counts int64 [4] = {valid, valid but occluded,
+# moving, uncovered} pixels.  camera_matrix turns motion or path into a 2 x 3 matrix.
+Stabilised = collections.namedtuple('Stabilised', ('frame', 'residual', 'motion', 'path', 'counts'))
+STABILISE_DEFAULTS = dict(tol=2, iters=3, follow=0)
+STABILISE_RANGES = dict(tol=(0, 4), iters=(0, 4), follow=(0, 8))
+
+
+def stabilise_option(stabilise):
+    """FlowEstimator's stabilise option -> None (None or False: no camera motion) or dict(tol, iters, follow): True gives
+    STABILISE_DEFAULTS, a dict overrides some of them — tol in 0..4 (the weight of a pixel halves per 2^(1 - tol) px of residual),
+    iters in 0..4 (reweighted fits behind the first), follow in 0..8 (0: lock, every frame in the first frame's coordinates; s: the
+    path loses 2^-s of its offset per pair).  Anything else: ValueError."""
+    if stabilise is None or stabilise is False:
+        return None
+    if stabilise is True:
+        return dict(STABILISE_DEFAULTS)
+    if not isinstance(stabilise, dict) or set(stabilise) - set(STABILISE_DEFAULTS):
+        raise ValueError("FlowEstimator: stabilise is True or a dict with tol, iters, follow, got %r" % (stabilise,))
+    out = dict(STABILISE_DEFAULTS)
+    for key, v in stabilise.items():
+        lo, hi = STABILISE_RANGES[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("FlowEstimator: stabilise['%s'] is an int in %d..%d, got %r" % (key, lo, hi, v))
+        out[key] = int(v)
+    return out
+
+
+def camera_matrix(words, h, w, path=False):
+    """Six words of a Stabilised tuple as a float64 2 x 3 matrix A in pixel coordinates, (x', y') = A (x, y, 1).  motion (path
+    False): where the dominant motion takes a pixel of frame n in frame n + 1, p + T + L (p - c).  path (True): where a pixel of
+    the stabilised frame is in frame n + 1, c + Dt + Dl (p - c).  c = ((w - 1) / 2, (h - 1) / 2)."""
+    v = [int(x) for x in np.asarray(words).reshape(-1)[:6]]
+    lin = np.array([[v[1], v[2]], [v[4], v[5]]], dtype=np.float64) / float(1 << 24)
+    if not path:
+        lin = lin + np.eye(2)
+    c = np.array([(int(w) - 1) / 2.0, (int(h) - 1) / 2.0])
+    t = c + np.array([v[0], v[3]], dtype=np.float64) / 65536.0 - lin @ c
+    return np.concatenate([lin, t[:, None]], axis=1)
+
+
+def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False, mid=0, stab=False):
     """The files export / export_sequence write for pair n, in the order they are written — _10, _01, _10_occ, then the pictures
     (visual_files' or sequence_visual_files' list) in their file order: [(file name, source)].  A source is
 
@@ -260,7 +314,8 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False
         ('track', attribute)  track: the dense tracks of row i on their grid, %06d_track.flo (FlowEstimator._track_flo), last.
 
     mid: the in-between frames j = 1..mid of the pair, %06d_mid%d.png (pair, j), PNGs of image (j - 1) * B + i of the surface
-    'mid', behind the pictures.
+    'mid', behind the pictures.  stab: the stabilised frame and the residual map of the pair, %06d_stab.png (8-bit RGB, surface
+    'stab') and %06d_motion.png (8-bit grey, surface 'stab_resid'), behind everything else.
 
     Both back ends of FlowEstimator._write_files and the entries of the replay's unflow_png_filter launch (filter_entries) come
     from this one list, so the span order and the file order cannot drift apart."""
@@ -270,7 +325,8 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False
         out.append(('%06d_10_occ.png' % n, ('png', 'occ', 0)))
     return out + [(name, ('png', 'vis', k)) for k, name in pictures] + \
         [('%06d_mid%d.png' % (n, j), ('png', 'mid', j - 1)) for j in range(1, int(mid) + 1)] + \
-        ([('%06d_track.flo' % n, ('track', 'track_disp'))] if track else [])
+        ([('%06d_track.flo' % n, ('track', 'track_disp'))] if track else []) + \
+        ([('%06d_stab.png' % n, ('png', 'stab', 0)), ('%06d_motion.png' % n, ('png', 'stab_resid', 0))] if stab else [])
 
 
 def filter_entries(files, rows, batch):
@@ -381,13 +437,14 @@ def chunks(it, n):
         yield buf
 
 
-def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=False):
+def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=False, stabilise=False):
     """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
     and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
     estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator; n_mid: the
     in-between frames per pair of an interpolating one.  ground_truth: also the rows of unflow_sequence_track_score,
     behind the others; their flag, track_gt, needs track and ground_truth both.  held_out: also the rows of
-    unflow_sequence_interpolate_score, behind everything else."""
+    unflow_sequence_interpolate_score, behind everything else.  stabilise: also the five rows of
+    unflow_sequence_stabilise, behind those."""
     scored = ()
     if ground_truth:
         scored = (('track_scores', 'out_track_scores', (B, 16), torch.int32, 'track_gt'),
@@ -397,6 +454,12 @@ def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=Fals
     if held_out:
         scored += (('mid_sse', 'out_mid_sse', (n_mid, B, 3), torch.int64, 'held_out'),
                    ('mid_ssim', 'out_mid_ssim', (n_mid, B, 3), torch.float64, 'held_out'))
+    if stabilise:
+        scored += (('stab', 'out_stab', (B, Hm, Wm, 3), torch.uint8, 'stabilise'),
+                   ('stab_resid', 'out_stab_resid', (B, Hm, Wm), torch.uint8, 'stabilise'),
+                   ('stab_motion', 'out_stab_motion', (B, 8), torch.int64, 'stabilise'),
+                   ('stab_path', 'out_stab_path', (B, 8), torch.int64, 'stabilise'),
+                   ('stab_counts', 'out_stab_counts', (B, 4), torch.int32, 'stabilise'))
     return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
             ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
             ('sums', 'sums', (B, 2, 2), torch.float64, None),
@@ -425,7 +488,8 @@ class _Slot:
         self.gt_flow = self.gt_mask = None
         # held_out: the truth frames of a replay's pairs, [n_mid][B][Hmax][Wmax][3], fp32-sized like the frames
         self.truth = pin(est.interpolate * B * Hm * Wm * 3 * 4, dtype=torch.uint8) if est.held_out else None
-        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate, True, held_out=True):
+        for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate, True, held_out=True,
+                                                          stabilise=True):
             setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
         self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
@@ -468,6 +532,8 @@ class _Encoder:
             named += [('vis', est.vis, len(VISUAL_IMAGES) * B, 3, _lib.PNG_U8)]
         if est.interpolate:
             named += [('mid', est.out_mid, est.interpolate * B, 3, _lib.PNG_U8)]
+        if est.stabilise:
+            named += [('stab', est.out_stab, B, 3, _lib.PNG_U8), ('stab_resid', est.out_stab_resid, B, 1, _lib.PNG_U8)]
         self.index = {name: k for k, (name, *_) in enumerate(named)}
         self.surfaces = [PngSurface(t, images, Hm, Wm, ch, kind) for _, t, images, ch, kind in named]
         n_files = sum(s.images for s in self.surfaces)
@@ -517,11 +583,17 @@ class FlowEstimator:
     held_out (with interpolate): the in-between frames are scored against the frames that were left out of the clip, given with
     the frames — push_held_out returns a HeldOut(frames, holes, sse, psnr, ssim) per pair, for the interpolated frame, the temporal
     blend and the nearest frame; evaluate_interpolation subsamples full-rate clips and pools the scores; every other method
-    returns what it returns without held_out."""
+    returns what it returns without held_out.
+    stabilise (with sequence): True or dict(tol=2, iters=3, follow=0) — the camera motion of the clip: per pair a
+    robust affine fit to the forward flow (tol in 0..4: a pixel's weight halves per 2^(1 - tol) px of residual; iters in 0..4
+    reweighted fits behind the first), the pixels that do not follow it, and the later frame resampled along the composed camera
+    path (follow = 0: locked on the clip's first frame; s in 1..8: the path loses 2^-s of its offset per pair).  push_stabilised /
+    stabilise_sequence return a Stabilised(frame, residual, motion, path, counts) per pair, export_sequence(stabilise=True) writes
+    them; every other method returns what it returns without stabilise.  reset() starts a new path."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
                  visual=False, sequence=False, track=False, interpolate=None, ground_truth=False, held_out=False,
-                 interpolate_order=None):
+                 interpolate_order=None, stabilise=None):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -549,6 +621,10 @@ class FlowEstimator:
         if self.held_out and not self.interpolate:
             raise ValueError("FlowEstimator: held_out scores the in-between frames against the frames left out of the clip; it "
                              "needs interpolate=n (and sequence=True or sequence='bidirectional')")
+        self.stabilise = stabilise_option(stabilise)             # camera motion along the clip; None: none
+        if self.stabilise and not sequence:
+            raise ValueError("FlowEstimator: stabilise fits the camera motion along a clip; it needs sequence=True or "
+                             "sequence='bidirectional'")
         self.ground_truth = bool(ground_truth)                   # sequence: the clip's pairs are scored
         if self.ground_truth and not sequence:
             raise ValueError("FlowEstimator: ground_truth scores the pairs of a clip; it needs sequence=True or "
@@ -587,7 +663,7 @@ class FlowEstimator:
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
             for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate, True,
-                                                              held_out=True):     # out_flow, out_u16, ...
+                                                              held_out=True, stabilise=True):     # out_flow, out_u16, ...
                 setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
             self.track_anchors = self.track_disp = self.track_alive = None
             if self.track:
@@ -617,6 +693,13 @@ class FlowEstimator:
                 self.mid_score_prev = z(Hm * Wm * 3 * 4, dtype=torch.uint8)
                 self.mid_score_ws = z(int(L.unflow_sequence_interpolate_score_workspace_bytes(self.interpolate, B, Hm, Wm)) // 8,
                                       dtype=torch.int64)
+            self.stab_path = self.stab_identity = self.stab_ws = None
+            if self.stabilise:
+                # unflow_sequence_stabilise: the camera path, kept from one replay of a clip to the next (never read while the
+                # carry source is 0: reset() needs no memset), and its workspace, zero now and left zero by every launch
+                self.stab_path = z(8, dtype=torch.int64)
+                self.stab_identity = torch.tensor([0, 1 << 24, 0, 0, 0, 1 << 24, 0, 0], dtype=torch.int64, device=self.dev)
+                self.stab_ws = z(int(L.unflow_sequence_stabilise_workspace_bytes(B)) // 8, dtype=torch.int64)
             self.vis_shown = self.vis_max = None
             if self.visual:
                 # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
@@ -709,6 +792,13 @@ class FlowEstimator:
                                                 ptr(self.out_gt_track_disp), ptr(self.out_gt_track_alive),
                                                 ptr(self.out_track_scores), ptr(self.out_track_err), ptr(self.track_score_ws),
                                                 e.stream()), "sequence_track_score")
+        if self.stabilise:
+            o = self.stabilise
+            check(L.unflow_sequence_stabilise(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, ptr(self.out_flow),
+                                              ptr(self.occ[0]) if self.seq_bidir else None, o['tol'], o['iters'], o['follow'],
+                                              ptr(self.stab_path), ptr(self.stab_ws), ptr(self.out_stab_motion),
+                                              ptr(self.out_stab_path), ptr(self.out_stab_resid), ptr(self.out_stab),
+                                              ptr(self.out_stab_counts), e.stream()), "sequence_stabilise")
         if self.interpolate:
             bw, ofw, obw = (self.out_flow_bw, self.occ[0], self.occ[1]) if self.seq_bidir else (None, None, None)
             args = (ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, self.interpolate, ptr(self.out_flow), ptr(bw), ptr(ofw),
@@ -917,7 +1007,8 @@ class FlowEstimator:
         truth was staged, the occlusion counts only when it had two maps."""
         special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
         nv = self._num_pictures(nmaps)
-        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate, True, held_out=True):
+        for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate, True, held_out=True,
+                                                 stabilise=True):
             if special.get(name, name in want):
                 dst, src = getattr(slot, name), getattr(self, attr)
                 if name == 'vis':
@@ -960,7 +1051,7 @@ class FlowEstimator:
 
     # ------------------------------------------------------------------------------------------ public API
     def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False, ground_truth=False,
-              held_out=False):
+              held_out=False, stabilise=False):
         """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
         one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
         if not sequence:
@@ -992,6 +1083,10 @@ class FlowEstimator:
         if held_out and not self.held_out:
             raise RuntimeError("%s: a sequence estimator without held-out frames; build it with FlowEstimator(..., sequence=%r, "
                                "interpolate=n, held_out=True)" % (what, 'bidirectional' if self.seq_bidir else True))
+        if stabilise and not self.stabilise:
+            raise RuntimeError("%s: a sequence estimator without camera motion; build it with FlowEstimator(..., sequence=%r, "
+                               "stabilise=True) (or stabilise=dict(tol=2, iters=3, follow=0))"
+                               % (what, 'bidirectional' if self.seq_bidir else True))
 
     def _visual_spelling(self):
         """How to build this sequence estimator with pictures, for the messages that ask for it."""
@@ -1279,6 +1374,10 @@ class FlowEstimator:
                             write_png_rgb8(path, slot.vis.numpy()[k[0], i, :h, :w])
                         elif attr == 'mid':
                             write_png_rgb8(path, slot.mid.numpy()[k[0], i, :h, :w])
+                        elif attr == 'stab':
+                            write_png_rgb8(path, slot.stab.numpy()[i, :h, :w])
+                        elif attr == 'stab_resid':
+                            write_png_gray8(path, slot.stab_resid.numpy()[i, :h, :w])
                         else:
                             write_kitti_flow_png(path, getattr(slot, attr).numpy()[i, :h, :w].view(np.uint16))
                         paths.append(path)
@@ -1489,6 +1588,7 @@ class FlowEstimator:
         for i, a in enumerate(frames):
             if not isinstance(a, torch.Tensor):
                 fr[i, :h, :w] = a
+        starts = self._carry == 0                 # the clip's first replay
         tab, valid, self._carry = sequence_tables((h, w), len(frames), B, self._carry, u8, max_flow, self._track_words(h, w),
                                                   nmaps=nmaps, held=int(truths is not None))
         slot.tab.numpy()[:] = tab
@@ -1504,6 +1604,11 @@ class FlowEstimator:
                 dv = self.frames[:nbytes].view(torch.uint8 if u8 else torch.float32).view(B, Hm, Wm, 3)
                 for i, a in on_dev:
                     dv[i, :h, :w].copy_(a, non_blocking=True)
+            if self.stabilise and starts and not valid:
+                # a clip that starts with one frame: its replay has no pair and unflow_sequence_stabilise leaves the path alone,
+                # the next one carries and continues from it — from the identity, not from the last clip's path (a device copy
+                # in front of the replay, outside the graph)
+                self.stab_path.copy_(self.stab_identity, non_blocking=True)
             return self._replay(slot, [(i, h, w) for i in valid], nmaps, want, files)
 
     def _push(self, frames, want, max_flow=None):
@@ -1623,6 +1728,35 @@ class FlowEstimator:
         out = []
         for slot, rows, _ in self._pipeline_sequence(frames, ('mid', 'mid_holes')):
             out += self._interpolated_of(slot, rows)
+        return out
+
+    # camera motion
+    STAB_WANT = ('stab', 'stab_resid', 'stab_motion', 'stab_path', 'stab_counts')
+
+    @staticmethod
+    def _stabilised_of(slot, rows):
+        """The rows of a finished stabilising replay as Stabilised tuples (copies)."""
+        s, r, m, p, c = (getattr(slot, name).numpy() for name in FlowEstimator.STAB_WANT)
+        return [Stabilised(s[i, :h, :w].copy(), r[i, :h, :w].copy(), m[i].copy(), p[i].copy(), c[i].astype(np.int64))
+                for i, h, w in rows]
+
+    def push_stabilised(self, frames):
+        """push's frames on an estimator built with stabilise: one Stabilised(frame, residual, motion, path, counts) per new pair
+        (the count is push's).  For the pair (n, n + 1): motion, the robust affine fit to the forward flow (on a
+        sequence='bidirectional' estimator the pixels under the forward occlusion mask are left out); residual, every pixel's
+        distance from it in quarter pixels — the independently moving objects stand out; path, the camera path up to frame n + 1,
+        the motions composed from the clip's first frame (with follow = s it drifts back to the identity by 2^-s per pair); frame,
+        frame n + 1 resampled along that path — with follow = 0 in the first frame's coordinates — black where the path leaves
+        the frame (counts[3] pixels).  Bit-reproducible from run to run.  reset() starts a new path."""
+        self._mode('push_stabilised', sequence=True, stabilise=True)
+        return self._stabilised_of(*self._push(frames, self.STAB_WANT))
+
+    def stabilise_sequence(self, frames):
+        """Camera motion along a clip: T >= 2 frames -> T - 1 Stabilised tuples (push_stabilised's)."""
+        self._mode('stabilise_sequence', sequence=True, stabilise=True)
+        out = []
+        for slot, rows, _ in self._pipeline_sequence(frames, self.STAB_WANT):
+            out += self._stabilised_of(slot, rows)
         return out
 
     # held-out scores of the in-between frames (DESIGN 7.18)
@@ -1820,7 +1954,7 @@ class FlowEstimator:
         return out
 
     def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False,
-                        visual=False, max_flow=None, tracks=False, interpolate=False):
+                        visual=False, max_flow=None, tracks=False, interpolate=False, stabilise=False):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
         writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
@@ -1837,7 +1971,11 @@ class FlowEstimator:
         .flo unknown-flow value, read back as mask = 0 — through the same writer as the other .flo files.  Sparse anchors: one
         tracks.npz behind the last pair's files, with anchors [N, 2] int32, disp [T - 1, N, 2] float32, alive [T - 1, N] bool.
         interpolate (an estimator built with interpolate=n): the in-between frames of push_interpolated, %06d_mid%d.png (pair, j =
-        1..n), 8-bit RGB, behind a pair's pictures — through either writer, the same pixels."""
+        1..n), 8-bit RGB, behind a pair's pictures — through either writer, the same pixels.
+        stabilise (an estimator built with stabilise): behind a pair's other files %06d_stab.png, the stabilised frame of
+        push_stabilised (8-bit RGB), and %06d_motion.png, its residual map (8-bit grey, quarter pixels) — through any writer, the
+        same pixels; behind the last pair's files one camera.npz with motion [T - 1, 8], path [T - 1, 8], counts [T - 1, 4] and
+        matrix [T - 1, 2, 3], camera_matrix of every pair's motion."""
         from .png_device import check_deflate_mode
         self._mode('export_sequence', sequence=True)
         if tracks and not self.track:
@@ -1853,25 +1991,38 @@ class FlowEstimator:
         if interpolate and not self.interpolate:
             raise ValueError("export_sequence: the in-between frames need FlowEstimator(..., sequence=%r, interpolate=n)"
                              % ('bidirectional' if self.seq_bidir else True))
+        if stabilise and not self.stabilise:
+            raise ValueError("export_sequence: the stabilised frames need FlowEstimator(..., sequence=%r, stabilise=True)"
+                             % ('bidirectional' if self.seq_bidir else True))
         if max_flow is not None and not visual:
             raise ValueError("export_sequence: max_flow scales the flow colours of the pictures; it needs visual=True")
 
         def plan(n, nmaps):
             return pair_files(n, fmt, backward, occlusion, sequence_visual_files(n, self.seq_bidir) if visual else (),
-                              track=dense, mid=self.interpolate if interpolate else 0)
+                              track=dense, mid=self.interpolate if interpolate else 0, stab=bool(stabilise))
         dense = bool(tracks) and self.track_spec[0] == 'dense'
         sparse = [] if tracks and not dense else None      # sparse anchors: the Track of every pair, for tracks.npz
+        camera = [] if stabilise else None                 # (motion, path, counts, matrix) of every pair, for camera.npz
 
         def replays(want, files):
             if sparse is not None:
                 want += ('track_disp', 'track_alive')
+            if camera is not None:
+                want += tuple(n for n in self.STAB_WANT[2:] if n not in want)
             for slot, rows, nmaps in self._pipeline_sequence(frames, want, files, max_flow):
                 if sparse is not None:
                     sparse.extend(self._tracks_of(slot, rows))
+                if camera is not None:
+                    camera.extend((slot.stab_motion.numpy()[i].copy(), slot.stab_path.numpy()[i].copy(),
+                                   slot.stab_counts.numpy()[i].astype(np.int64), camera_matrix(slot.stab_motion.numpy()[i], h, w))
+                                  for i, h, w in rows)
                 yield slot, rows, nmaps
         paths = self._write_files(replays, plan, out_dir, workers, level, on_device)
         if sparse is not None:
             paths.append(os.path.join(out_dir, 'tracks.npz'))
             np.savez(paths[-1], anchors=self.track_spec[1], disp=np.stack([t.disp for t in sparse]),
                      alive=np.stack([t.alive for t in sparse]))
+        if camera is not None:
+            paths.append(os.path.join(out_dir, 'camera.npz'))
+            np.savez(paths[-1], **{k: np.stack([c[j] for c in camera]) for j, k in enumerate(('motion', 'path', 'counts', 'matrix'))})
         return paths

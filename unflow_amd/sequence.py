@@ -4,6 +4,7 @@ once (core/inference.FlowEstimator(..., sequence=True)).
     python -m unflow_amd.sequence --ex NAME --frames DIR [--out DIR] [--flo] [--batch B] [--net_size H W] [--host_decode]
                                   [--output_backward] [--occlusion] [--visual] [--max_flow F]
                                   [--track] [--track_stride S] [--track_points FILE] [--interpolate N [--order K] [--held_out]]
+                                  [--stabilise [--stabilise_tol K] [--stabilise_iters R] [--stabilise_follow S]]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -25,7 +26,12 @@ one direction a hole takes the later frame's colour; the files are the same.  --
 2 (N + 1), ... go to the network, the N frames between two of them are held out, and trailing frames that complete no pair are
 dropped (their number is printed).  It prints PSNR and SSIM of the interpolated frames, of the temporal blend and of the nearest
 frame against the held-out frames, over the clip and per position j, and the share of hole pixels; the files are then those of the
-subsampled clip, pairs numbered along it."""
+subsampled clip, pairs numbered along it.
+--stabilise fits the camera motion of every pair and adds %06d_stab.png, frame n + 1 resampled along the camera path
+(black where the path leaves the frame), %06d_motion.png, every pixel's distance from the pair's dominant motion in quarter pixels
+(the independently moving objects), and one camera.npz (motion, path, counts, matrix per pair).  --stabilise_tol K (0..4, default
+2): the weight of a pixel halves per 2^(1 - K) px of residual; --stabilise_iters R (0..4, default 3): reweighted fits behind the
+first; --stabilise_follow S (0..8, default 0 = lock on the first frame): the path loses 2^-S of its offset per pair."""
 import argparse
 import os
 import sys
@@ -157,6 +163,15 @@ def parser():
     ap.add_argument('--held_out', action='store_true',
                     help='with --interpolate N: DIR is the full-rate clip; every (N + 1)-th frame goes to the network and the '
                          'in-between frames are scored against the frames left out (PSNR, SSIM; also blend and nearest frame)')
+    ap.add_argument('--stabilise', action='store_true',
+                    help='also the camera motion of every pair: %%06d_stab.png (frame n + 1 along the camera path), %%06d_motion.png '
+                         '(the residual against the dominant motion, quarter pixels) and camera.npz')
+    ap.add_argument('--stabilise_tol', type=int, default=None, metavar='K',
+                    help='with --stabilise: the weight of a pixel halves per 2^(1 - K) px of residual (0..4, default 2)')
+    ap.add_argument('--stabilise_iters', type=int, default=None, metavar='R',
+                    help='with --stabilise: reweighted fits behind the first (0..4, default 3)')
+    ap.add_argument('--stabilise_follow', type=int, default=None, metavar='S',
+                    help='with --stabilise: the path loses 2^-S of its offset per pair (1..8); 0, the default, locks on the first frame')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -184,6 +199,16 @@ def parse_args(argv=None):
         ap.error("--order orders the splat of the in-between frames: it needs --interpolate N")
     if a.held_out and a.interpolate is None:
         ap.error("--held_out scores the in-between frames: it needs --interpolate N")
+    a.stabilise_option = None                     # FlowEstimator's stabilise
+    given = {k: getattr(a, 'stabilise_' + k) for k in ('tol', 'iters', 'follow') if getattr(a, 'stabilise_' + k) is not None}
+    if given and not a.stabilise:
+        ap.error("--stabilise_%s sets the camera-motion fit: it needs --stabilise" % sorted(given)[0])
+    if a.stabilise:
+        from .core.inference import STABILISE_RANGES
+        for k, v in given.items():
+            if not STABILISE_RANGES[k][0] <= v <= STABILISE_RANGES[k][1]:
+                ap.error("--stabilise_%s is an integer in %d..%d" % ((k,) + STABILISE_RANGES[k]))
+        a.stabilise_option = given or True
     if a.track_stride is not None and a.track_stride < 1:
         ap.error("--track_stride must be at least 1")
     if a.track_points is not None and (a.track or a.track_stride is not None):
@@ -249,7 +274,8 @@ def main(argv=None):
     est = FlowEstimator.from_checkpoint(ckpt_dir, params, a.batch, net_size=tuple(a.net_size), max_frame=a.frame_size,
                                         sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
                                         visual='sequence' if a.visual else False, track=a.track_option,
-                                        interpolate=a.interpolate, held_out=a.held_out, interpolate_order=a.order)
+                                        interpolate=a.interpolate, held_out=a.held_out, interpolate_order=a.order,
+                                        stabilise=a.stabilise_option)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
@@ -266,7 +292,7 @@ def main(argv=None):
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
                                     deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion, visual=a.visual,
                                     max_flow=a.max_flow, tracks=a.track_option is not False,
-                                    interpolate=a.interpolate is not None)
+                                    interpolate=a.interpolate is not None, stabilise=a.stabilise)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))
