@@ -6,16 +6,19 @@
  * CPU restatement, in plain C, of the arithmetic of the reference's custom ops.
  * The reference registers GPU kernels only (REGISTER_KERNEL_BUILDER(...DEVICE_GPU)
  * in ops/correlation_op.cc:189-194, backward_warp_op.cc:93-98,
- * forward_warp_op.cc:102-107, downsample_op.cc:83-87) and needs nvcc plus the
- * TensorFlow headers, neither of which exists here, so it cannot be compiled;
- * this file states the same math per output element, keeping the reference's
- * fp32 operation ORDER wherever the order changes the rounding.  Every function
- * cites the lines whose behaviour it restates.
+ * forward_warp_op.cc:102-107, downsample_op.cc:83-87), so there is nothing of
+ * it to run on a CPU; this file states the same math per output element,
+ * keeping the reference's fp32 operation ORDER wherever the order changes the
+ * rounding.  Every function cites the lines whose behaviour it restates.
  *
  * Pinned by the reference's own known-answer tests (tests/golden/ref_kats.json,
  * from src/e2eflow/test/ops/{correlation,backward_warp,downsample}.py and
- * src/e2eflow/test/test_image_warp.py).  forward_warp VALUES are unpinned by
- * the reference (its test is a Jacobian check only).
+ * src/e2eflow/test/test_image_warp.py) and, element by element, by the
+ * reference's own GPU kernels compiled for gfx950 (oracle/_ref/libref_ops.so,
+ * oracle/Makefile; tests/test_reference_kernels_gpu.py): correlation forward
+ * and both gradients over six attribute sets, the warps, the splat and
+ * downsample.  image_warp is Python in the reference and stays pinned by its
+ * known-answer vectors alone.
  *
  * Build: oracle/Makefile  (gcc -O2 -fopenmp -shared -> oracle/_build/liboracle.so)
  */

@@ -3,7 +3,7 @@
 own unit tests hold for the hot path.
 
 The reference cannot be imported here (every module imports TensorFlow, which is
-not installed and cannot be; the ops additionally need nvcc), so these vectors
+not installed and cannot be, and loads the ops through it), so these vectors
 are TRANSCRIBED from the reference's test files — inputs and expected outputs
 exactly as written there — and each entry cites its source lines.  Derived
 entries (marked "derived") follow from a closed form stated in the entry.
