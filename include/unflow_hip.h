@@ -973,6 +973,57 @@ int unflow_sequence_stabilise(const void* frames, const int* tab, int B, int Hma
                               long long* out_motion, long long* out_path, unsigned char* out_resid, unsigned char* out_stab,
                               int* out_counts, unflow_stream_t stream);
 
+/* Temporal denoising along a clip (csrc/denoise.hip): per valid pair slot i of a bidirectional sequence replay, of size
+ * (h, w), the pair's LATER frame averaged with its own history fetched along the backward flow — a recursive, motion-compensated
+ * filter.  This definition is part of the ABI; tests/denoise_ref.py mirrors it step by step and the kernels are held to equality.
+ * Setting.  frames, tab, B, Hmax, Wmax: unflow_sequence_stabilise's, and so is the pair rule: a pair slot with h <= 0, w <= 0, h >
+ *   Hmax or w > Wmax — and slot 0 while the carry source is 0 — is not a pair.  For pair slot i: im1 = staged frame i (frame-table
+ *   slot i of `frames`, uint8 or fp32 per word 5 of the pair row), bw = flow_bw[i] ([B][Hmax][Wmax][2], the backward flow on the
+ *   later frame's grid), occ = occ_bw[i] ([B][Hmax][Wmax] uint8, unflow_inference_occlusion's backward mask).  All three are
+ *   required: the entry has no one-direction form (the history would have to be splatted forward).
+ * State.  state [Hmax][Wmax][4] uint16: per pixel the history colour A in 8.8 fixed point (three words, 0..65280) and the history
+ *   count n (one word, 1..depth), kept by the caller from one replay of a clip to the next; it needs no initialisation.  With
+ *   carry source 0 the clip starts here: before any pair is processed the history is A = q(frame-table slot 0), n = 1 on that
+ *   slot's (h, w) (a slot 0 with h <= 0, w <= 0, h > Hmax or w > Wmax initialises nothing), whatever state holds —
+ *   unflow_sequence_track's rule, so an estimator's first replay ever, which runs the entry twice (the eager pass, then the
+ *   graph's first replay), gives what one run gives.  q is csrc/mid_common.h's quantisation, (long)rintf(min(max(c, 0), 255) *
+ *   256).  A slot changes the history on its (h, w) alone.  After the launch state is the history behind the last valid slot; with
+ *   carry source 0 and no pair it is the initial history of slot 0; with a carried frame and no pair it is unchanged.
+ * Per valid slot in order, per pixel (x, y) of im1 — integers but for the flow test and one rintf per component; / is integer
+ * division of non-negative integers, >> a shift of a non-negative integer:
+ *   cur = q(im1(x, y)) per channel.  (u, v) = bw(x, y).  VALID: both components finite and of magnitude < 4096, tested before any
+ *     conversion.  PX = (x << 6) + (int)rintf(u * 64), PY likewise.  INSIDE: 0 <= PX <= (w - 1) << 6 and the same in y.
+ *   FRESH: not VALID, or not INSIDE, or occ(x, y) != 0.  Otherwise: ix = PX >> 6, qx = PX & 63, the neighbour min(ix + 1, w - 1),
+ *     the same in y; pred = (sum over the four taps of wx wy A_prev + 2048) >> 12 per channel, wx = 64 - qx | qx, wy likewise;
+ *     np = the minimum of the four taps' n_prev, clamped and zero-weight taps included; e = |pred.r - cur.r| + |pred.g - cur.g| +
+ *     |pred.b - cur.b|; E = min(e >> 8, 255).
+ *   Noise level.  hist: the 256-bin histogram of E over the slot's pixels that are not FRESH, eligible their number.  M = the
+ *     smallest m with hist[0] + .. + hist[m] >= (eligible + 1) / 2; M = 0 when eligible = 0.
+ *   Tolerance.  t = tol for tol in 0..4; tol = -1 (automatic): the smallest t in 0..4 with (8 << t) >= 2 M, else 4.
+ *   Update.  d = min(e >> (11 + t), 6).  neff = 0 for a FRESH pixel and for d == 6 (REJECTED), else np >> d.  A' = (neff pred +
+ *     cur + ((neff + 1) >> 1)) / (neff + 1) per channel, n' = min(neff + 1, depth), out_den[i](x, y) = (A' + 128) >> 8 per channel.
+ *   A_prev and n_prev are the history BEFORE this slot: the taps are read at displaced positions, so the update is not in place.
+ *   The entry keeps two history slabs in its workspace that take turns — slot i reads slab i & 1 and writes the other, pixels
+ *   outside (h, w) and slots that are no pairs are copied across — filled from state by a launch in front and copied back to state
+ *   by one behind (unflow_sequence_interpolate's prev is kept the same way).
+ * Outputs: out_den [B][Hmax][Wmax][3] uint8; out_stats [B][8] int32 = {t, M, eligible, FRESH, REJECTED, the sum of n', 0, 0}.
+ * Nothing is written for a slot that is no pair, nor outside (h, w).
+ * workspace: unflow_sequence_denoise_workspace_bytes(B, Hmax, Wmax) bytes (0 for arguments the entry refuses), 8-byte aligned:
+ *   first B * 256 int32, the histograms — zero on entry of the first launch and left zero by every launch, no memset node in a
+ *   captured graph — then the two slabs, [2][Hmax][Wmax] 8-byte words, which need not be zero.  state and flow_bw are 8-byte
+ *   aligned too (UNFLOW_ERR_UNSUPPORTED otherwise).
+ * Ranges.  |rintf(u * 64)| <= 2^18 and x < 2^12: PX fits an int.  A, pred <= 65280 and neff <= 64 on a state this entry wrote; on
+ *   any state the words are below 2^16, a tap sum is below 2^12 2^16 and neff pred + cur + 2^15 below 2^32: unsigned 32-bit
+ *   arithmetic is exact.  The sum of n' is at most 64 * 2^24.
+ * Integer LDS and global atomics for the histogram and the three counts; no float atomics, no float reductions: two launches and
+ * two graph replays give the same bytes.  2 B + 2 launches.
+ * UNFLOW_ERR_NULL for any NULL pointer; UNFLOW_ERR_SHAPE for B < 1 or above 65535, Hmax or Wmax outside 1..4096, tol outside
+ * -1..4, depth outside 1..64.  A refused call launches and writes nothing. */
+size_t unflow_sequence_denoise_workspace_bytes(int B, int Hmax, int Wmax);
+int unflow_sequence_denoise(const void* frames, const int* tab, int B, int Hmax, int Wmax, const float* flow_bw,
+                            const unsigned char* occ_bw, int tol, int depth, void* state, void* workspace,
+                            unsigned char* out_den, int* out_stats, unflow_stream_t stream);
+
 /* ===================================================================== */
 /* PNG decode on the device (csrc/png_decode.hip, core/png_device.py)      */
 /* ===================================================================== */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sequence inference against pair mode at the KITTI evaluation shape; one JSON line.
 
-    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --stabilise | --interpolate N [--order K | --held_out] |
+    python tools/sequence_bench.py [--iters 20] [--warmup 5] [--rocprof] [--bidirectional | --visual | --track | --stabilise | --denoise | --interpolate N [--order K | --held_out] |
                                     --ground_truth [--track]]
 
 For FlowNetC and CSS at 384 x 1280 and B in {1, 4, 8} (bf16x3, 375 x 1242 uint8 frames), in ONE process on one GPU: ms per pair
@@ -52,7 +52,12 @@ profiles/sequence_gt_bench_line.json.
 --stabilise: FlowNetC at B = 4, both sequence modes: ms per pair of the replayed graph of the stabilising estimator
 (the defaults: tol 2, iters 3, follow 0) against the SAME RUN's plain estimator, the two taking turns; and
 unflow_sequence_stabilise alone (device events around 50 calls, nine launches each) with the bytes it must move.  One line per mode
-in profiles/sequence_stabilise_bench_line.json."""
+in profiles/sequence_stabilise_bench_line.json.
+
+--denoise: FlowNetC at B = 4, sequence='bidirectional': ms per pair of the replayed graph of the denoising estimator
+(the defaults: tol 'auto', depth 8) against the SAME RUN's plain bidirectional estimator, the two taking turns; and
+unflow_sequence_denoise alone (device events around 50 calls, 2 B + 2 launches each) with the bytes it must move and the HBM
+bandwidth they imply.  One line in profiles/sequence_denoise_bench_line.json."""
 import argparse
 import csv
 import glob
@@ -78,7 +83,7 @@ def _frames(n):
 
 
 def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False, head_scale=None, interpolate=None,
-               ground_truth=False, held_out=False, interpolate_order=None, stabilise=None):
+               ground_truth=False, held_out=False, interpolate_order=None, stabilise=None, denoise=None):
     """sequence: False, True or 'bidirectional'; bidirectional: the pair-mode estimator of both directions; visual: with the
     pictures at the end of the graph; track: FlowEstimator's; head_scale: the flow heads' weights times this."""
     import torch
@@ -102,6 +107,8 @@ def _estimator(spec, B, sequence, bidirectional=False, visual=False, track=False
         kw['held_out'] = True
     if stabilise:
         kw['stabilise'] = stabilise
+    if denoise:
+        kw['denoise'] = denoise
     est = FlowEstimator(dict(flownet=spec), B, net_size=(H, W), device=dev, sequence=sequence, bidirectional=bidirectional, **kw)
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated(dev) - m0
@@ -788,6 +795,104 @@ def stabilise_case(seq, iters, warmup, rounds, B=4, rocprof=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- --denoise
+def denoise_bytes(B=4):
+    """Compulsory bytes of unflow_sequence_denoise per replay on uint8 FRAMEs in (H, W) buffers: per slot and frame pixel the two
+    passes each read the flow (8), the mask (1), the frame (3) and the history (8, every word once: neighbouring pixels share
+    their taps), the second writes the new history (8) and the denoised pixel (3), and copies the history of the buffer's pixels
+    outside the frame (8 + 8); the launches in front and behind copy the history of the whole buffer (16 each)."""
+    px, plane = FRAME[0] * FRAME[1], H * W
+    return B * (px * (20 + 20 + 8 + 3) + (plane - px) * 16) + plane * 32
+
+
+def _denoise_call(e):
+    from unflow_amd import _lib
+    from unflow_amd._lib import check, ptr
+    L, o = _lib.lib(), e.denoise
+
+    def call():
+        check(L.unflow_sequence_denoise(ptr(e.frames), ptr(e.tab), e.B, e.Hmax, e.Wmax, ptr(e.out_flow_bw), ptr(e.occ[1]),
+                                        -1 if o['tol'] == 'auto' else o['tol'], o['depth'], ptr(e.den_state), ptr(e.den_ws),
+                                        ptr(e.out_den), ptr(e.out_den_stats), e.engine.stream()), "sequence_denoise")
+    return call
+
+
+def _noisy_frames(n):
+    """A static smooth picture with noise of its own per frame (sigma 8): the filter has something to average."""
+    import numpy as np
+    rs = np.random.RandomState(0)
+    yy, xx = np.meshgrid(np.arange(FRAME[0]), np.arange(FRAME[1]), indexing='ij')
+    base = np.stack([128 + 80 * np.sin(xx / (40.0 + 9 * c)) * np.cos(yy / (30.0 + 7 * c)) for c in range(3)], axis=-1)
+    return [np.clip(np.rint(base + rs.randn(*base.shape) * 8.0), 0, 255).astype(np.uint8) for _ in range(n)]
+
+
+def denoise_kernels_only(iters, B=4):
+    """Child: unflow_sequence_denoise alone on a set-up FlowNetC estimator, `iters` times (carry source B, every pair valid)."""
+    import torch
+    e, _ = _estimator('C', B, 'bidirectional', denoise=True, head_scale=0.1)
+    e.denoise_sequence(_noisy_frames(3 * B))
+    call = _denoise_call(e)
+    torch.cuda.synchronize()
+    for _ in range(iters):
+        call()
+    torch.cuda.synchronize()
+
+
+def denoise_rocprof(B=4, iters=50):
+    """Per-kernel times of the entry from a counters-free kernel-trace child: {kernel: calls, mean us}, and the sum of one entry's
+    2 B + 2 launches (the estimator's own few replays are in the means too)."""
+    rows, err = _rocprof(['--denoise-kernels-only', '--iters', str(iters)])
+    if err:
+        return err
+    out = {}
+    per_entry = {'dn_begin_kernel': 1, 'dn_level_kernel': B, 'dn_filter_kernel': B, 'dn_end_kernel': 1}
+    for row in rows:
+        for name in per_entry:
+            if name in row['Name']:
+                out[name] = dict(calls=int(row['Calls']), us=round(float(row['AverageNs']) / 1e3, 2))
+    if len(out) == len(per_entry):
+        out['kernels_us_per_entry'] = round(sum(out[n]['us'] * k for n, k in per_entry.items()), 2)
+    return out
+
+
+def denoise_case(iters, warmup, rounds, B=4, rocprof=False):
+    """The denoising estimator (defaults: tol 'auto', depth 8) against the SAME RUN's plain bidirectional estimator, the two taking
+    turns; and the new entry alone, with the bytes it has to move."""
+    import gc
+    import torch
+    plain, _ = _estimator('C', B, 'bidirectional', head_scale=0.1)
+    den, mem = _estimator('C', B, 'bidirectional', denoise=True, head_scale=0.1)
+    last = den.denoise_sequence(_noisy_frames(3 * B))[-1]    # the tables of the last replay: a carried frame, B pairs
+    runs = {'plain': plain.graph.replay, 'denoise': den.graph.replay}
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                                # in turn, so that drift of the box hits them alike
+        for k, fn in runs.items():
+            ms[k].append(_time(fn, iters, warmup))
+    out = dict(spec='C', B=B, sequence='bidirectional', rounds=rounds, options=dict(den.denoise))
+    for k in runs:
+        out[k] = _stats([v for r in ms[k] for v in r], B)
+        out[k]['round_means'] = [round(statistics.mean(r) / B, 4) for r in ms[k]]
+    out['denoise']['estimator_MB'] = round(mem / 1e6, 1)
+    out['denoise_over_plain'] = round(out['denoise']['ms_per_pair'] / out['plain']['ms_per_pair'], 4)
+    out['denoise_added_us_per_replay'] = round((out['denoise']['ms_per_pair'] - out['plain']['ms_per_pair']) * B * 1e3, 2)
+    us = [_launches_us(_denoise_call(den), den.dev) for _ in range(rounds)]
+    nbytes = denoise_bytes(B)
+    launches = 2 * B + 2
+    out['kernel'] = dict(us=round(statistics.mean(us), 2), rounds_us=[round(x, 2) for x in us], launches=launches,
+                         compulsory_MB=round(nbytes / 1e6, 2), TBps_of_compulsory=round(nbytes / statistics.mean(us) / 1e6, 3),
+                         us_per_launch=round(statistics.mean(us) / launches, 2),
+                         how='device events around 50 back-to-back calls of the entry (%d launches each), launch gaps included'
+                             % launches)
+    out['last_pair'] = dict(noise=last.noise, tol=last.tol, counts=last.counts)
+    assert not bool(den.den_ws[:B * 256].any())
+    if rocprof:
+        out['kernel']['rocprofv3'] = denoise_rocprof(B)
+    del plain, den
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -820,7 +925,24 @@ def main():
                     help='the stabilising estimator against the same run\'s plain estimator, FlowNetC at B = 4, both sequence modes, '
                          'and unflow_sequence_stabilise alone (DESIGN 7.20)')
     ap.add_argument('--stabilise-kernels-only', choices=('fw', 'bidir'), help=argparse.SUPPRESS)
+    ap.add_argument('--denoise', action='store_true',
+                    help='the denoising estimator against the same run\'s plain bidirectional estimator, FlowNetC at B = 4, and '
+                         'unflow_sequence_denoise alone (DESIGN 7.21)')
+    ap.add_argument('--denoise-kernels-only', action='store_true', help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.denoise_kernels_only:
+        return denoise_kernels_only(a.iters)
+    if a.denoise:
+        res = dict(metric='sequence_denoise_ms_per_pair_over_the_same_runs_plain_bidirectional_estimator', shape=[H, W],
+                   frames='uint8 %dx%d' % FRAME, math='bf16x3', iters=a.iters, warmup=a.warmup,
+                   expected='no time or ratio was predicted: nobody had measured this entry.  From the bytes: two passes per slot '
+                            'over flow, mask, frame and history, one history and one frame written, the history copied in and out '
+                            '— %.1f MB per replay at B = 4, tens of microseconds at HBM rate; the entry is 2 B + 2 dependent '
+                            'launches, so its launch gaps weigh as much' % (denoise_bytes(4) / 1e6),
+                   note='one run on one box; box to box +- 3 %',
+                   cases=[denoise_case(a.iters, a.warmup, a.rounds, rocprof=a.rocprof)])
+        print(json.dumps(res), flush=True)
+        return
     if a.stabilise_kernels_only:
         return stabilise_kernels_only(a.stabilise_kernels_only, a.iters)
     if a.stabilise:

@@ -65,6 +65,8 @@ def lib():
         _lib.unflow_sequence_interpolate_score_workspace_bytes.restype = ctypes.c_size_t
         _lib.unflow_sequence_stabilise.restype = ctypes.c_int
         _lib.unflow_sequence_stabilise_workspace_bytes.restype = ctypes.c_size_t
+        _lib.unflow_sequence_denoise.restype = ctypes.c_int
+        _lib.unflow_sequence_denoise_workspace_bytes.restype = ctypes.c_size_t
         for name in ('unflow_deflate_segment_bound', 'unflow_deflate_stream_bound', 'unflow_deflate_slot_bytes'):
             getattr(_lib, name).restype = ctypes.c_long
         _apply_env_options(_lib)

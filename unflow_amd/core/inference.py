@@ -101,6 +101,15 @@ track kernels and in front of the interpolation either sequence graph runs
 
 (push_stabilised, stabilise_sequence, export_sequence(stabilise=True)); tol, iters and follow travel by value.
 
+sequence='bidirectional' with denoise=True | dict(tol, depth): temporal denoising along a clip.  Behind
+unflow_inference_occlusion the bidirectional sequence graph runs
+
+    unflow_sequence_denoise        the staged frames, the backward flow and the backward occlusion mask of the replay's pairs -> per
+                                   pair the later frame averaged with its own history fetched along the backward flow (a gather,
+                                   integers throughout); the history stays on the device from one replay of the clip to the next
+
+(push_denoised, denoise_sequence, export_sequence(denoise=True)); tol and depth travel by value.
+
 The host side is the same for every mode.  output_buffers lists what a replay can bring back (device buffer, pinned copy, flag);
 _submit / _submit_sequence stage their inputs and end in _replay (run, copy back, the files' scanlines, the slot's event), which
 leaves the replay's rows [(slot row, h, w)] in slot.pending; _one_ahead keeps one replay in flight ahead of the caller; pair_files
@@ -304,7 +313,42 @@ def camera_matrix(words, h, w, path=False):
     return np.concatenate([lin, t[:, None]], axis=1)
 
 
-def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False, mid=0, stab=False):
+# What push_denoised returns per pair (n, n + 1) (unflow_sequence_denoise): frame uint8 [h, w, 3], frame n + 1
+# averaged with its history along the backward flow; noise, the pair's noise level M (the median over the pixels with a history of
+# the L1 distance, three channels summed, between the frame and its prediction, in grey levels, at most 255); tol, the tolerance
+# 0..4 the pair was filtered with (the chosen one with tol='auto'); counts, a dict: eligible (pixels with a history), fresh (pixels
+# without: no usable flow, a source outside the frame, or occluded), rejected (pixels whose history was too far from the frame and
+# was dropped) and history, the mean history count behind the pair (1: nothing averaged, up to depth).
+Denoised = collections.namedtuple('Denoised', ('frame', 'noise', 'tol', 'counts'))
+DENOISE_DEFAULTS = dict(tol='auto', depth=8)
+DENOISE_RANGES = dict(tol=(0, 4), depth=(1, 64))
+
+
+def denoise_option(denoise):
+    """FlowEstimator's denoise option -> None (None or False: no denoising) or dict(tol, depth): True gives DENOISE_DEFAULTS, a dict
+    overrides some of them — tol 'auto' (per pair, from its noise level) or an int in 0..4 (a pixel's history counts half per
+    8 * 2^tol grey levels of L1 distance between it and the frame, and not at all from six halvings on), depth in 1..64 (the
+    largest history count: the longest average).  Anything else: ValueError."""
+    if denoise is None or denoise is False:
+        return None
+    if denoise is True:
+        return dict(DENOISE_DEFAULTS)
+    if not isinstance(denoise, dict) or set(denoise) - set(DENOISE_DEFAULTS):
+        raise ValueError("FlowEstimator: denoise is True or a dict with tol, depth, got %r" % (denoise,))
+    out = dict(DENOISE_DEFAULTS)
+    for key, v in denoise.items():
+        lo, hi = DENOISE_RANGES[key]
+        if key == 'tol' and isinstance(v, str) and v == 'auto':
+            out[key] = v
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("FlowEstimator: denoise['%s'] is %san int in %d..%d, got %r"
+                             % (key, "'auto' or " if key == 'tol' else '', lo, hi, v))
+        out[key] = int(v)
+    return out
+
+
+def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False, mid=0, stab=False, den=False):
     """The files export / export_sequence write for pair n, in the order they are written — _10, _01, _10_occ, then the pictures
     (visual_files' or sequence_visual_files' list) in their file order: [(file name, source)].  A source is
 
@@ -315,7 +359,8 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False
 
     mid: the in-between frames j = 1..mid of the pair, %06d_mid%d.png (pair, j), PNGs of image (j - 1) * B + i of the surface
     'mid', behind the pictures.  stab: the stabilised frame and the residual map of the pair, %06d_stab.png (8-bit RGB, surface
-    'stab') and %06d_motion.png (8-bit grey, surface 'stab_resid'), behind everything else.
+    'stab') and %06d_motion.png (8-bit grey, surface 'stab_resid'), behind those.  den: the denoised frame of the pair,
+    %06d_den.png (8-bit RGB, surface 'den'), behind everything else.
 
     Both back ends of FlowEstimator._write_files and the entries of the replay's unflow_png_filter launch (filter_entries) come
     from this one list, so the span order and the file order cannot drift apart."""
@@ -326,7 +371,8 @@ def pair_files(n, fmt, backward=False, occlusion=False, pictures=(), track=False
     return out + [(name, ('png', 'vis', k)) for k, name in pictures] + \
         [('%06d_mid%d.png' % (n, j), ('png', 'mid', j - 1)) for j in range(1, int(mid) + 1)] + \
         ([('%06d_track.flo' % n, ('track', 'track_disp'))] if track else []) + \
-        ([('%06d_stab.png' % n, ('png', 'stab', 0)), ('%06d_motion.png' % n, ('png', 'stab_resid', 0))] if stab else [])
+        ([('%06d_stab.png' % n, ('png', 'stab', 0)), ('%06d_motion.png' % n, ('png', 'stab_resid', 0))] if stab else []) + \
+        ([('%06d_den.png' % n, ('png', 'den', 0))] if den else [])
 
 
 def filter_entries(files, rows, batch):
@@ -437,14 +483,15 @@ def chunks(it, n):
         yield buf
 
 
-def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=False, stabilise=False):
+def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=False, stabilise=False, denoise=False):
     """The output buffers of a replay, written down once, in the order they are copied back: (the name a slot's pinned copy has
     and `want` asks for, the estimator's attribute of the device buffer, shape, dtype, the estimator flag it needs — None: every
     estimator has it).  Without its flag both attributes are None.  Ncap: the track capacity of a tracking estimator; n_mid: the
     in-between frames per pair of an interpolating one.  ground_truth: also the rows of unflow_sequence_track_score,
     behind the others; their flag, track_gt, needs track and ground_truth both.  held_out: also the rows of
     unflow_sequence_interpolate_score, behind everything else.  stabilise: also the five rows of
-    unflow_sequence_stabilise, behind those."""
+    unflow_sequence_stabilise, behind those.  denoise: also the two rows of unflow_sequence_denoise,
+    last."""
     scored = ()
     if ground_truth:
         scored = (('track_scores', 'out_track_scores', (B, 16), torch.int32, 'track_gt'),
@@ -460,6 +507,9 @@ def output_buffers(B, Hm, Wm, Ncap=0, n_mid=0, ground_truth=False, held_out=Fals
                    ('stab_motion', 'out_stab_motion', (B, 8), torch.int64, 'stabilise'),
                    ('stab_path', 'out_stab_path', (B, 8), torch.int64, 'stabilise'),
                    ('stab_counts', 'out_stab_counts', (B, 4), torch.int32, 'stabilise'))
+    if denoise:
+        scored += (('den', 'out_den', (B, Hm, Wm, 3), torch.uint8, 'denoise'),
+                   ('den_stats', 'out_den_stats', (B, 8), torch.int32, 'denoise'))
     return (('flow', 'out_flow', (B, Hm, Wm, 2), torch.float32, None),
             ('u16', 'out_u16', (B, Hm, Wm, 3), torch.int16, None),
             ('sums', 'sums', (B, 2, 2), torch.float64, None),
@@ -489,7 +539,7 @@ class _Slot:
         # held_out: the truth frames of a replay's pairs, [n_mid][B][Hmax][Wmax][3], fp32-sized like the frames
         self.truth = pin(est.interpolate * B * Hm * Wm * 3 * 4, dtype=torch.uint8) if est.held_out else None
         for name, _, shape, dtype, flag in output_buffers(B, Hm, Wm, est.track_cap, est.interpolate, True, held_out=True,
-                                                          stabilise=True):
+                                                          stabilise=True, denoise=True):
             setattr(self, name, pin(*shape, dtype=dtype) if flag is None or getattr(est, flag) else None)
         self.event = None
         self.pending = None      # the rows of the last replay as ([(slot row i, h, w), ...], nmaps): set by FlowEstimator._replay
@@ -534,6 +584,8 @@ class _Encoder:
             named += [('mid', est.out_mid, est.interpolate * B, 3, _lib.PNG_U8)]
         if est.stabilise:
             named += [('stab', est.out_stab, B, 3, _lib.PNG_U8), ('stab_resid', est.out_stab_resid, B, 1, _lib.PNG_U8)]
+        if est.denoise:
+            named += [('den', est.out_den, B, 3, _lib.PNG_U8)]
         self.index = {name: k for k, (name, *_) in enumerate(named)}
         self.surfaces = [PngSurface(t, images, Hm, Wm, ch, kind) for _, t, images, ch, kind in named]
         n_files = sum(s.images for s in self.surfaces)
@@ -589,11 +641,18 @@ class FlowEstimator:
     reweighted fits behind the first), the pixels that do not follow it, and the later frame resampled along the composed camera
     path (follow = 0: locked on the clip's first frame; s in 1..8: the path loses 2^-s of its offset per pair).  push_stabilised /
     stabilise_sequence return a Stabilised(frame, residual, motion, path, counts) per pair, export_sequence(stabilise=True) writes
-    them; every other method returns what it returns without stabilise.  reset() starts a new path."""
+    them; every other method returns what it returns without stabilise.  reset() starts a new path.
+    denoise (with sequence='bidirectional'): True or dict(tol='auto', depth=8) — temporal noise reduction: every
+    frame of the clip is averaged with its own history, fetched along the backward flow; a pixel without a usable source (no
+    valid flow, a source outside the frame, occluded) starts a new history, one whose history is too far from the frame drops
+    it (tol in 0..4: the distance that halves the history's weight is 8 * 2^tol grey levels; 'auto': chosen per pair from its
+    noise level), and depth in 1..64 bounds the length of the average.  push_denoised / denoise_sequence return a
+    Denoised(frame, noise, tol, counts) per pair, export_sequence(denoise=True) writes the frames; every other method returns what
+    it returns without denoise.  reset() starts a new history."""
 
     def __init__(self, params, batch, net_size=(384, 1280), max_frame=None, device=None, use_graph=True, bidirectional=False,
                  visual=False, sequence=False, track=False, interpolate=None, ground_truth=False, held_out=False,
-                 interpolate_order=None, stabilise=None):
+                 interpolate_order=None, stabilise=None, denoise=None):
         if not isinstance(sequence, bool) and sequence != 'bidirectional':
             raise ValueError("FlowEstimator: sequence is False, True or 'bidirectional', got %r" % (sequence,))
         if sequence and bidirectional:
@@ -625,6 +684,11 @@ class FlowEstimator:
         if self.stabilise and not sequence:
             raise ValueError("FlowEstimator: stabilise fits the camera motion along a clip; it needs sequence=True or "
                              "sequence='bidirectional'")
+        self.denoise = denoise_option(denoise)                   # temporal denoising along the clip; None: none
+        if self.denoise and sequence != 'bidirectional':
+            raise ValueError("FlowEstimator: denoise averages a frame with its history, which is fetched along the backward flow "
+                             "and dropped under the backward occlusion mask; it needs sequence='bidirectional' (got sequence=%r)"
+                             % (sequence,))
         self.ground_truth = bool(ground_truth)                   # sequence: the clip's pairs are scored
         if self.ground_truth and not sequence:
             raise ValueError("FlowEstimator: ground_truth scores the pairs of a clip; it needs sequence=True or "
@@ -663,7 +727,7 @@ class FlowEstimator:
             self.partial = z(B * nb * 6, dtype=torch.float64)
             self.ticket = z(B, dtype=torch.int32)
             for _, attr, shape, dtype, flag in output_buffers(B, Hm, Wm, self.track_cap, self.interpolate, True,
-                                                              held_out=True, stabilise=True):     # out_flow, out_u16, ...
+                                                              held_out=True, stabilise=True, denoise=True):     # out_flow, ...
                 setattr(self, attr, z(*shape, dtype=dtype) if flag is None or getattr(self, flag) else None)
             self.track_anchors = self.track_disp = self.track_alive = None
             if self.track:
@@ -700,6 +764,13 @@ class FlowEstimator:
                 self.stab_path = z(8, dtype=torch.int64)
                 self.stab_identity = torch.tensor([0, 1 << 24, 0, 0, 0, 1 << 24, 0, 0], dtype=torch.int64, device=self.dev)
                 self.stab_ws = z(int(L.unflow_sequence_stabilise_workspace_bytes(B)) // 8, dtype=torch.int64)
+            self.den_state = self.den_ws = None
+            if self.denoise:
+                # unflow_sequence_denoise: the history (an 8.8 colour and a count per pixel), kept from one replay of a clip to the
+                # next (re-initialised on the device while the carry source is 0: reset() needs no memset), and its workspace —
+                # the histograms, zero now and left zero by every launch, then the two history slabs
+                self.den_state = z(Hm, Wm, 4, dtype=torch.int16)
+                self.den_ws = z(int(L.unflow_sequence_denoise_workspace_bytes(B, Hm, Wm)) // 4, dtype=torch.int32)
             self.vis_shown = self.vis_max = None
             if self.visual:
                 # the frames as shown: resized to the network and back; sequence: one per engine row, row 0 carried
@@ -765,7 +836,7 @@ class FlowEstimator:
     def _launch_sequence(self):
         """Carry, input of the new frames, forward pass, output kernel over the pair table (what the sequence graph holds);
         sequence='bidirectional': the output kernel on either block of the engine's 2B rows, then the occlusion kernel, all
-        three over the pair table and without ground truth; track: then the tracks, through the pairs of the table; interpolate:
+        three over the pair table and without ground truth (denoise: then the denoised frames); track: then the tracks, through the pairs of the table; interpolate:
         then the in-between frames of those pairs (held_out: and their scores where the table says held); visual: then the pictures, from the same tables."""
         e, B = self.engine, self.B
         L = _lib.lib()
@@ -778,6 +849,12 @@ class FlowEstimator:
             self._output(fw, pairs, self.out_flow, self.out_u16, gt=self.ground_truth)
             self._output(bw, pairs, self.out_flow_bw, self.out_u16_bw)
             self._occlusion(pairs, self.gt_mask if self.ground_truth else None)
+            if self.denoise:
+                o = self.denoise
+                check(L.unflow_sequence_denoise(ptr(self.frames), ptr(self.tab), B, self.Hmax, self.Wmax, ptr(self.out_flow_bw),
+                                                ptr(self.occ[1]), -1 if o['tol'] == 'auto' else o['tol'], o['depth'],
+                                                ptr(self.den_state), ptr(self.den_ws), ptr(self.out_den), ptr(self.out_den_stats),
+                                                e.stream()), "sequence_denoise")
         else:
             self._output(self.flow_src, pairs, self.out_flow, self.out_u16, gt=self.ground_truth)
         if self.track:
@@ -1008,7 +1085,7 @@ class FlowEstimator:
         special = {'sums': nmaps > 0, 'counts': nmaps > 0, 'occ_counts': 'occ_counts' in want and nmaps == 2}
         nv = self._num_pictures(nmaps)
         for name, attr, *_ in output_buffers(self.B, self.Hmax, self.Wmax, self.track_cap, self.interpolate, True, held_out=True,
-                                                 stabilise=True):
+                                                 stabilise=True, denoise=True):
             if special.get(name, name in want):
                 dst, src = getattr(slot, name), getattr(self, attr)
                 if name == 'vis':
@@ -1051,7 +1128,7 @@ class FlowEstimator:
 
     # ------------------------------------------------------------------------------------------ public API
     def _mode(self, what, sequence, bidirectional=False, visual=False, track=False, interpolate=False, ground_truth=False,
-              held_out=False, stabilise=False):
+              held_out=False, stabilise=False, denoise=False):
         """The guard of public method `what`: RuntimeError unless this is a pair (sequence False) or a sequence estimator, and
         one built with both directions / with pictures where the method needs them; the message names the constructor flags."""
         if not sequence:
@@ -1087,6 +1164,9 @@ class FlowEstimator:
             raise RuntimeError("%s: a sequence estimator without camera motion; build it with FlowEstimator(..., sequence=%r, "
                                "stabilise=True) (or stabilise=dict(tol=2, iters=3, follow=0))"
                                % (what, 'bidirectional' if self.seq_bidir else True))
+        if denoise and not self.denoise:
+            raise RuntimeError("%s: a sequence estimator without denoising; build it with FlowEstimator(..., "
+                               "sequence='bidirectional', denoise=True) (or denoise=dict(tol='auto', depth=8))" % what)
 
     def _visual_spelling(self):
         """How to build this sequence estimator with pictures, for the messages that ask for it."""
@@ -1378,6 +1458,8 @@ class FlowEstimator:
                             write_png_rgb8(path, slot.stab.numpy()[i, :h, :w])
                         elif attr == 'stab_resid':
                             write_png_gray8(path, slot.stab_resid.numpy()[i, :h, :w])
+                        elif attr == 'den':
+                            write_png_rgb8(path, slot.den.numpy()[i, :h, :w])
                         else:
                             write_kitti_flow_png(path, getattr(slot, attr).numpy()[i, :h, :w].view(np.uint16))
                         paths.append(path)
@@ -1759,6 +1841,36 @@ class FlowEstimator:
             out += self._stabilised_of(slot, rows)
         return out
 
+    # temporal denoising
+    DEN_WANT = ('den', 'den_stats')
+
+    @staticmethod
+    def _denoised_of(slot, rows):
+        """The rows of a finished denoising replay as Denoised tuples (copies)."""
+        d, s = (getattr(slot, name).numpy() for name in FlowEstimator.DEN_WANT)
+        return [Denoised(d[i, :h, :w].copy(), int(s[i, 1]), int(s[i, 0]),
+                         dict(eligible=int(s[i, 2]), fresh=int(s[i, 3]), rejected=int(s[i, 4]), history=int(s[i, 5]) / float(h * w)))
+                for i, h, w in rows]
+
+    def push_denoised(self, frames):
+        """push's frames on an estimator built with denoise: one Denoised(frame, noise, tol, counts) per new pair (the count is
+        push's).  For the pair (n, n + 1): frame, frame n + 1 averaged with the history of the clip up to frame n, fetched along
+        the pair's backward flow — four taps at 1/64 px, 8.8 colours; noise, the pair's noise level M; tol, the tolerance it was
+        filtered with; counts, dict(eligible, fresh, rejected, history): the pixels that had a history, those that started a new
+        one (no usable flow, a source outside the frame, or occluded in frame n), those whose history was dropped because it was
+        too far from the frame, and the mean history count behind the pair.  The clip's first frame is its own denoised frame
+        and is not returned.  Bit-reproducible from run to run.  reset() starts a new history."""
+        self._mode('push_denoised', sequence=True, denoise=True)
+        return self._denoised_of(*self._push(frames, self.DEN_WANT))
+
+    def denoise_sequence(self, frames):
+        """Temporal denoising along a clip: T >= 2 frames -> T - 1 Denoised tuples (push_denoised's), of frames 1 .. T - 1."""
+        self._mode('denoise_sequence', sequence=True, denoise=True)
+        out = []
+        for slot, rows, _ in self._pipeline_sequence(frames, self.DEN_WANT):
+            out += self._denoised_of(slot, rows)
+        return out
+
     # held-out scores of the in-between frames (DESIGN 7.18)
     HELD_WANT = ('mid', 'mid_holes', 'mid_sse', 'mid_ssim')
 
@@ -1954,7 +2066,7 @@ class FlowEstimator:
         return out
 
     def export_sequence(self, frames, out_dir, fmt='png', workers=0, level=6, deflate='host', backward=False, occlusion=False,
-                        visual=False, max_flow=None, tracks=False, interpolate=False, stabilise=False):
+                        visual=False, max_flow=None, tracks=False, interpolate=False, stabilise=False, denoise=False):
         """estimate_sequence's flows as files: out_dir/%06d_10.png (KITTI 16-bit RGB) or out_dir/%06d_10.flo for pair n (frame n
         -> frame n + 1), with export's writers.  Returns the written paths.  workers, level: as for export (0: the host
         writers; >= 1: the row filters on the device and a writer pool; the captured graph is the same one).  deflate: as for
@@ -1975,7 +2087,10 @@ class FlowEstimator:
         stabilise (an estimator built with stabilise): behind a pair's other files %06d_stab.png, the stabilised frame of
         push_stabilised (8-bit RGB), and %06d_motion.png, its residual map (8-bit grey, quarter pixels) — through any writer, the
         same pixels; behind the last pair's files one camera.npz with motion [T - 1, 8], path [T - 1, 8], counts [T - 1, 4] and
-        matrix [T - 1, 2, 3], camera_matrix of every pair's motion."""
+        matrix [T - 1, 2, 3], camera_matrix of every pair's motion.
+        denoise (an estimator built with denoise): behind everything else of a pair %06d_den.png, the denoised frame of
+        push_denoised (8-bit RGB; pair n's is frame n + 1) — through any writer, the same pixels.  The clip's first frame is its
+        own denoised frame and is not written."""
         from .png_device import check_deflate_mode
         self._mode('export_sequence', sequence=True)
         if tracks and not self.track:
@@ -1994,12 +2109,15 @@ class FlowEstimator:
         if stabilise and not self.stabilise:
             raise ValueError("export_sequence: the stabilised frames need FlowEstimator(..., sequence=%r, stabilise=True)"
                              % ('bidirectional' if self.seq_bidir else True))
+        if denoise and not self.denoise:
+            raise ValueError("export_sequence: the denoised frames need FlowEstimator(..., sequence='bidirectional', denoise=True)")
         if max_flow is not None and not visual:
             raise ValueError("export_sequence: max_flow scales the flow colours of the pictures; it needs visual=True")
 
         def plan(n, nmaps):
             return pair_files(n, fmt, backward, occlusion, sequence_visual_files(n, self.seq_bidir) if visual else (),
-                              track=dense, mid=self.interpolate if interpolate else 0, stab=bool(stabilise))
+                              track=dense, mid=self.interpolate if interpolate else 0, stab=bool(stabilise),
+                              den=bool(denoise))
         dense = bool(tracks) and self.track_spec[0] == 'dense'
         sparse = [] if tracks and not dense else None      # sparse anchors: the Track of every pair, for tracks.npz
         camera = [] if stabilise else None                 # (motion, path, counts, matrix) of every pair, for camera.npz

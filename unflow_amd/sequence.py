@@ -5,6 +5,7 @@ once (core/inference.FlowEstimator(..., sequence=True)).
                                   [--output_backward] [--occlusion] [--visual] [--max_flow F]
                                   [--track] [--track_stride S] [--track_points FILE] [--interpolate N [--order K] [--held_out]]
                                   [--stabilise [--stabilise_tol K] [--stabilise_iters R] [--stabilise_follow S]]
+                                  [--denoise [--denoise_tol {auto,0..4}] [--denoise_depth D]]
 
 The frames are the 8-bit RGB PNG files of DIR in sorted order, all of one size; pair n is (frame n, frame n + 1).  They are
 inflated by a thread pool and decoded on the device, one launch per replay's frames (--host_decode: the host decoder).  The
@@ -31,7 +32,12 @@ subsampled clip, pairs numbered along it.
 (black where the path leaves the frame), %06d_motion.png, every pixel's distance from the pair's dominant motion in quarter pixels
 (the independently moving objects), and one camera.npz (motion, path, counts, matrix per pair).  --stabilise_tol K (0..4, default
 2): the weight of a pixel halves per 2^(1 - K) px of residual; --stabilise_iters R (0..4, default 3): reweighted fits behind the
-first; --stabilise_follow S (0..8, default 0 = lock on the first frame): the path loses 2^-S of its offset per pair."""
+first; --stabilise_follow S (0..8, default 0 = lock on the first frame): the path loses 2^-S of its offset per pair.
+--denoise (with --output_backward or --occlusion: it needs both directions along the clip) adds %06d_den.png per pair (DESIGN
+7.21): frame n + 1 averaged with its own history, fetched along the backward flow; the clip's first frame is its own denoised
+frame and is not written.  --denoise_tol (auto, the default, or 0..4): the distance between a pixel and its history that halves the
+history's weight is 8 * 2^tol grey levels, auto chooses it per pair from the pair's noise level; --denoise_depth D (1..64, default
+8): the longest average."""
 import argparse
 import os
 import sys
@@ -172,6 +178,14 @@ def parser():
                     help='with --stabilise: reweighted fits behind the first (0..4, default 3)')
     ap.add_argument('--stabilise_follow', type=int, default=None, metavar='S',
                     help='with --stabilise: the path loses 2^-S of its offset per pair (1..8); 0, the default, locks on the first frame')
+    ap.add_argument('--denoise', action='store_true',
+                    help='also %%06d_den.png per pair: frame n + 1 averaged with its history along the backward flow; needs both '
+                         'directions along the clip (--output_backward or --occlusion)')
+    ap.add_argument('--denoise_tol', default=None, metavar='{auto,0..4}',
+                    help="with --denoise: 8 * 2^tol grey levels between a pixel and its history halve the history's weight; auto "
+                         "(the default): per pair, from its noise level")
+    ap.add_argument('--denoise_depth', type=int, default=None, metavar='D',
+                    help='with --denoise: the longest average, in frames (1..64, default 8)')
     ap.add_argument('--config', default='../config.ini', help='the project config.ini (dirs: log, checkpoints)')
     ap.add_argument('--host_decode', action='store_true', help="decode the frames with the host's PNG decoder (slow)")
     from .evaluate import add_encode_flags
@@ -209,6 +223,24 @@ def parse_args(argv=None):
             if not STABILISE_RANGES[k][0] <= v <= STABILISE_RANGES[k][1]:
                 ap.error("--stabilise_%s is an integer in %d..%d" % ((k,) + STABILISE_RANGES[k]))
         a.stabilise_option = given or True
+    a.denoise_option = None                       # FlowEstimator's denoise
+    for k in ('tol', 'depth'):
+        if getattr(a, 'denoise_' + k) is not None and not a.denoise:
+            ap.error("--denoise_%s sets the temporal filter: it needs --denoise" % k)
+    if a.denoise:
+        if not (a.output_backward or a.occlusion):
+            ap.error("--denoise fetches a frame's history along the backward flow: it needs both directions along the clip; add "
+                     "--output_backward or --occlusion")
+        given = {}
+        if a.denoise_tol is not None:
+            if a.denoise_tol != 'auto' and a.denoise_tol not in ('0', '1', '2', '3', '4'):
+                ap.error("--denoise_tol is auto or an integer in 0..4")
+            given['tol'] = a.denoise_tol if a.denoise_tol == 'auto' else int(a.denoise_tol)
+        if a.denoise_depth is not None:
+            if not 1 <= a.denoise_depth <= 64:
+                ap.error("--denoise_depth is an integer in 1..64")
+            given['depth'] = a.denoise_depth
+        a.denoise_option = given or True
     if a.track_stride is not None and a.track_stride < 1:
         ap.error("--track_stride must be at least 1")
     if a.track_points is not None and (a.track or a.track_stride is not None):
@@ -275,7 +307,7 @@ def main(argv=None):
                                         sequence='bidirectional' if (a.output_backward or a.occlusion) else True,
                                         visual='sequence' if a.visual else False, track=a.track_option,
                                         interpolate=a.interpolate, held_out=a.held_out, interpolate_order=a.order,
-                                        stabilise=a.stabilise_option)
+                                        stabilise=a.stabilise_option, denoise=a.denoise_option)
     out_dir = os.path.join(a.out, a.ex)
     print("-- %s (step %s): %d frames of %dx%d from %s" % (a.ex, est.global_step, len(a.files), a.frame_size[0], a.frame_size[1],
                                                            a.frames))
@@ -292,7 +324,8 @@ def main(argv=None):
         paths = est.export_sequence(frames, out_dir, fmt='flo' if a.flo else 'png', workers=a.encode_workers, level=a.level,
                                     deflate=a.deflate, backward=a.output_backward, occlusion=a.occlusion, visual=a.visual,
                                     max_flow=a.max_flow, tracks=a.track_option is not False,
-                                    interpolate=a.interpolate is not None, stabilise=a.stabilise)
+                                    interpolate=a.interpolate is not None, stabilise=a.stabilise,
+                                    denoise=a.denoise)
     except ValueError as err:
         raise SystemExit("Error: %s" % err)
     print("wrote %d files to %s" % (len(paths), out_dir))
