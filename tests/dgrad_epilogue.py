@@ -44,18 +44,26 @@ def edge_channels(N, lo, hi):
 def act_field(shape, lo, hi, key):
     """(act, where, special): an fp32 activation [B,H,W,N] (numpy) of normal numbers in +-[0.5, 1.5), half of them negative, with
     SPECIALS[i] planted at the pixels i and npix - 1 - i (flat pixel order: the first and the last pixel included) of every
-    channel of edge_channels(N, lo, hi); where: the list of (pixel, channel, index into SPECIALS); special: bool mask of them."""
+    channel of edge_channels(N, lo, hi); where: the list of (pixel, channel, index into SPECIALS); special: bool mask of them.
+    An image of fewer than 2 len(SPECIALS) pixels (the smallest flow-head cases of tests/head_cases.py) takes npix // 8 specials per
+    edge channel, every edge channel another stretch of the table, and EXACTLY half of its pixels negative in every channel (a fair
+    coin over 6 pixels would leave assert_conditions to luck)."""
     B, H, W, N = shape
     g = E.gen('act', key, tuple(shape), lo, hi)
     mag = 0.5 + torch.rand(shape, generator=g, dtype=torch.float64)
     act = (mag * E._sign(shape, g)).float().numpy().reshape(B * H * W, N).copy()
     special = np.zeros(act.shape, dtype=bool)
     npix, K = act.shape[0], len(SPECIALS)
-    assert npix >= 2 * K, "too few pixels for the specials table"
+    if npix < 2 * K:
+        K = npix // 8
+        rank = torch.rand((npix, N), generator=g).argsort(0).argsort(0).numpy()
+        act = (np.abs(act) * np.where(rank < (npix + 1) // 2, -1.0, 1.0)).astype(np.float32)
     where = []
-    for c in edge_channels(N, lo, hi):
-        for i, (_, v) in enumerate(SPECIALS):
-            for px in (i, npix - 1 - i):
+    for j, c in enumerate(edge_channels(N, lo, hi)):
+        for i in range(K):
+            i = (j * K + i) % len(SPECIALS)
+            v = SPECIALS[i][1]
+            for px in (i % K, npix - 1 - i % K):
                 act[px, c] = v
                 special[px, c] = True
                 where.append((px, c, i))
@@ -231,10 +239,14 @@ ROWS = [
     # forces the gather kernel (6 blocks, one K tile: unsplit, the inline epilogue).
     ("inline_gather", 'f32', dict(), (2, 12, 16, 256, 32, 1, 1), False, 3),
     ("inline_reduce", 'f32', dict(), (8, 6, 8, 512, 1024, 3, 2), False, 3),            # vector reduce kernel; scalar one with pitch N + 1
-    # W % 4 == 0 in every Cout = 2 case of the tables: the strip kernel.  The per-pixel (skinny) kernel is what an activation of
-    # pitch N + 1 falls back to.
+    # Cout = 2 heads (tests/head_cases.py): W % 4 == 0 and fewer than 16384 pixels: strips of 4; an activation of pitch N + 1 falls
+    # back to the per-pixel (skinny) kernel.
     ("head_strip", 'f32', dict(), (2, 6, 8, 1028, 2, 3, 1), False, 3),
     ("head_strip_196", 'f32', dict(), (2, 12, 16, 196, 2, 3, 1), False, 3),
+    # 16896 pixels, W % 8 == 0: strips of 8, whose range test is quad-granular (n + 3 >= act_lo && n < act_hi, then per element)
+    ("head_tile8", 'f32', dict(), (2, 66, 128, 196, 2, 3, 1), False, 3),
+    # W % 4 != 0: the per-pixel kernel at every pitch
+    ("head_skinny", 'f32', dict(), (1, 10, 14, 196, 2, 3, 1), False, 3),
     ("pointwise", 'f32', dict(), (2, 12, 16, 256, 32, 1, 1), False, 3),
 ]
 FORCE_PITCH = {"inline_gather"}                     # rows whose fp32 activation always has pitch N + 1

@@ -33,8 +33,9 @@ CONV_CASES = [
     (8, 6, 8, 512, 1024, 3, 2),    # conv6 size: split-K path
     (8, 6, 8, 1024, 1024, 3, 1),   # conv6_1: split-K
     (1, 10, 14, 36, 40, 3, 1),     # odd sizes, N tail
-    (2, 6, 8, 1026, 2, 3, 1),      # flow5 head: skinny kernels
+    (2, 6, 8, 1026, 2, 3, 1),      # flow5 head: W % 4 == 0, the strip kernels (S = 4)
     (2, 12, 16, 194, 2, 3, 1),     # flow2 head
+    (2, 5, 7, 1026, 2, 3, 1),      # flow6 of a 320 x 448 input: W % 4 != 0, the per-pixel (skinny) kernels
 ]
 
 

@@ -126,7 +126,9 @@ def run_forward(regime, case, dev, P, deconv=False, leaky=False, entry='pl'):
         L.conv2d_fwd(X.t, wd, bd, Yv.t, stride, leaky)
     assert_exact(Yv.t, want, "forward %s" % regime)
     assert torch.all(Y.t[..., Cout:] == 7.0)                                  # neighbours of the written slice untouched
-    if entry == 'pl':                                                         # the output planes re-sum to the fp32 output
+    if entry == 'pl' and Cout <= 4 and not deconv:                            # the flow heads (conv_igemm.hip) write no planes at all
+        assert not Y.pl.any()
+    elif entry == 'pl':                                                       # the output planes re-sum to the fp32 output
         got_pl = planes_value(Y.pl.cpu())[..., :Cout]
         if P == 3:
             assert torch.equal(got_pl, want)
@@ -134,7 +136,8 @@ def run_forward(regime, case, dev, P, deconv=False, leaky=False, entry='pl'):
             assert torch.equal(got_pl.float(), want.float().half().float())
 
 
-def run_dgrad(regime, case, dev, P, deconv=False, entry='pl', scale=0.0):
+def run_dgrad(regime, case, dev, P, deconv=False, entry='pl', scale=0.0, hi=None):
+    """hi: end of the activated range [0, hi) — default the aligned half of the channels (a four-channel flow-head case passes 2)."""
     from unflow_amd.core import layers as L
     B, H, W, Cin, Cout, k, stride = case
     dz, w, ref = _dgrad_problem(regime, case, deconv)
@@ -143,11 +146,13 @@ def run_dgrad(regime, case, dev, P, deconv=False, entry='pl', scale=0.0):
     assert_gpu_planes(DZ, dz, regime, 0)
     g = E.gen('base', regime, case)
     base = E.ints((B, H, W, Cin), g, -3, 3) * E.GRANULE[regime]
-    hi = Cin // 2 // 4 * 4
+    hi = Cin // 2 // 4 * 4 if hi is None else hi
+    tiny = deconv and Cin == 2 and Cout == 2                                  # the 2 -> 2 conv_transpose refuses a derivative
     s = base + ref                                                            # |base + ref| stays below 2^22 granules: exact
     # a real derivative (tests/dgrad_epilogue.py): about half of the activations negative, the specials planted in channels 0, hi - 1, hi
     act, _, special = D.act_field((B, H, W, Cin), 0, hi, (regime, case))
-    D.assert_conditions(act, s, 0, hi, "%s %s" % (regime, case))
+    if not tiny:                                                              # (its activation is never passed)
+        D.assert_conditions(act, s, 0, hi, "%s %s" % (regime, case))
     want = D.expected(s, D.slope_f32(act), 0, hi)                             # inside [0, hi): fl32((base + ref) * slope), one fp32 multiply
     A = make_pt(torch.from_numpy(act), dev, P) if entry == 'pl' else L.PT(torch.from_numpy(act).to(dev))
 
@@ -167,7 +172,6 @@ def run_dgrad(regime, case, dev, P, deconv=False, entry='pl', scale=0.0):
         call = lambda d, **kw: L.conv2d_transpose_bwd_data(DZ.t, wd, d.t, **kw)             # noqa: E731
     else:
         call = lambda d, **kw: L.conv2d_bwd_data(DZ.t, wd, d.t, stride, **kw)               # noqa: E731
-    tiny = deconv and Cin == 2 and Cout == 2                                  # the 2 -> 2 conv_transpose refuses a derivative
     call(v, accumulate=False)
     call(v2, accumulate=True, **({} if tiny else dict(act_src=A.t, act_lo=0, act_hi=hi)))
     assert_exact(v.t, ref, "data gradient %s" % regime)
@@ -180,7 +184,7 @@ def run_dgrad(regime, case, dev, P, deconv=False, entry='pl', scale=0.0):
     # the derivative from the first operand plane of an activation that has no fp32 copy: the reference is slope_bits of the plane bits
     # the kernel reads
     DX3, v3 = dest(True)
-    if not deconv and k == 1 and stride == 1 and Cout == 32 and hi:           # the pointwise kernel of conv_igemm.hip reads no planes
+    if not deconv and (Cout <= 4 or (k == 1 and stride == 1 and Cout == 32)) and hi:   # the fp32-operand kernels of conv_igemm.hip (pointwise, flow heads) read no planes
         with pytest.raises(_lib_error()) as e:
             call(v3, accumulate=True, act_src=A, act_lo=0, act_hi=hi, act_planes=True)
         assert e.value.status == -7                                           # UNFLOW_ERR_UNSUPPORTED, nothing launched
@@ -211,7 +215,8 @@ def run_wgrad(regime, case, dev, P, entry='pl', scale=0.0):
     DZ = scaled_pt(dz.float(), dev, scale) if scale else make_pt(dz.float(), dev, P)
     assert_gpu_planes(X, x, regime, 0)
     assert_gpu_planes(DZ, dz, regime, 1)
-    dw = torch.full(tuple(ref.shape), float('nan'), device=dev)               # every element must be written
+    guard = torch.full((ref.numel() + 128,), float('nan'), device=dev)        # every element must be written, and nothing beside them
+    dw = guard[64:64 + ref.numel()].view(tuple(ref.shape))
     if entry == 'pl' and deconv:
         L.deconv_bwd_filter(X, DZ, dw)
     elif entry == 'pl':
@@ -221,6 +226,7 @@ def run_wgrad(regime, case, dev, P, entry='pl', scale=0.0):
     else:
         L.conv2d_bwd_filter(X.t, DZ.t, dw, None, stride)
     assert_exact(dw, ref, "filter gradient %s" % regime)
+    assert torch.isnan(guard[:64]).all() and torch.isnan(guard[64 + ref.numel():]).all()
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
